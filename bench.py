@@ -9,13 +9,22 @@ loop of reference main.py:641-650 on HBM-resident data: device get_batch (+-1 ra
 900k-row training streams, start indices, window gather), forward, loss, backward, gradient
 all-reduce (N > 1), fused AdamW.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c1|target|c3|c4] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c1|target|c3|c4] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline]]
+
+A plain run sets up, warms up, times the K steps and prints the result line. `--full` adds the legs
+that take runs of their own after the timed region: the probed steps (per-family kernel times,
+roofline, main-stream family), the serial (side stream off) probed steps, the bit-exact get_batch
+loops and the CPU baseline; without it their keys in the result line are null / empty.
+`--dump-outputs DIR` writes what the last timed step computed (dump_outputs) as DIR/<name>.npy; in such a
+run that step starts from the initial parameters and a fresh optimizer, so its outputs depend on the
+arguments alone (`final_loss` is then that step's loss, not the trained one).
 
 Multi-GPU: one rank per GPU, RCCL ("nccl") all-reduce of the flat gradient, weak scaling (fixed
 batch per GPU). Launched by torch.distributed.run (the driver's line), or, when `--gpus N > 1` is
 given without it, this process starts that launcher itself (launch_plan) before touching a GPU.
 
-Roofline: the engine times every launch matching the probe patterns (default: all weight-gradient
+Roofline (--full): the engine times every launch matching the probe patterns (default: all weight-gradient
 GEMMs, attention forward / backward, ffn0, the ffn2 data gradient, the other data gradients) with HIP
 events on the stream it runs on, over --probe-steps live steps run AFTER the timed region (the timed
 steps carry no events), and reports each family's algorithmic flops / bytes per launch over that time; `roofline` is the family with the largest measured time per step, `kernels` all of them.
@@ -194,6 +203,34 @@ def cpu_baseline(cfg, data, seconds):
                       f"({t_batch:.2f} s)"}
 
 
+DUMP_BUDGET_BYTES = 48 << 20  # all of --dump-outputs, float32 (the limit for one dump is 64 MB)
+
+
+def dump_outputs(out_dir, logits, losses, model):
+    """What the last timed step handed its caller, as float32 <name>.npy under out_dir: the per-modality
+    losses (`losses`), each modality's logits (`logits_<i>`), the gradient the backward left
+    (`grad`) and the parameters after the AdamW update (`params`), the last two as the flat vectors.
+    An array larger than its equal share of DUMP_BUDGET_BYTES is written as a fixed sample: the
+    elements at sorted indices drawn without replacement by numpy's default_rng(0) (a function of the
+    array's size alone, so two builds sample the same elements). The dumped step's inputs
+    (data, batch, dropout seed, and the initial parameters and fresh optimizer main() puts back before
+    it) are fixed by the arguments, so two runs agree bitwise in losses and logits and to the order
+    of the backward's float atomics in grad and params (rel-L2 6e-8 and 9e-10 measured at C1)."""
+    import numpy as np
+    arrays = {"losses": torch.stack([l.detach() for l in losses])}
+    for i, lg in enumerate(logits):
+        arrays[f"logits_{i}"] = lg.detach()
+    arrays["grad"] = model.flat_params.grad.detach()
+    arrays["params"] = model.flat_params.detach()
+    cap = DUMP_BUDGET_BYTES // 4 // len(arrays)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.to(torch.float32).cpu().numpy()
+        if a.size > cap:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, size=cap, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def launch_plan(n, argv, port):
     """Command the parent runs when `--gpus N > 1` is asked without a torch.distributed launcher:
     one rank per GPU (the driver's own launch line), started before this process touches a GPU."""
@@ -223,6 +260,12 @@ def main():
     ap.add_argument("--bucket-mb", type=int, default=32, help="DP gradient all-reduce bucket size")
     ap.add_argument("--precision", default=None, choices=["bf16", "fp8"],
                     help="compute precision (default: fp8 for c4 as BASELINE configs[4] names it, else bf16)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's losses, logits, gradient and updated parameters as "
+                         "DIR/<name>.npy (float32; fixed seeded samples of the large ones)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs after the timed region: probed steps (kernels, roofline), serial probed "
+                         "steps, bit-exact get_batch loops, CPU baseline (the options below size them)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=20.0)
     ap.add_argument("--probe-steps", type=int, default=8,
@@ -232,6 +275,10 @@ def main():
     ap.add_argument("--exact-steps", type=int, default=20,
                     help="steps timed with the bit-exact device get_batch (reference RNG streams) after the main run")
     args = ap.parse_args()
+    if not args.full:
+        # a plain run ends with its timed steps: none of the legs that take steps of their own
+        args.probe_steps = args.serial_steps = args.exact_steps = 0
+        args.no_cpu_baseline = True
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # one rank per GPU, launched before this process makes any GPU call; exit with its status
@@ -282,9 +329,17 @@ def main():
     batcher = TU.DeviceBatcher(data["train"], data["val"], V, [p[2] for p in data["params"]], data["file_lengths"],
                                data["is_percents"], T, B, dev, seed=1000 + rank)
 
+    last_logits = [None]  # the last step's logits, for --dump-outputs
+    # --dump-outputs: the gradient's float-atomic column sums add in arrival order (tests/test_gpu_determinism.py),
+    # so parameters trained for more than one step differ run to run, from the second step on at the
+    # bf16 rounding of the forward. The dumped step therefore starts from the state the arguments fix:
+    # the initial parameters and a fresh optimizer, put back just before the last timed step; its
+    # batch and dropout seed are functions of the step count alone.
+    init_params = model.flat_params.detach().clone() if args.dump_outputs else None
+
     def step():
         xb, yb = batcher.next("train", 1)
-        _, losses = model(xb, yb)
+        last_logits[0], losses = model(xb, yb)
         opt.zero_grad(set_to_none=True)
         sum(losses).backward()  # DP: the gradient comes back already averaged over ranks
         opt.step()
@@ -302,11 +357,15 @@ def main():
     # kernel times come from separate probed steps after the timed region
     t0 = time.perf_counter()
     for i in range(args.steps):
+        if init_params is not None and i == args.steps - 1:
+            with torch.no_grad():
+                model.flat_params.copy_(init_params)
+            opt.state.clear()
         losses = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
-    t1 = time.perf_counter()
+    t1 =time.perf_counter()
     dt = t1 - t0
     if world > 1:
         tt = torch.tensor([dt], device=dev)
@@ -314,16 +373,20 @@ def main():
         dt = float(tt.item())
     peaks = {lb: PEAK_TFLOPS_FP8 for lb in FP8_LABELS} if precision == "fp8" else {}
     final_loss = float(sum(l.item() for l in losses))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_logits[0], losses, model)
     # live per-family kernel times: every launch whose label matches a probe pattern bracketed by HIP
     # events on the stream it runs on, over --probe-steps steps (side stream on, as in the timed loop;
     # the event pairs are made by mmt_probe_set, outside these steps)
-    L_.mmt_probe_set(model._ctx, ",".join(probes).encode())
-    L_.mmt_probe_enable(model._ctx, 1)
-    for _ in range(args.probe_steps):
-        step()
-    torch.cuda.synchronize()
-    kernels = read_probes(L_, model._ctx, probes, args.probe_steps, args.config, peaks)
-    L_.mmt_probe_set(model._ctx, None)
+    kernels = []
+    if args.probe_steps > 0:
+        L_.mmt_probe_set(model._ctx, ",".join(probes).encode())
+        L_.mmt_probe_enable(model._ctx, 1)
+        for _ in range(args.probe_steps):
+            step()
+        torch.cuda.synchronize()
+        kernels = read_probes(L_, model._ctx, probes, args.probe_steps, args.config, peaks)
+        L_.mmt_probe_set(model._ctx, None)
     if args.serial_steps > 0 and world == 1:
         # the same families with the side stream off (weight gradients and keep bits on the main
         # stream): each launch has the chip to itself, so these are the per-kernel rates the live

@@ -18,6 +18,32 @@ def test_launch_plan_one_rank_per_gpu():
     assert cmd[-5:] == [os.path.join(REPO, "bench.py"), "--gpus", "8", "--steps", "5"]
 
 
+def test_dump_outputs_writes_float32_within_budget(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+    from types import SimpleNamespace
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 4 * 5 * 1000)  # 5 arrays: 1000 elements each
+    g = torch.Generator().manual_seed(0)
+    flat = torch.randn(4321, generator=g, dtype=torch.float64)
+    flat.grad = torch.randn(4321, generator=g, dtype=torch.float64)
+    logits = [torch.randn(2, 3, 7, generator=g), torch.randn(5, 40, 9, generator=g)]
+    losses = [torch.tensor(1.5), torch.tensor(0.25)]
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), logits, losses, SimpleNamespace(flat_params=flat))
+    got = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in ("losses", "logits_0", "logits_1", "grad", "params")}
+    assert sorted(os.listdir(tmp_path / "a")) == sorted(n + ".npy" for n in got)
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= 4 * 5 * 1000
+    # small arrays whole and in shape, large ones as the same ordered sample of their elements in every dump
+    assert got["losses"].tolist() == [1.5, 0.25]
+    assert np.array_equal(got["logits_0"], logits[0].numpy())
+    for n, full in (("logits_1", logits[1]), ("grad", flat.grad), ("params", flat)):
+        assert got[n].shape == (1000,) and np.array_equal(got[n], np.load(tmp_path / "b" / (n + ".npy")))
+        full = full.to(torch.float32).numpy().reshape(-1)
+        pos = np.searchsorted(np.sort(full), got[n])
+        assert np.array_equal(np.sort(full)[pos], got[n]) and len(set(got[n].tolist())) == 1000
+
+
 def test_roofline_entry_picks_binding_roof():
     # 100 launches in 25 sampled steps, 10 ms total: 0.1 ms per launch
     hbm = bench.roofline_entry("ffn0", 10.0, 100, 100 * 1e9, 100 * 1e8, 25, "c1")  # 10 flop/B
