@@ -155,6 +155,28 @@ int mmt_probe_enable(mmt_ctx* ctx, int32_t on);
  * next mmt_forward applies it (a forward and its backward always run under one setting). */
 int mmt_set_side_stream(mmt_ctx* ctx, int32_t on);
 
+/* Deterministic training mode (the counterpart of torch.use_deterministic_algorithms for this engine's
+ * backward): on != 0 makes mmt_backward / mmt_backward_stage write BIT-IDENTICAL gradients whenever the
+ * build, the device model, the environment knobs (MMT_* variables and the *_set_* tuning calls), the batch
+ * size, the parameters, the inputs and the dropout seed are the same. Every sum that otherwise leaves its
+ * kernel as one float atomic per block (bias, LayerNorm weight / bias, per-head stage-2 and embedding-table
+ * gradients: added in arrival order, so their low bits change run to run) is instead stored as per-block
+ * partials in the workspace and added by one ordered-sum launch in block-index order. The forward, the
+ * split-K weight gradients, the loss and AdamW are order-fixed in both modes, so with the mode on a whole
+ * training run replays bit for bit. Per context, off by default, and latched like mmt_set_side_stream: the
+ * next mmt_forward applies it, a forward and its backward always run under one setting.
+ * mmt_workspace_bytes does not depend on the switch (the scratch is always planned).
+ * What it does NOT promise: equal bits across different knob settings or builds (they change tile shapes
+ * and therefore the partials), across side stream on and off, between this mode and the default mode
+ * (same sums, another order: equal to rounding), or for the cross-rank all-reduce of a data-parallel run
+ * (world size > 1), which is outside this library.
+ * The token-table gradient has a fixed order only through the stable row sort (batch * block_size <= 16384
+ * rows, vocabularies <= 16384, n_embd <= 1024): outside that, mmt_backward / stage 0 return
+ * MMT_ERR_UNSUPPORTED in this mode before launching anything (the default mode runs as before).
+ * The ordered-sum launches carry the probe label "det_sum" (mmt_probe_set). */
+int mmt_set_deterministic(mmt_ctx* ctx, int32_t on);
+int32_t mmt_get_deterministic(const mmt_ctx* ctx); /* the requested setting (what the next forward latches) */
+
 /* ---- device-resident batcher: get_batch (training_utils.py:333-384) on HBM token streams ---- */
 /* in-place random walk of one int32 training stream (data_utils.py:342-351 as reached through
  * training_utils.py:350-360): x += uniform{0,+-1..+-r} where r < x < V - r */
@@ -285,6 +307,9 @@ int mmt_op_qkv2_fwd(void* stream, int32_t R, int32_t nblk, int32_t hs, const voi
 int mmt_op_qkv2_bwd(void* stream, int32_t R, int32_t nblk, int32_t hs, const void* h1, int32_t ld_h1,
                     const float* w2, const void* dout, int32_t ld_out, void* dh1, float* dw2);
 int mmt_op_colsum(void* stream, int32_t R, int32_t N, const void* x, int32_t ld, float* out, float alpha);
+/* the deterministic mode's ordered sum: dst[i] += (((parts[i] + parts[ld + i]) + parts[2 ld + i]) + ...) over
+ * nparts partial vectors of n floats (row stride ld >= n), plain fp32 adds in index order (no FMA, no tree) */
+int mmt_op_ordered_sum(void* stream, int32_t nparts, int32_t n, const float* parts, int64_t ld, float* dst);
 int mmt_op_cross_entropy(void* stream, int32_t R, int32_t V, const float* logits, const int64_t* tgt,
                          void* dlogits, int32_t ld_d, float* loss);
 int mmt_op_embedding_fwd(void* stream, int32_t B, int32_t T, int32_t C, int32_t V, const int64_t* idx,

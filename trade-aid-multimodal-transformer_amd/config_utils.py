@@ -18,7 +18,9 @@ _DEFAULTS = {
     "model_architecture": {"n_embd": 384, "n_head": 6, "n_layer": 6, "dropout": 0.2,
                            "fixed_values": [-0.5, -0.2, -0.1, 0, 0.1, 0.2, 0.5],
                            # build-only key (the reference ignores unknown keys): "bf16" | "fp8"
-                           "precision": "bf16"},
+                           "precision": "bf16",
+                           # build-only key: bitwise-reproducible gradients (mmt_set_deterministic)
+                           "deterministic": False},
 }
 
 
@@ -92,3 +94,23 @@ def _get_precision():
     if p not in ("bf16", "fp8"):
         raise ValueError(f"precision must be 'bf16' or 'fp8', got {p!r}")
     return p
+
+
+def _get_deterministic():
+    """Build-only knob (the counterpart of torch.use_deterministic_algorithms): True makes every
+    backward write bit-identical gradients for identical inputs (include/mmt.h, mmt_set_deterministic).
+    Default False; the MMT_DETERMINISTIC environment variable (0/1, false/true, off/on, no/yes)
+    overrides the config."""
+    env = os.environ.get("MMT_DETERMINISTIC")
+    v = env if env else _get_config().get("deterministic", False)
+    if isinstance(v, bool):
+        return v
+    if isinstance(v, int) and v in (0, 1):
+        return bool(v)
+    if isinstance(v, str):
+        t = v.strip().lower()
+        if t in ("1", "true", "on", "yes"):
+            return True
+        if t in ("0", "false", "off", "no"):
+            return False
+    raise ValueError(f"deterministic must be a boolean (0/1, false/true, off/on, no/yes), got {v!r}")

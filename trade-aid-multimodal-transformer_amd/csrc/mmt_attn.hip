@@ -1160,9 +1160,12 @@ __device__ __forceinline__ float a_sum32(float v) {
 // barrier stay
 #define MMT_F32_NB 0
 #endif
-template <bool DROP, bool MS, bool Q2>
+// DET (Q2 only; deterministic mode, mmt_det.h): a separate instantiation whose stage-2 epilogue stores the
+// workgroup's dW2 / db1 sums as partials (partial index = batch element b) instead of adding them by atomics
+template <bool DROP, bool MS, bool Q2, bool DET = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd_fused32(AttnBatch batch, int T, int H, float scale) {
   static_assert(!(MS && Q2), "the stage-2 backward follows the self-attention only");
+  static_assert(!DET || Q2, "only the stage-2 epilogue has sums to store");
   // NB (off: see MMT_F32_NB): every wave walks its own (query tile, key tile) products without waiting for the others: the
   // Q / dO images are complete before the walk, and the dQ contributions go into per-tile fp32 sums
   // in LDS ([8 tiles][32 d][32 q], ds_add_f32) instead of per-step partials reduced behind a barrier.
@@ -1840,9 +1843,16 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_fused32(AttnBatch batch, int 
           mine = r == kd * 8 + e ? v : mine;
         }
       const int kd = r >> 3, e = r & 7;
+      if constexpr (DET) {
+        // the wave's 48 sums into LDS behind the dW2 reduction area (past the tile images, which other waves
+        // may still read: the dQ partials there are spent since the barrier above); summed over the waves below
+        if (r < 24)
+          reinterpret_cast<float*>(lds + OFF_DQ)[4 * 3 * 512 + w * 48 + kd * 16 + (e < 4 ? 4 * h + e : 8 + 4 * h + e - 4)] = mine;
+      } else {
       if (r < 24)
         __hip_atomic_fetch_add(db1 + (kd * H + head) * 16 + (e < 4 ? 4 * h + e : 8 + 4 * h + e - 4), mine, __ATOMIC_RELAXED,
                                __HIP_MEMORY_SCOPE_AGENT);
+      }
     }
     // dW2: the four waves' partials summed through LDS, one atomic per element
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -1857,6 +1867,23 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_fused32(AttnBatch batch, int 
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
+    if constexpr (DET) {
+      static_assert((4 * 3 * 512 + 4 * 48) * 4 <= 8 * 4096, "the reduction areas fit the dQ partials");
+      const int nb = gridDim.x / H;  // batch elements = partials per element
+      float* const dp = batch.det.base + (int64_t)blockIdx.z * batch.det.stride;
+      for (int q = tid; q < 3 * 512; q += 256) {
+        const float v = (red[q] + red[1536 + q]) + (red[3072 + q] + red[4608 + q]);
+        const int kd = q / 512, oi = q % 512;
+        dp[((int64_t)b * 3 * H + kd * H + head) * 512 + oi] = v;
+      }
+      if (tid < 48) {
+        const float* dbw = red + 4 * 3 * 512;
+        const float v = (dbw[tid] + dbw[48 + tid]) + (dbw[96 + tid] + dbw[144 + tid]);
+        const int kd = tid / 16, col = tid % 16;
+        dp[(int64_t)nb * 3 * H * 512 + ((int64_t)b * 3 * H + kd * H + head) * 16 + col] = v;
+      }
+      return;
+    }
     for (int q = tid; q < 3 * 512; q += 256) {
       const float v = (red[q] + red[1536 + q]) + (red[3072 + q] + red[4608 + q]);
       const int kd = q / 512, oi = q % 512;
@@ -1976,6 +2003,8 @@ bool mmt_attn_bwd_fuses_qkv2(const AttnBatch& bt, int T, int hs) {
   return fused32_ok(t, T, 1);
 }
 
+int64_t mmt_attn_q2_det_floats(int count, int B, int H) { return (int64_t)count * B * 3 * H * (512 + 16); }
+
 template <int HS>
 static hipError_t attn_launch(const AttnBatch& bt, int B, int T, int H, float scale, bool bwd, hipStream_t s) {
   const int nb = ((T + 31) / 32 + 7) / 8;
@@ -2007,6 +2036,23 @@ static hipError_t attn_launch(const AttnBatch& bt, int B, int T, int H, float sc
       if (ns > 1) {
         if (drop) hipLaunchKernelGGL((attn_bwd_fused32<true, true, false>), grid, dim3(256), 0, s, bt, T, H, scale);
         else hipLaunchKernelGGL((attn_bwd_fused32<false, true, false>), grid, dim3(256), 0, s, bt, T, H, scale);
+      } else if (q2 && bt.det.base) {
+        // deterministic mode: the stage-2 sums as per-batch-element partials, dW2 [B][3 H * 512] then db1
+        // [B][3 H * 16] per problem, + the ordered sum
+        AttnBatch d = bt;
+        d.det.stride = mmt_attn_q2_det_floats(1, B, H);
+        DetLaunch L;
+        hipError_t e = L.begin(d.det, d.count, d.det.stride, s);
+        if (e != hipSuccess) return e;
+        if (drop) hipLaunchKernelGGL((attn_bwd_fused32<true, false, true, true>), grid, dim3(256), 0, s, d, T, H, scale);
+        else hipLaunchKernelGGL((attn_bwd_fused32<false, false, true, true>), grid, dim3(256), 0, s, d, T, H, scale);
+        e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        for (int g = 0; g < d.count; ++g) {
+          L.seg(g, d.det.stride, 0, d.p[g].q2_dw2, B, 3 * H * 512);
+          L.seg(g, d.det.stride, (int64_t)B * 3 * H * 512, d.p[g].q2_db1, B, 3 * H * 16);
+        }
+        return L.finish();
       } else if (q2) {
         if (drop) hipLaunchKernelGGL((attn_bwd_fused32<true, false, true>), grid, dim3(256), 0, s, bt, T, H, scale);
         else hipLaunchKernelGGL((attn_bwd_fused32<false, false, true>), grid, dim3(256), 0, s, bt, T, H, scale);

@@ -4,6 +4,8 @@
 // All grouped over modalities with blockIdx.z (one launch per op per layer).
 #include <stdlib.h>
 
+#include <algorithm>
+
 #include "mmt_common.h"
 #include "mmt_kernels.h"
 
@@ -185,10 +187,14 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(LnBatch batch, int R, int C
     }
   }
   __syncthreads();
+  // deterministic mode (mmt_det.h): the block's sums stored at [k][block][C] of the problem's scratch (the grid
+  // is capped, so the partial index is blockIdx.x); the ordered sum behind the launch adds them
+  float* const det = batch.det.base ? batch.det.base + (int64_t)blockIdx.z * batch.det.stride : nullptr;
   for (int c = threadIdx.x; c < C; c += 256) {
     for (int k = 0; k < nred; ++k) {
       const float a = red[k][0][c] + red[k][1][c] + red[k][2][c] + red[k][3][c];
-      atomicAdd((k == 0 ? P.dgamma : k == 1 ? P.dbeta : P.dsum) + c, a);
+      if (det) det[((int64_t)k * gridDim.x + blockIdx.x) * C + c] = a;
+      else atomicAdd((k == 0 ? P.dgamma : k == 1 ? P.dbeta : P.dsum) + c, a);
     }
   }
 }
@@ -202,8 +208,12 @@ hipError_t mmt_launch_ln_fwd(const LnBatch& b, int R, int C, hipStream_t s) {
   return hipGetLastError();
 }
 
-hipError_t mmt_launch_ln_bwd(const LnBatch& b, int R, int C, hipStream_t s) {
-  if (C % 4 != 0 || C > 1024 || b.count == 0) return C % 4 ? hipErrorInvalidValue : hipSuccess;
+#define LNB_DET_CAP 256
+static int ln_bwd_det_blocks(int R) { return std::max(1, std::min((R + 3) / 4, LNB_DET_CAP)); }
+int64_t mmt_ln_bwd_det_floats(int count, int R, int C) { return (int64_t)count * 3 * ln_bwd_det_blocks(R) * C; }
+
+hipError_t mmt_launch_ln_bwd(const LnBatch& b0, int R, int C, hipStream_t s) {
+  if (C % 4 != 0 || C > 1024 || b0.count == 0) return C % 4 ? hipErrorInvalidValue : hipSuccess;
   // 4 rows per block per pass; the grid is capped so the dgamma/dbeta atomics stay few
   static const int cap = [] {
     // blocks per problem: every block adds its dgamma/dbeta(/dsum) partials with one atomic per
@@ -214,12 +224,27 @@ hipError_t mmt_launch_ln_bwd(const LnBatch& b, int R, int C, hipStream_t s) {
   }();
   int blocks = (R + 3) / 4;
   if (blocks > cap) blocks = cap;
+  LnBatch b = b0;
+  DetLaunch L;
+  if (b.det.base) {  // deterministic mode: at most LNB_DET_CAP partials per column, whatever MMT_LNB_CAP says
+    blocks = ln_bwd_det_blocks(R);
+    b.det.stride = 3 * (int64_t)blocks * C;
+    const hipError_t e = L.begin(b.det, b.count, b.det.stride, s);
+    if (e != hipSuccess) return e;
+  }
   dim3 grid(blocks, 1, b.count);
   const int nv = (C / 4 + 63) / 64;
   if (nv <= 1) hipLaunchKernelGGL((ln_bwd_kernel<1, 4>), grid, dim3(256), 0, s, b, R, C);
   else if (nv <= 2) hipLaunchKernelGGL((ln_bwd_kernel<2, 2>), grid, dim3(256), 0, s, b, R, C);
   else hipLaunchKernelGGL((ln_bwd_kernel<4, 1>), grid, dim3(256), 0, s, b, R, C);
-  return hipGetLastError();
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess || !b.det.base) return e;
+  for (int g = 0; g < b.count; ++g) {
+    L.seg(g, b.det.stride, 0, b.p[g].dgamma, blocks, C);
+    L.seg(g, b.det.stride, (int64_t)blocks * C, b.p[g].dbeta, blocks, C);
+    L.seg(g, b.det.stride, 2 * (int64_t)blocks * C, b.p[g].dsum, blocks, C);
+  }
+  return L.finish();
 }
 
 // ============================================================================================
@@ -394,6 +419,10 @@ __global__ __launch_bounds__(256) void embed_pos_bwd_kernel(EmbBatch batch, int 
       const int m = q / B, b = q % B;
       s += reinterpret_cast<const f32x4*>(batch.p[m].dx + ((int64_t)b * T + t) * C)[c4];
     }
+    if (batch.det.base) {  // deterministic mode (mmt_det.h): this split's sums at [split][T * C]
+      *reinterpret_cast<f32x4*>(batch.det.base + ((int64_t)blockIdx.y * T + t) * C + 4 * c4) = s;
+      continue;
+    }
     float* dp = batch.p[0].dpos + (int64_t)t * C + 4 * c4;
 #pragma unroll
     for (int e = 0; e < 4; ++e) atomicAdd(dp + e, s[e]);
@@ -514,6 +543,15 @@ __global__ __launch_bounds__(256) void emb_segsum_kernel(EmbBatch batch, int R, 
   int cur = __builtin_amdgcn_readlane(mytok, 0);
   const float* const dx = sgpr_ptr(P.dx);
   float* const dtok = sgpr_ptr(P.dtok);
+  // deterministic mode (mmt_det.h): a run that begins and ends inside these 64 rows is the only add of the
+  // launch into its dtok row and stays an atomic; the wave's FIRST and LAST run may continue in the
+  // neighbouring waves (whose adds into that row would land in arrival order), so they are stored -- sums
+  // [range][2][C], then their tokens as int [range][2] (-1: no last run) -- and emb_det_sum_kernel adds them
+  // in wave order
+  const int nrange = (R + 63) / 64;
+  float* const dvec = batch.det.base ? batch.det.base + (int64_t)blockIdx.z * batch.det.stride : nullptr;
+  int* const dtk = dvec ? reinterpret_cast<int*>(dvec + (int64_t)nrange * 2 * C) : nullptr;
+  bool first = dvec != nullptr;
   constexpr int U = 8;  // rows in flight
   for (int k0 = 0; k0 < n; k0 += U) {
     f32x4 v[U];
@@ -529,7 +567,11 @@ __global__ __launch_bounds__(256) void emb_segsum_kernel(EmbBatch batch, int R, 
       if (k >= n) break;  // wave-uniform
       const int t = __builtin_amdgcn_readlane(mytok, k);
       if (t != cur) {  // wave-uniform: a run of token cur ends
-        if (col_ok) {
+        if (first) {
+          if (col_ok) *reinterpret_cast<f32x4*>(dvec + ((int64_t)range * 2 + 0) * C + 4 * c4) = acc;
+          if (lane == 0 && hf == 0) dtk[range * 2 + 0] = cur;
+          first = false;
+        } else if (col_ok) {
           float* d = dtok + (int64_t)cur * C + 4 * c4;
 #pragma unroll
           for (int e = 0; e < 4; ++e) atomicAdd(d + e, acc[e]);
@@ -540,11 +582,67 @@ __global__ __launch_bounds__(256) void emb_segsum_kernel(EmbBatch batch, int R, 
       acc += v[u];
     }
   }
+  if (dvec) {  // the last run (the first one too when the 64 rows are one run)
+    const int slot = first ? 0 : 1;
+    if (col_ok) *reinterpret_cast<f32x4*>(dvec + ((int64_t)range * 2 + slot) * C + 4 * c4) = acc;
+    if (lane == 0 && hf == 0) {
+      dtk[range * 2 + slot] = cur;
+      if (first) dtk[range * 2 + 1] = -1;
+    }
+    return;
+  }
   if (col_ok) {
     float* d = dtok + (int64_t)cur * C + 4 * c4;
 #pragma unroll
     for (int e = 0; e < 4; ++e) atomicAdd(d + e, acc[e]);
   }
+}
+
+// deterministic mode: the stored first / last runs of emb_segsum_kernel, added in wave order. Thread = one
+// float4 column; it walks the 2 * nrange entries (sorted rows: equal tokens are consecutive), sums a token's
+// entries in that order and adds each token's sum into dtok once. Loads run EMB_DET_U entries ahead.
+#define EMB_DET_U 8
+__global__ __launch_bounds__(256) void emb_det_sum_kernel(EmbBatch batch, int R, int C) {
+  const EmbProblem& P = batch.p[blockIdx.z];
+  const int c4 = blockIdx.x * 256 + threadIdx.x;
+  if (4 * c4 >= C) return;
+  const int nrange = (R + 63) / 64;
+  const float* dvec = batch.det.base + (int64_t)blockIdx.z * batch.det.stride;
+  const int* dtk = reinterpret_cast<const int*>(dvec + (int64_t)nrange * 2 * C);
+  const int n = 2 * nrange;
+  int cur = -1;
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  auto flush = [&] {
+    if (cur < 0) return;
+    f32x4* d = reinterpret_cast<f32x4*>(P.dtok + (int64_t)cur * C) + c4;
+    f32x4 o = *d;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = __fadd_rn(o[e], acc[e]);
+    *d = o;
+  };
+  for (int k0 = 0; k0 < n; k0 += EMB_DET_U) {
+    int tk[EMB_DET_U];
+    f32x4 v[EMB_DET_U];
+#pragma unroll
+    for (int u = 0; u < EMB_DET_U; ++u) {
+      const int k = k0 + u;
+      tk[u] = k < n ? dtk[k] : -1;
+      v[u] = k < n ? reinterpret_cast<const f32x4*>(dvec + (int64_t)k * C)[c4] : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+#pragma unroll
+    for (int u = 0; u < EMB_DET_U; ++u) {
+      if (tk[u] < 0) continue;  // no last run in that wave (or past the end)
+      if (tk[u] != cur) {
+        flush();
+        cur = tk[u];
+        acc = v[u];
+      } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[e] = __fadd_rn(acc[e], v[u][e]);
+      }
+    }
+  }
+  flush();
 }
 
 // the sorted path applies when every problem has int scratch for the permutation and a vocabulary
@@ -587,10 +685,22 @@ hipError_t mmt_launch_embed_fwd(const EmbBatch& b, int B, int T, int C, hipStrea
   return hipGetLastError();
 }
 
-hipError_t mmt_launch_embed_bwd(const EmbBatch& b, int B, int T, int C, hipStream_t s) {
-  if (C % 4 || b.count == 0) return C % 4 ? hipErrorInvalidValue : hipSuccess;
+// deterministic mode: only the stable row sort fixes the order of a token's rows
+bool mmt_embed_bwd_det_ok(const EmbBatch& b, int R, int C) {
+  return b.count > 0 && C % 4 == 0 && emb_sorted_ok(b, R, C) && R <= EMB_SORT_RMAX;
+}
+static int64_t emb_det_stride(int R, int C) { return (((int64_t)(R + 63) / 64) * (2 * C + 2) + 3) & ~(int64_t)3; }
+int64_t mmt_embed_bwd_det_floats(int count, int B, int T, int C) {
+  return std::max((int64_t)count * emb_det_stride(B * T, C), (int64_t)EMB_POS_SPLIT * T * C);
+}
+
+hipError_t mmt_launch_embed_bwd(const EmbBatch& b0, int B, int T, int C, hipStream_t s) {
+  if (C % 4 || b0.count == 0) return C % 4 ? hipErrorInvalidValue : hipSuccess;
   const int R = B * T;
   if (C % 4 || C > 1024) return hipErrorInvalidValue;
+  // deterministic mode: refused (never run in arrival order) outside the stable sort's limits
+  if (b0.det.base && !mmt_embed_bwd_det_ok(b0, R, C)) return hipErrorInvalidValue;
+  EmbBatch b = b0;
   if (emb_sorted_ok(b, R, C)) {
     for (int g = 1; g < b.count; ++g)
       if (b.p[g].dpos != b.p[0].dpos) return hipErrorInvalidValue;
@@ -600,6 +710,26 @@ hipError_t mmt_launch_embed_bwd(const EmbBatch& b, int B, int T, int C, hipStrea
     if (!sorted) hipLaunchKernelGGL(emb_sort_kernel, dim3(1, 1, b.count), dim3(1024), 0, s, b, R);  // into perm / part
     const int halves = (C + 255) / 256;
     const int waves = ((R + 63) / 64) * halves;
+    if (b.det.base) {
+      // every wave with rows stores its first / last run (no zeroing needed: emb_det_sum_kernel reads exactly those)
+      b.det.stride = emb_det_stride(R, C);
+      if ((int64_t)b.count * b.det.stride > b.det.cap || (int64_t)EMB_POS_SPLIT * T * C > b.det.cap ||
+          ((uintptr_t)b.det.base & 15))
+        return hipErrorInvalidValue;
+      hipLaunchKernelGGL(emb_segsum_kernel, dim3((waves + 3) / 4, 1, b.count), dim3(256), 0, s, b, R, C);
+      if (b.det.hook) b.det.hook(b.det.user, 0);
+      hipLaunchKernelGGL(emb_det_sum_kernel, dim3((C / 4 + 255) / 256, 1, b.count), dim3(256), 0, s, b, R, C);
+      if (b.det.hook) b.det.hook(b.det.user, 1);
+      // the positional table: EMB_POS_SPLIT partials of [T * C] (every block stores all its columns)
+      DetLaunch L;
+      hipError_t e = L.begin(b.det, 1, (int64_t)EMB_POS_SPLIT * T * C, s);
+      if (e != hipSuccess) return e;
+      hipLaunchKernelGGL(embed_pos_bwd_kernel, dim3(T, EMB_POS_SPLIT), dim3(256), 0, s, b, B, T, C);
+      e = hipGetLastError();
+      if (e != hipSuccess) return e;
+      L.seg(0, 0, 0, b.p[0].dpos, EMB_POS_SPLIT, T * C);
+      return L.finish();
+    }
     hipLaunchKernelGGL(emb_segsum_kernel, dim3((waves + 3) / 4, 1, b.count), dim3(256), 0, s, b, R, C);
     hipLaunchKernelGGL(embed_pos_bwd_kernel, dim3(T, EMB_POS_SPLIT), dim3(256), 0, s, b, B, T, C);
     return hipGetLastError();
@@ -808,17 +938,32 @@ __global__ __launch_bounds__(256) void colsum_kernel(ColsumBatch batch, int R) {
     for (int i = 0; i < 8; ++i) s += red[i][c];
     float alpha = P.alpha;
     if (P.alpha_ptr) alpha *= *P.alpha_ptr;
-    atomicAdd(P.out + gc, alpha * s);
+    // deterministic mode (mmt_det.h): the 256-row block's sums stored at [row block][N]
+    if (batch.det.base) batch.det.base[(int64_t)blockIdx.z * batch.det.stride + (int64_t)blockIdx.y * P.N + gc] = alpha * s;
+    else atomicAdd(P.out + gc, alpha * s);
   }
 }
 
-hipError_t mmt_launch_colsum(const ColsumBatch& b, int R, hipStream_t s) {
+int64_t mmt_colsum_det_floats(int count, int R, int maxn) { return (int64_t)count * ((R + 255) / 256) * maxn; }
+
+hipError_t mmt_launch_colsum(const ColsumBatch& b0, int R, hipStream_t s) {
   int maxn = 0;
-  for (int g = 0; g < b.count; ++g) maxn = b.p[g].N > maxn ? b.p[g].N : maxn;
-  if (maxn == 0 || b.count == 0) return hipSuccess;
-  dim3 grid((maxn + 255) / 256, (R + 255) / 256, b.count);
+  for (int g = 0; g < b0.count; ++g) maxn = b0.p[g].N > maxn ? b0.p[g].N : maxn;
+  if (maxn == 0 || b0.count == 0 || R <= 0) return hipSuccess;
+  ColsumBatch b = b0;
+  const int nrb = (R + 255) / 256;
+  DetLaunch L;
+  if (b.det.base) {
+    b.det.stride = (int64_t)nrb * maxn;
+    const hipError_t e = L.begin(b.det, b.count, b.det.stride, s);
+    if (e != hipSuccess) return e;
+  }
+  dim3 grid((maxn + 255) / 256, nrb, b.count);
   hipLaunchKernelGGL(colsum_kernel, grid, dim3(256), 0, s, b, R);
-  return hipGetLastError();
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess || !b.det.base) return e;
+  for (int g = 0; g < b.count; ++g) L.seg(g, b.det.stride, 0, b.p[g].out, nrb, b.p[g].N);
+  return L.finish();
 }
 
 // ============================================================================================
@@ -927,17 +1072,35 @@ __global__ __launch_bounds__(256) void drop_copy_kernel(DropCopyBatch batch, int
   }
   if (!P.dsum) return;
   __syncthreads();
-  for (int c = threadIdx.x; c < C; c += 256) atomicAdd(P.dsum + c, red[0][c] + red[1][c] + red[2][c] + red[3][c]);
+  // deterministic mode (mmt_det.h): the block's sums stored at [block][C] (capped grid: blockIdx.x)
+  float* const det = batch.det.base ? batch.det.base + (int64_t)blockIdx.z * batch.det.stride : nullptr;
+  for (int c = threadIdx.x; c < C; c += 256) {
+    const float a = red[0][c] + red[1][c] + red[2][c] + red[3][c];
+    if (det) det[(int64_t)blockIdx.x * C + c] = a;
+    else atomicAdd(P.dsum + c, a);
+  }
 }
 
-hipError_t mmt_launch_drop_copy(const DropCopyBatch& b, int R, int C, hipStream_t s) {
+static int drop_copy_blocks(int R) { return std::max(1, std::min((R + 15) / 16, 256)); }
+int64_t mmt_drop_copy_det_floats(int count, int R, int C) { return (int64_t)count * drop_copy_blocks(R) * C; }
+
+hipError_t mmt_launch_drop_copy(const DropCopyBatch& b0, int R, int C, hipStream_t s) {
   if (C % 4 != 0 || C > 1024) return hipErrorInvalidValue;
-  if (b.count == 0 || R == 0) return hipSuccess;
+  if (b0.count == 0 || R == 0) return hipSuccess;
   // one dsum atomic per column per block: cap the blocks (see mmt_launch_ln_bwd)
-  int blocks = (R + 15) / 16;
-  if (blocks > 256) blocks = 256;
+  const int blocks = drop_copy_blocks(R);
+  DropCopyBatch b = b0;
+  DetLaunch L;
+  if (b.det.base) {
+    b.det.stride = (int64_t)blocks * C;
+    const hipError_t e = L.begin(b.det, b.count, b.det.stride, s);
+    if (e != hipSuccess) return e;
+  }
   hipLaunchKernelGGL(drop_copy_kernel, dim3(blocks, 1, b.count), dim3(256), 0, s, b, R, C);
-  return hipGetLastError();
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess || !b.det.base) return e;
+  for (int g = 0; g < b.count; ++g) L.seg(g, b.det.stride, 0, b.p[g].dsum, blocks, C);
+  return L.finish();
 }
 
 hipError_t mmt_launch_f32_to_bf16(const float* src, bf16_t* dst, int64_t n, hipStream_t s) {
@@ -1103,5 +1266,43 @@ hipError_t mmt_launch_mx_quant(const MxSeg* segs_dev, int nseg, int max_units, c
                                hipStream_t s) {
   if (nseg == 0 || max_units == 0) return hipSuccess;
   hipLaunchKernelGGL(mx_quant_kernel, dim3((max_units + 255) / 256, nseg), dim3(256), 0, s, segs_dev, base, dst);
+  return hipGetLastError();
+}
+
+// ============================================================================================
+// Deterministic mode (mmt_det.h): dst[i] += parts[0][i] + parts[1][i] + ... in index order, one thread per
+// element, a batch of segments per launch (blockIdx.y). Plain fp32 adds (__fadd_rn: nothing contracts or
+// reassociates them); the loads run DET_U partials ahead of the add chain.
+// ============================================================================================
+#define DET_U 32
+__global__ __launch_bounds__(256) void ordered_sum_kernel(DetSumBatch b) {
+  const DetSeg& S = b.s[blockIdx.y];
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= S.n) return;
+  const float* p = S.parts + i;
+  const int64_t ld = S.ld;
+  const int np = S.nparts;  // (block-uniform: the guards below do not diverge)
+  const float d0 = S.dst[i];
+  float acc = p[0];
+  for (int k = 1; k < np; k += DET_U) {
+    float v[DET_U];
+#pragma unroll
+    for (int u = 0; u < DET_U; ++u) v[u] = k + u < np ? p[(int64_t)(k + u) * ld] : 0.f;
+#pragma unroll
+    for (int u = 0; u < DET_U; ++u)
+      if (k + u < np) acc = __fadd_rn(acc, v[u]);
+  }
+  S.dst[i] = __fadd_rn(d0, acc);
+}
+
+hipError_t mmt_launch_ordered_sum(const DetSumBatch& b, hipStream_t s) {
+  int maxn = 0;
+  for (int g = 0; g < b.count; ++g) {
+    if (b.s[g].nparts < 1 || b.s[g].n < 0 || !b.s[g].dst || !b.s[g].parts) return hipErrorInvalidValue;
+    maxn = std::max(maxn, b.s[g].n);
+  }
+  if (b.count == 0 || maxn == 0) return hipSuccess;
+  if (b.count > MMT_DET_MAX_SEG) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(ordered_sum_kernel, dim3((maxn + 255) / 256, b.count), dim3(256), 0, s, b);
   return hipGetLastError();
 }

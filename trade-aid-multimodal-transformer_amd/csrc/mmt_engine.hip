@@ -97,6 +97,10 @@ struct Plan {
   size_t celoss[MAXM];  // float [512]: the cross-entropy blocks' loss shares (summed in block order)
   const void* gh1_pad_ws = nullptr;  // the workspace whose gh1 pad columns (written by no kernel) are zeroed
   size_t eperm[MAXM];  // int [R]: the rows in token order for the token-table gradient (mmt_launch_emb_sort)
+  // deterministic mode: partial-sum scratch of ONE producer launch (every producer runs on the main stream, in
+  // stream order with its ordered sum, so one region serves them all); planned whatever the switch says
+  size_t det = 0;
+  int64_t det_floats = 0;
   // KV-cache decode (generate): compact [B, *] rows of ONE new position per sequence
   struct Dec {
     size_t x0, a16, mean, rstd, h1, qkv, o16, p1, f, x2h, d16, qc, oc, pc, lnf16, hh;
@@ -220,6 +224,11 @@ struct mmt_ctx {
   std::vector<hipEvent_t> evpool;
   size_t evnext = 0;
   int d16 = 0;  // rotation index of the current dres16 copy (reset at backward stage 0)
+  // deterministic mode (mmt_set_deterministic; mmt_det.h): every arrival-order float sum of the backward leaves
+  // its kernel as per-block partials (Plan::det) that one ordered sum adds. det_req is the requested setting,
+  // latched into det by the next mmt_forward (a forward and its backward always run under one setting)
+  bool det = false;
+  bool det_req = false;
 };
 
 namespace {
@@ -515,6 +524,22 @@ void make_plan(mmt_ctx* c, int B) {
     p.slab_bytes = (size_t)mx * 16 * f4;
     p.slab = A(p.slab_bytes);
   }
+  // deterministic mode: the largest partial-sum region any producer launch of the backward needs
+  {
+    const int Ri = (int)R;
+    int64_t df = 0;
+    df = std::max(df, mmt_gemm_det_floats(M, Ri, std::max(4 * C, maxvh), false));  // dbias of the data-gradient GEMMs
+    df = std::max(df, mmt_gemm_det_floats(M, Ri, C, true));                        // LayerNorm-fused: dsum, dgamma, dbeta
+    df = std::max(df, mmt_mlp2_bwd_det_floats(std::min(M, MMT_MLP2_GROUP), Ri, C / 2));
+    df = std::max(df, mmt_ln_bwd_det_floats(M, Ri, C));
+    df = std::max(df, mmt_colsum_det_floats(M, Ri, maxv));
+    df = std::max(df, mmt_drop_copy_det_floats(M, Ri, C));
+    df = std::max(df, mmt_qkv2_bwd_det_floats(M, Ri, 3 * H, c->hs));
+    if (c->hs == 32) df = std::max(df, mmt_attn_q2_det_floats(M, B, H));
+    df = std::max(df, mmt_embed_bwd_det_floats(M, B, c->T, C));
+    p.det_floats = df;
+    p.det = A((size_t)df * f4);
+  }
   // decode scratch (tiny: B rows)
   p.dec_x.resize((size_t)c->L * M * 3);
   for (int i = 0; i < M; ++i) {
@@ -685,6 +710,24 @@ struct Runner {
     if (e != hipSuccess && rc == MMT_OK) rc = fail(c, MMT_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
     return e == hipSuccess;
   }
+  // deterministic mode (backward only): hands a producer launch the partial-sum scratch; its ordered sum is
+  // launched by the producer's launcher right behind it, between the probe hooks (label "det_sum")
+  bool det = false;
+  int det_probe = -1;
+  static void det_hook(void* user, int after) {
+    Runner* r = static_cast<Runner*>(user);
+    if (!after) r->det_probe = r->probe_begin("det_sum", r->s);
+    else r->probe_end(r->det_probe, r->s, 0.0, 0.0);
+  }
+  template <class Bt>
+  void det_arm(Bt& b) {
+    if (!det) return;
+    b.det.base = W<float>(c->plan.det);
+    b.det.cap = c->plan.det_floats;
+    b.det.stride = 0;
+    b.det.hook = &Runner::det_hook;
+    b.det.user = this;
+  }
   // live kernel timing (mmt_probe_set): HIP events around every launch whose label matches one of
   // the probe patterns, recorded on the stream the launch goes to (the side stream for weight
   // gradients), each tagged with the launch's algorithmic flops and bytes
@@ -751,6 +794,7 @@ struct Runner {
         P.bias = nullptr; P.aux = nullptr; P.split_stride = 0;
       }
       if (mmt_gemm_ln_bwd_ok(f)) {
+        det_arm(f);
         const int id = probe_begin(gname, s);
         ok(mmt_launch_gemm_ln_bwd(f, s), gname);
         if (id >= 0) {
@@ -762,7 +806,9 @@ struct Runner {
       }
     }
     gemm(dx, true, false, EPI_STORE_F32, 1, gname);
-    ok(mmt_launch_ln_bwd(lb, R, C, s), lname);
+    LnBatch ld = lb;
+    det_arm(ld);
+    ok(mmt_launch_ln_bwd(ld, R, C, s), lname);
   }
   // the attention out-projection Linear(C, C/2) -> tanh -> Linear(C/2, C) + dropout + residual as one fused
   // launch (mmt_launch_mlp2: h stays in LDS between the products); false (nothing launched) when the
@@ -796,6 +842,8 @@ struct Runner {
     }
     for (int k = 0; k < nch; ++k)
       if (!(bwd ? mmt_mlp2_bwd_ok(chunk[k]) : mmt_mlp2_ok(chunk[k]))) return false;
+    if (bwd)
+      for (int k = 0; k < nch; ++k) det_arm(chunk[k]);  // (each chunk's ordered sum runs before the next chunk's launch)
     const int id = probe_begin(what, s);
     for (int k = 0; k < nch; ++k) ok(bwd ? mmt_launch_mlp2_bwd(chunk[k], s) : mmt_launch_mlp2(chunk[k], s), what);
     if (id >= 0) {
@@ -830,9 +878,10 @@ struct Runner {
   void gemm(const GemmBatch& b, bool akc, bool bkc, int epi, int splits, const char* what) {
     if (rc != MMT_OK) return;
     const int id = probe_begin(what, s);
-    if (gemm_hint) {
+    if (gemm_hint || det) {
       GemmBatch h = b;
-      h.tile_hint = gemm_hint;
+      if (gemm_hint) h.tile_hint = gemm_hint;
+      det_arm(h);
       ok(mmt_launch_gemm(h, akc, bkc, epi, splits, s), what);
     } else {
       ok(mmt_launch_gemm(b, akc, bkc, epi, splits, s), what);
@@ -914,7 +963,11 @@ struct Runner {
   void attn(const AttnBatch& ab, bool bwd, float scale, const char* what) {
     if (rc != MMT_OK) return;
     const int id = probe_begin(what, s);
-    if (bwd) ok(mmt_launch_attn_bwd(ab, B, c->T, c->H, c->hs, scale, s), what);
+    if (bwd && det) {
+      AttnBatch ad = ab;
+      det_arm(ad);
+      ok(mmt_launch_attn_bwd(ad, B, c->T, c->H, c->hs, scale, s), what);
+    } else if (bwd) ok(mmt_launch_attn_bwd(ab, B, c->T, c->H, c->hs, scale, s), what);
     else ok(mmt_launch_attn_fwd(ab, B, c->T, c->H, c->hs, scale, s), what);
     if (id >= 0) {
       double fl = 0, by = 0;
@@ -1546,6 +1599,7 @@ int run_backward_stage(mmt_ctx* c, Runner& r, int stage, const float* loss_grads
       dx.p[i].o16 = r.W<bf16_t>(p.gbig[par][i]); dx.p[i].ldo16 = c->ldvh[i];
     }
     r.dwgemm(dw, "head2_dw");
+    r.det_arm(cs);
     r.ok(mmt_launch_colsum(cs, R, r.s), "head2_db");
     for (int i = 0; i < M; ++i) dx.p[i].dbias = grads + c->post[i].b0;  // head0 bias grad fused
     r.gemm(dx, true, false, EPI_DTANH_BF16, 1, "head2_dx");
@@ -1708,6 +1762,7 @@ int run_backward_stage(mmt_ctx* c, Runner& r, int stage, const float* loss_grads
       q.src = r.W<float>(p.dres[i]); q.dst = d16_cur(c, r, i); q.dsum = grads + x[i].bf2;
       r.set_drop(q, l, i, DS_FFN);
     }
+    r.det_arm(db);
     if (db.count) r.ok(mmt_launch_drop_copy(db, R, C, r.s), "dres16");
   }
   if (r.rc != MMT_OK) return r.rc;
@@ -1819,6 +1874,7 @@ int run_backward_stage(mmt_ctx* c, Runner& r, int stage, const float* loss_grads
     p.gh1_pad_ws = r.ws;
   }
   r.attn(ab, true, scale, "attn_bwd");
+  r.det_arm(qb);
   if (!q2) r.ok(mmt_launch_qkv2_bwd(qb, R, 3 * H, hs, ldh1, 3 * C, r.s), "qkv2_bwd");
   for (int i = 0; i < M; ++i) {
     const bf16_t* g = r.W<bf16_t>(p.gh1[par][i]);
@@ -1937,7 +1993,7 @@ void ensure_side(mmt_ctx* c) {
 // =============================================================================================
 extern "C" {
 
-const char* mmt_version(void) { return "mmt_hip 0.1 gfx950"; }
+const char* mmt_version(void) { return "mmt_hip 0.2 gfx950"; }
 const char* mmt_create_error(void) { return g_create_err.c_str(); }
 
 mmt_ctx* mmt_create(const mmt_config* cfg) {
@@ -2014,6 +2070,7 @@ int mmt_forward(mmt_ctx* c, void* stream, int32_t batch, const int64_t* const* i
   int rc = ensure_device_tables(c);
   if (rc) return rc;
   c->side_off = c->side_off_req;
+  c->det = c->det_req;
   Runner r{c, (hipStream_t)stream, workspace, params, nullptr, batch, batch * c->T};
   // dropout (training mode only, as nn.Dropout): one seed per training forward, reused by its backward
   r.drop = training && c->cfg.dropout > 0.f;
@@ -2079,6 +2136,18 @@ int mmt_backward_stage(mmt_ctx* c, void* stream, int32_t stage, const float* los
   Runner r{c, (hipStream_t)stream, workspace, params, nullptr, c->plan.B, c->plan.B * c->T};
   r.drop = c->fwd_drop;
   r.seed = c->fwd_seed;
+  r.det = c->det;
+  if (c->det && stage == 0) {
+    // the token-table gradient has a fixed summation order only through the stable row sort: outside its
+    // limits the step is refused here, before anything is launched, never run in arrival order
+    EmbBatch eb{}; eb.count = c->M;
+    for (int i = 0; i < c->M; ++i) { eb.p[i].V = c->V[i]; eb.p[i].perm = r.W<int>(c->plan.eperm[i]); }
+    if (!mmt_embed_bwd_det_ok(eb, r.R, c->C))
+      return fail(c, MMT_ERR_UNSUPPORTED,
+                  "deterministic mode: the token-table gradient's stable row sort covers batch * block_size <= 16384 "
+                  "rows, vocabularies <= 16384 and n_embd <= 1024 (with MMT_EMB_SORT on); got " +
+                      std::to_string(r.R) + " rows");
+  }
   if (stage == c->L + 1) {
     EmbBatch eb{}; eb.count = c->M;
     for (int i = 0; i < c->M; ++i) {
@@ -2089,6 +2158,7 @@ int mmt_backward_stage(mmt_ctx* c, void* stream, int32_t stage, const float* los
     }
     if (c->emb_sorted) r.ok(hipStreamWaitEvent(r.s, c->emb_ev, 0), "stream wait");
     c->emb_sorted = false;
+    r.det_arm(eb);
     r.ok(mmt_launch_embed_bwd(eb, r.B, c->T, c->C, r.s), "embed_bwd");
     return r.rc;
   }
@@ -2172,6 +2242,14 @@ extern "C" int mmt_set_side_stream(mmt_ctx* c, int32_t on) {
   c->side_off_req = on == 0;
   return MMT_OK;
 }
+
+// deterministic mode (mmt.h): latched like the side-stream switch, per context
+extern "C" int mmt_set_deterministic(mmt_ctx* c, int32_t on) {
+  if (!c) return MMT_ERR_INVALID;
+  c->det_req = on != 0;
+  return MMT_OK;
+}
+extern "C" int32_t mmt_get_deterministic(const mmt_ctx* c) { return c && c->det_req ? 1 : 0; }
 
 extern "C" int mmt_probe_set(mmt_ctx* c, const char* label) {
   if (!c) return MMT_ERR_INVALID;

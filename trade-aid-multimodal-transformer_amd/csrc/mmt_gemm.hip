@@ -370,12 +370,12 @@ __global__ __launch_bounds__(TL::NT, MINB) void gemm_kernel(GemmBatch batch) {
   if constexpr (SWAP && EPI == EPI_BIAS_TANH_BF16 && TL::NW == 4 && TL::BN == 128) {
     if (P.qkv2_out) {  // the per-head stage 2 of Q/K/V (uniform per problem)
       qkv2_fused<TL>(P, acc, lds, lds + LDS_MAIN, alpha, m0, n0, lane, wave);
-      epilogue_swap<TL, EPI, EPI_ROWS, true>(P, acc, lds, o32, alpha, m0, n0, tid, lane, wave);
+      epilogue_swap<TL, EPI, EPI_ROWS, true>(P, acc, lds, o32, alpha, m0, n0, tid, lane, wave, det_of(batch, prob));
     } else {
-      epilogue_swap<TL, EPI, EPI_ROWS>(P, acc, lds, o32, alpha, m0, n0, tid, lane, wave);
+      epilogue_swap<TL, EPI, EPI_ROWS>(P, acc, lds, o32, alpha, m0, n0, tid, lane, wave, det_of(batch, prob));
     }
   } else if constexpr (SWAP) {
-    epilogue_swap<TL, EPI, EPI_ROWS>(P, acc, lds, o32, alpha, m0, n0, tid, lane, wave);
+    epilogue_swap<TL, EPI, EPI_ROWS>(P, acc, lds, o32, alpha, m0, n0, tid, lane, wave, det_of(batch, prob));
   } else {
     // acc[i][j]: rows = m (sub-tile i), cols = n (sub-tile j)
 #pragma unroll
@@ -797,7 +797,57 @@ static bool gemm_span_ok(const GemmBatch& b) {
   return true;
 }
 
+// Deterministic mode (GemmBatch::det, mmt_det.h): the epilogue's column sums (dbias; with `ln` also
+// ln_dgamma / ln_dbeta) are stored per row tile at [slot][ceil(M / 128)][N] of the problem's scratch and
+// one ordered sum behind the launch adds them into the gradients
+static int64_t gemm_det_stride(const GemmBatch& b, bool ln) {
+  int64_t st = 0;
+  for (int g = 0; g < b.count; ++g) {
+    const int64_t nrt = (b.p[g].M + MMT_DET_GEMM_ROWS - 1) / MMT_DET_GEMM_ROWS;
+    st = std::max(st, (ln ? 3 : 1) * nrt * (int64_t)b.p[g].N);
+  }
+  return (st + 3) & ~(int64_t)3;
+}
+int64_t mmt_gemm_det_floats(int count, int M, int N, bool ln) {
+  GemmBatch b{};
+  b.count = 1; b.p[0].M = M; b.p[0].N = N;
+  return count * gemm_det_stride(b, ln);
+}
+template <class F>
+static hipError_t gemm_det_run(const GemmBatch& b, bool ln, hipStream_t s, F run) {
+  bool any = false;
+  for (int g = 0; g < b.count; ++g) any = any || b.p[g].dbias || (ln && (b.p[g].ln_dgamma || b.p[g].ln_dbeta));
+  GemmBatch d = b;
+  if (!any) {  // no column sums leave this launch
+    d.det = DetScratch{};
+    return run(d);
+  }
+  d.det.stride = gemm_det_stride(b, ln);
+  DetLaunch L;
+  hipError_t e = L.begin(d.det, b.count, d.det.stride, s);
+  if (e != hipSuccess) return e;
+  e = run(d);
+  if (e != hipSuccess) return e;
+  for (int g = 0; g < b.count; ++g) {
+    const GemmProblem& P = b.p[g];
+    const int nrt = (P.M + MMT_DET_GEMM_ROWS - 1) / MMT_DET_GEMM_ROWS;
+    const int64_t slot = (int64_t)nrt * P.N;
+    L.seg(g, d.det.stride, 0, P.dbias, nrt, P.N);
+    if (ln) {
+      L.seg(g, d.det.stride, slot, P.ln_dgamma, nrt, P.N);
+      L.seg(g, d.det.stride, 2 * slot, P.ln_dbeta, nrt, P.N);
+    }
+  }
+  return L.finish();
+}
+
+static hipError_t launch_gemm_any(const GemmBatch& b, bool a_kc, bool b_kc, int epi, int splits, hipStream_t s);
 hipError_t mmt_launch_gemm(const GemmBatch& b, bool a_kc, bool b_kc, int epi, int splits, hipStream_t s) {
+  if (!b.det.base) return launch_gemm_any(b, a_kc, b_kc, epi, splits, s);
+  return gemm_det_run(b, false, s, [&](const GemmBatch& d) { return launch_gemm_any(d, a_kc, b_kc, epi, splits, s); });
+}
+
+static hipError_t launch_gemm_any(const GemmBatch& b, bool a_kc, bool b_kc, int epi, int splits, hipStream_t s) {
   if (!gemm_span_ok(b)) return hipErrorInvalidValue;
   for (int g = 0; g < b.count; ++g) {
     const GemmProblem& P = b.p[g];
@@ -1020,7 +1070,13 @@ bool mmt_gemm_ln_bwd_ok(const GemmBatch& b) {
   return true;
 }
 
+static hipError_t launch_gemm_ln_bwd_any(const GemmBatch& b, hipStream_t s);
 hipError_t mmt_launch_gemm_ln_bwd(const GemmBatch& b, hipStream_t s) {
+  if (!b.det.base) return launch_gemm_ln_bwd_any(b, s);
+  return gemm_det_run(b, true, s, [&](const GemmBatch& d) { return launch_gemm_ln_bwd_any(d, s); });
+}
+
+static hipError_t launch_gemm_ln_bwd_any(const GemmBatch& b, hipStream_t s) {
   if (!mmt_gemm_ln_bwd_ok(b) || !gemm_span_ok(b)) return hipErrorInvalidValue;
   // a tile as wide as the row, whatever K: its block owns whole rows of the LayerNorm (C = 256:
   // 256 x 256; C = 512: 128 x 512 at BK 32 x 2 stages = 80 KiB of ring; BK 64 measured neutral, a

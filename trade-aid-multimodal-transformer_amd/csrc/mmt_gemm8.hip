@@ -219,7 +219,7 @@ __global__ __launch_bounds__(512, 1) void gemm8_kernel(GemmBatch batch) {
   float alpha = P.alpha;
   if (P.alpha_ptr) alpha *= *P.alpha_ptr;
   float* o32 = P.o32 + (P.split_stride ? (int64_t)split * P.split_stride : (int64_t)0);
-  epilogue_swap<TL, EPI, EPI_ROWS>(P, acc, lds, o32, alpha, m0, n0, tid, lane, wave);
+  epilogue_swap<TL, EPI, EPI_ROWS>(P, acc, lds, o32, alpha, m0, n0, tid, lane, wave, det_of(batch, prob));
 }
 
 template <int EPI, bool A_KC, bool B_KC>

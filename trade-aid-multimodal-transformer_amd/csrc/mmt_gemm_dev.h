@@ -27,6 +27,11 @@ using TileW = TileCfg<1, 8, 4, 2>;
 
 typedef __attribute__((address_space(3))) void lds_void;
 
+// deterministic mode: problem `prob`'s partial-sum scratch of this launch, or null (the atomic path)
+__device__ __forceinline__ float* det_of(const GemmBatch& batch, int prob) {
+  return batch.det.base ? batch.det.base + (int64_t)prob * batch.det.stride : nullptr;
+}
+
 // swizzle of the 16-B chunk index of a K-contiguous image row (BK/8 chunks per row):
 //   BK 64 (128-B rows): chunk ^ ((row>>1)&7) ; BK 32 (64-B rows): chunk ^ ((row>>2)&3)
 template <int BK>
@@ -250,7 +255,8 @@ __device__ __forceinline__ void stage_acc(f32x4 (&acc)[4][8], float* ct, int pas
 
 template <class TL, int EPI, int EPI_ROWS, bool PRE = false, class ACC>
 __device__ __forceinline__ void epilogue_swap(const GemmProblem& P, ACC& acc, char* lds,
-                                              float* o32, float alpha, int m0, int n0, int tid, int lane, int wave) {
+                                              float* o32, float alpha, int m0, int n0, int tid, int lane, int wave,
+                                              float* det = nullptr) {
   constexpr int GBM = TL::BM, GBN = TL::BN, NW = TL::NW, NT = TL::NT, TM = TL::TM, TN = TL::TN;
   const int M = P.M, N = P.N;
   const int wm = wave / TL::WN, wn = wave % TL::WN;
@@ -651,9 +657,13 @@ __device__ __forceinline__ void epilogue_swap(const GemmProblem& P, ACC& acc, ch
   }
   // column sums: rows of a column group live in lanes l, l^TPR, ... of every wave: fold those, then
   // the waves via LDS (the staged tile is dead: every thread has read its own rows), one atomic per
-  // column
+  // column. Deterministic mode (det, this problem's partial-sum scratch, wave-uniform; mmt_det.h): the
+  // block's sums are stored at [slot][row tile m0 / GBM][N] instead (slot 0 dbias, 1 ln_dgamma, 2
+  // ln_dbeta; ceil(M / 128) row-tile rows per slot) and the launcher's ordered sum adds them
 #undef EA
-  auto flush_colsums = [&](float (&v)[8], float* dst) {
+  // (every tile with column sums is 128 or 256 rows tall; the 64-row forward tile of the fused MLP has none)
+  constexpr bool DET_OK = GBM % MMT_DET_GEMM_ROWS == 0;
+  auto flush_colsums = [&](float (&v)[8], float* dst, int slot) {
 #pragma unroll
     for (int e = 0; e < 8; ++e)
 #pragma unroll
@@ -669,12 +679,17 @@ __device__ __forceinline__ void epilogue_swap(const GemmProblem& P, ACC& acc, ch
       float sum = 0.f;
 #pragma unroll
       for (int w = 0; w < NW; ++w) sum += red[w * GBN + tid];
-      atomicAdd(dst + n0 + tid, sum);
+      if (DET_OK && det) {
+        const int nrt = (M + MMT_DET_GEMM_ROWS - 1) / MMT_DET_GEMM_ROWS;
+        det[((int64_t)slot * nrt + m0 / GBM) * N + n0 + tid] = sum;
+      } else {
+        atomicAdd(dst + n0 + tid, sum);
+      }
     }
   };
-  if (want_db) flush_colsums(cs, P.dbias);
+  if (want_db) flush_colsums(cs, P.dbias, 0);
   if constexpr (LNB) {
-    flush_colsums(cg, P.ln_dgamma);
-    flush_colsums(cb, P.ln_dbeta);
+    flush_colsums(cg, P.ln_dgamma, 1);
+    flush_colsums(cb, P.ln_dbeta, 2);
   }
 }

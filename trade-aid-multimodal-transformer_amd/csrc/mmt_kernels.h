@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "mmt_det.h"
 
 #ifndef MMT_MAX_GROUP
 #define MMT_MAX_GROUP 8
@@ -105,6 +106,7 @@ struct GemmBatch {
   int dw_blocks;  // weight gradients: blocks per launch the split-K factor aims at (0: MMT_WGRAD_BLOCKS / 128)
   // diagnostic builds only (-DMMT_GEMM_STAMPS, tools/gemm_stamps.py): per-block s_memtime stamps
   unsigned long long* stamps;
+  DetScratch det;  // deterministic mode (mmt_det.h): the column sums leave as per-block partials; null base: atomics
 };
 
 hipError_t mmt_launch_gemm(const GemmBatch& b, bool a_kc, bool b_kc, int epi, int splits, hipStream_t s);
@@ -138,7 +140,9 @@ struct Mlp2Batch {
   GemmProblem g1[MMT_MLP2_GROUP];
   GemmProblem g2[MMT_MLP2_GROUP];
   int count;
+  DetScratch det;  // deterministic mode (mmt_det.h): the column sums leave as per-block partials; null base: atomics
 };
+static_assert(sizeof(Mlp2Batch) <= 4096, "Mlp2Batch is a kernel argument");
 bool mmt_mlp2_ok(const Mlp2Batch& b);
 hipError_t mmt_launch_mlp2(const Mlp2Batch& b, hipStream_t s);
 // its backward-data pair in one launch: dh = alpha (dY W2) * (1 - h^2) (g1: A = dY [M][C], B = W2 [C][C/2]
@@ -189,6 +193,7 @@ struct LnBatch {
   // non-finite flag the cross-entropy kernel adds into next), instead of two memset launches
   float* zero_f; int nzero_f;
   int* zero_i; int nzero_i;
+  DetScratch det;  // deterministic mode (mmt_det.h): the column sums leave as per-block partials; null base: atomics
 };
 hipError_t mmt_launch_ln_fwd(const LnBatch& b, int R, int C, hipStream_t s);
 hipError_t mmt_launch_ln_bwd(const LnBatch& b, int R, int C, hipStream_t s);
@@ -245,7 +250,13 @@ inline int64_t mmt_attn_mask_tiles(int B, int H, int T) {
   return (int64_t)B * H * (nt * (nt + 1) / 2);
 }
 inline int64_t mmt_attn_mask_dwords(int B, int H, int T) { return 2 * 32 * mmt_attn_mask_tiles(B, H, T); }
-struct AttnBatch { AttnProblem p[MMT_MAX_GROUP]; int count; };
+struct AttnBatch {
+  AttnProblem p[MMT_MAX_GROUP];
+  int count;
+  // deterministic mode: the fused stage-2 epilogue of the one-pass hs-32 backward (q2_*) stores its dW2 / db1
+  // sums per workgroup (partial index = batch element b)
+  DetScratch det;
+};
 hipError_t mmt_launch_attn_fwd(const AttnBatch& b, int B, int T, int H, int hs, float scale, hipStream_t s);
 hipError_t mmt_launch_attn_bwd(const AttnBatch& b, int B, int T, int H, int hs, float scale, hipStream_t s);
 // true when mmt_launch_attn_bwd runs this batch on the one-pass hs-32 kernel with one KV stream, which
@@ -292,7 +303,7 @@ struct Qkv2Problem {
   float* db1;          // optional: atomic accumulate of the column sums of dh1 [nblk*hs/2] (the stage-1
                        // bias gradient, model.py:36-50), fused so no separate column-sum pass reads dh1
 };
-struct Qkv2Batch { Qkv2Problem p[MMT_MAX_GROUP]; int count; };
+struct Qkv2Batch { Qkv2Problem p[MMT_MAX_GROUP]; int count; DetScratch det; };
 hipError_t mmt_launch_qkv2_fwd(const Qkv2Batch& b, int R, int nblk, int hs, int ld_h1, int ld_out, hipStream_t s);
 hipError_t mmt_launch_qkv2_bwd(const Qkv2Batch& b, int R, int nblk, int hs, int ld_h1, int ld_out, hipStream_t s);
 
@@ -316,7 +327,7 @@ struct EmbProblem {
   int* perm;
   int V;
 };
-struct EmbBatch { EmbProblem p[MMT_MAX_GROUP]; int count; };
+struct EmbBatch { EmbProblem p[MMT_MAX_GROUP]; int count; DetScratch det; };
 bool mmt_emb_sort_ok(const EmbBatch& b, int R, int C);
 hipError_t mmt_launch_emb_sort(const EmbBatch& b, int R, hipStream_t s);
 hipError_t mmt_launch_embed_fwd(const EmbBatch& b, int B, int T, int C, hipStream_t s);
@@ -343,7 +354,7 @@ struct ColsumProblem {
   float alpha;
   int N, ld;
 };
-struct ColsumBatch { ColsumProblem p[MMT_MAX_GROUP]; int count; };
+struct ColsumBatch { ColsumProblem p[MMT_MAX_GROUP]; int count; DetScratch det; };
 hipError_t mmt_launch_colsum(const ColsumBatch& b, int R, hipStream_t s);
 
 // fp32 -> bf16 copy of a list of matrices (rows x cols, src ld = cols, dst ld = dld, pad zeroed).
@@ -373,7 +384,7 @@ struct DropCopyProblem {
   uint32_t drop_key, drop_thr;
   float drop_scale;
 };
-struct DropCopyBatch { DropCopyProblem p[MMT_MAX_GROUP]; int count; };
+struct DropCopyBatch { DropCopyProblem p[MMT_MAX_GROUP]; int count; DetScratch det; };
 hipError_t mmt_launch_drop_copy(const DropCopyBatch& b, int R, int C, hipStream_t s);
 
 hipError_t mmt_launch_adamw(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2,
@@ -382,3 +393,18 @@ hipError_t mmt_launch_adamw(float* p, const float* g, float* m, float* v, int64_
 hipError_t mmt_launch_eval_direction(const float* logits, const int64_t* xb, const int64_t* yb, const double* vocab,
                                      int B, int T, int V, int is_pct, int* wins_losses, double* certainty,
                                      hipStream_t s);
+
+// ------------------------------------------------------------------------------------------
+// Deterministic mode: floats of partial-sum scratch (DetScratch::cap) the largest launch of each producer
+// family needs for `count` problems; the engine's workspace plan takes the maximum
+// ------------------------------------------------------------------------------------------
+int64_t mmt_gemm_det_floats(int count, int M, int N, bool ln);         // GEMM epilogues (ln: the LayerNorm-fused form)
+int64_t mmt_mlp2_bwd_det_floats(int count, int M, int N1);
+int64_t mmt_ln_bwd_det_floats(int count, int R, int C);
+int64_t mmt_colsum_det_floats(int count, int R, int maxn);
+int64_t mmt_drop_copy_det_floats(int count, int R, int C);
+int64_t mmt_qkv2_bwd_det_floats(int count, int R, int nblk, int hs);
+int64_t mmt_attn_q2_det_floats(int count, int B, int H);
+int64_t mmt_embed_bwd_det_floats(int count, int B, int T, int C);
+// whether the token-table gradient of this batch has a fixed summation order (the stable row sort)
+bool mmt_embed_bwd_det_ok(const EmbBatch& b, int R, int C);

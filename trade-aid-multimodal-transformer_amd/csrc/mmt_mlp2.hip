@@ -446,7 +446,12 @@ __global__ __launch_bounds__(512, 1) void mlp2_bwd_kernel(Mlp2Batch batch) {
     }
   }
 
-  if (P1.dbias && tid < N1) atomicAdd(P1.dbias + tid, red[tid] + red[N1 + tid]);  // (published by the stage-2 barriers)
+  if (P1.dbias && tid < N1) {  // (red: published by the stage-2 barriers)
+    const float sum = red[tid] + red[N1 + tid];
+    // deterministic mode (mmt_det.h): the row tile's sums stored at [tile][N1]; the ordered sum adds them
+    if (batch.det.base) batch.det.base[(int64_t)prob * batch.det.stride + (int64_t)tile * N1 + tid] = sum;
+    else atomicAdd(P1.dbias + tid, sum);
+  }
   epilogue_swap<T2, EPI_STORE_BF16, CF::EPI_ROWS>(P2, acc2, lds, P2.o32, P2.alpha, m0, 0, tid, lane, wave);
 
   {
@@ -497,13 +502,36 @@ bool mmt_mlp2_bwd_ok(const Mlp2Batch& b) {
   return true;
 }
 
-hipError_t mmt_launch_mlp2_bwd(const Mlp2Batch& b, hipStream_t s) {
-  if (!mmt_mlp2_bwd_ok(b)) return hipErrorInvalidValue;
+int64_t mmt_mlp2_bwd_det_floats(int count, int M, int N1) {
+  return (int64_t)count * ((M + MLP_BM - 1) / MLP_BM) * N1;
+}
+
+hipError_t mmt_launch_mlp2_bwd(const Mlp2Batch& b0, hipStream_t s) {
+  if (!mmt_mlp2_bwd_ok(b0)) return hipErrorInvalidValue;
+  Mlp2Batch b = b0;
   int mt = 0;
-  for (int g = 0; g < b.count; ++g) mt = std::max(mt, (b.g1[g].M + MLP_BM - 1) / MLP_BM);
-  if (b.g1[0].N == 128) hipLaunchKernelGGL(mlp2_bwd_kernel<128>, dim3(mt, 1, b.count), dim3(512), 0, s, b);
+  bool any_db = false;
+  for (int g = 0; g < b.count; ++g) {
+    mt = std::max(mt, (b.g1[g].M + MLP_BM - 1) / MLP_BM);
+    any_db = any_db || b.g1[g].dbias;
+  }
+  // deterministic mode: db0 as per-row-tile partials [tile][N1] per problem + the ordered sum
+  const int n1 = b.g1[0].N;
+  DetLaunch L;
+  if (b.det.base && any_db) {
+    b.det.stride = (int64_t)mt * n1;
+    const hipError_t e = L.begin(b.det, b.count, b.det.stride, s);
+    if (e != hipSuccess) return e;
+  } else {
+    b.det = DetScratch{};
+  }
+  if (n1 == 128) hipLaunchKernelGGL(mlp2_bwd_kernel<128>, dim3(mt, 1, b.count), dim3(512), 0, s, b);
   else hipLaunchKernelGGL(mlp2_bwd_kernel<256>, dim3(mt, 1, b.count), dim3(512), 0, s, b);
-  return hipGetLastError();
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess || !b.det.base) return e;
+  for (int g = 0; g < b.count; ++g)
+    L.seg(g, b.det.stride, 0, b.g1[g].dbias, (b.g1[g].M + MLP_BM - 1) / MLP_BM, n1);
+  return L.finish();
 }
 
 bool mmt_mlp2_ok(const Mlp2Batch& b) {

@@ -218,6 +218,14 @@ int mmt_op_colsum(void* stream, int32_t R, int32_t N, const void* x, int32_t ld,
   return st(mmt_launch_colsum(b, R, (hipStream_t)stream));
 }
 
+int mmt_op_ordered_sum(void* stream, int32_t nparts, int32_t n, const float* parts, int64_t ld, float* dst) {
+  if (nparts < 1 || n < 0 || ld < n || !parts || !dst) return MMT_ERR_INVALID;
+  DetSumBatch b{};
+  b.count = 1;
+  b.s[0].dst = dst; b.s[0].parts = parts; b.s[0].ld = ld; b.s[0].nparts = nparts; b.s[0].n = n;
+  return st(mmt_launch_ordered_sum(b, (hipStream_t)stream));
+}
+
 int mmt_op_cross_entropy(void* stream, int32_t R, int32_t V, const float* logits, const int64_t* tgt, void* dlogits,
                          int32_t ld_d, float* loss) {
   CeBatch b{};

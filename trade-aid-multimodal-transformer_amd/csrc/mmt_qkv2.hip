@@ -258,8 +258,15 @@ __global__ __launch_bounds__(256) void qkv2_bwd_mfma(Qkv2Batch batch, int R, int
       }
   }
   __syncthreads();
-  if (P.db1 && tid < HH)
-    atomicAdd(P.db1 + (int64_t)blk * HH + tid, (dbr[0][tid] + dbr[1][tid]) + (dbr[2][tid] + dbr[3][tid]));
+  // deterministic mode (mmt_det.h): the block's sums stored at row block (tile / nblk) of the problem's scratch,
+  // dW2 [row blocks][nblk * HS * HH] first, then db1 [row blocks][nblk * HH]; the ordered sum adds them
+  float* const det = batch.det.base ? batch.det.base + (int64_t)blockIdx.z * batch.det.stride : nullptr;
+  const int64_t nrb = gridDim.x / nblk, rbk = tile / nblk;
+  if (P.db1 && tid < HH) {
+    const float v = (dbr[0][tid] + dbr[1][tid]) + (dbr[2][tid] + dbr[3][tid]);
+    if (det) det[(nrb * HS + rbk) * nblk * HH + (int64_t)blk * HH + tid] = v;
+    else atomicAdd(P.db1 + (int64_t)blk * HH + tid, v);
+  }
   float* red = reinterpret_cast<float*>(sd);  // reuse: [4 waves][NOT*32 o][32 i] floats
 #pragma unroll
   for (int ot = 0; ot < NOT; ++ot)
@@ -274,7 +281,8 @@ __global__ __launch_bounds__(256) void qkv2_bwd_mfma(Qkv2Batch batch, int R, int
     float s = 0.f;
 #pragma unroll
     for (int ww = 0; ww < 4; ++ww) s += red[(ww * NOT * 32 + o) * 32 + i];
-    atomicAdd(P.dw2 + (int64_t)blk * HS * HH + q, s);
+    if (det) det[(rbk * nblk + blk) * HS * HH + q] = s;
+    else atomicAdd(P.dw2 + (int64_t)blk * HS * HH + q, s);
   }
 }
 
@@ -481,7 +489,14 @@ __global__ __launch_bounds__(256, MMT_QKV2B_OCC) void qkv2_bwd_v2(Qkv2Batch batc
       for (int e = 0; e < 8; ++e) dbr[w][16 * q + 8 * h + e] = cs[8 * q + e];
   }
   __syncthreads();
-  if (P.db1 && tid < HH) atomicAdd(P.db1 + (int64_t)blk * HH + tid, (dbr[0][tid] + dbr[1][tid]) + (dbr[2][tid] + dbr[3][tid]));
+  // deterministic mode (mmt_det.h): as qkv2_bwd_mfma, the partial index is the row block rb
+  float* const det = batch.det.base ? batch.det.base + (int64_t)blockIdx.z * batch.det.stride : nullptr;
+  const int64_t nrb = gridDim.x / nblk;
+  if (P.db1 && tid < HH) {
+    const float v = (dbr[0][tid] + dbr[1][tid]) + (dbr[2][tid] + dbr[3][tid]);
+    if (det) det[(nrb * HS + rb) * nblk * HH + (int64_t)blk * HH + tid] = v;
+    else atomicAdd(P.db1 + (int64_t)blk * HH + tid, v);
+  }
   // dW2 partials: D[o][i], o = ot*32 + (e&3) + 8(e>>2) + 4h, i = lane r (< HH valid)
   static_assert(HS * HH * 4 <= 4 * (NOT + 1) * 2048, "dW2 reduction fits the images");
   for (int ww = 0; ww < 4; ++ww) {
@@ -499,7 +514,10 @@ __global__ __launch_bounds__(256, MMT_QKV2B_OCC) void qkv2_bwd_v2(Qkv2Batch batc
     }
     __syncthreads();
   }
-  for (int q = tid; q < HS * HH; q += 256) atomicAdd(P.dw2 + (int64_t)blk * HS * HH + q, red[q]);
+  for (int q = tid; q < HS * HH; q += 256) {
+    if (det) det[((int64_t)rb * nblk + blk) * HS * HH + q] = red[q];
+    else atomicAdd(P.dw2 + (int64_t)blk * HS * HH + q, red[q]);
+  }
 }
 
 static int g_qkv2_coal = [] {
@@ -532,9 +550,25 @@ static void qkv2_launch(const Qkv2Batch& b, int R, int nblk, int ld_h1, int ld_o
                        dim3(256), 0, s, b, R, ld_h1, ld_out);
 }
 
-static hipError_t qkv2_dispatch(const Qkv2Batch& b, int R, int nblk, int hs, int ld_h1, int ld_out, bool bwd,
+// rows per backward block (the partial unit of the deterministic mode)
+static int qkv2_bwd_rows(int hs) { return (hs == 32 || hs == 64) ? 4 * 32 * QKV2B_TILES : QKV2_BWD_ROWS; }
+int64_t mmt_qkv2_bwd_det_floats(int count, int R, int nblk, int hs) {
+  const int64_t nrb = (R + qkv2_bwd_rows(hs) - 1) / qkv2_bwd_rows(hs);
+  return (int64_t)count * ((nrb * nblk * (hs * (hs / 2) + hs / 2) + 3) & ~(int64_t)3);
+}
+
+static hipError_t qkv2_dispatch(const Qkv2Batch& b0, int R, int nblk, int hs, int ld_h1, int ld_out, bool bwd,
                                 hipStream_t s) {
-  if (b.count == 0 || R == 0) return hipSuccess;
+  if (b0.count == 0 || R == 0) return hipSuccess;
+  Qkv2Batch b = b0;
+  DetLaunch L;
+  const int nrb = (R + qkv2_bwd_rows(hs) - 1) / qkv2_bwd_rows(hs);
+  if (!bwd) b.det = DetScratch{};
+  if (b.det.base) {  // deterministic mode: dW2 / db1 as per-row-block partials + the ordered sum
+    b.det.stride = mmt_qkv2_bwd_det_floats(1, R, nblk, hs);
+    const hipError_t e = L.begin(b.det, b.count, b.det.stride, s);
+    if (e != hipSuccess) return e;
+  }
   if (!bwd) {  // the forward stores 16-B row pieces of out
     if (ld_out & 7) return hipErrorInvalidValue;
     for (int g = 0; g < b.count; ++g)
@@ -554,7 +588,14 @@ static hipError_t qkv2_dispatch(const Qkv2Batch& b, int R, int nblk, int hs, int
     case 64: qkv2_launch<64>(b, R, nblk, ld_h1, ld_out, bwd, s); break;
     default: return hipErrorInvalidValue;
   }
-  return hipGetLastError();
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess || !b.det.base) return e;
+  const int hh = hs / 2;
+  for (int g = 0; g < b.count; ++g) {
+    L.seg(g, b.det.stride, 0, b.p[g].dw2, nrb, nblk * hs * hh);
+    L.seg(g, b.det.stride, (int64_t)nrb * nblk * hs * hh, b.p[g].db1, nrb, nblk * hh);
+  }
+  return L.finish();
 }
 
 hipError_t mmt_launch_qkv2_fwd(const Qkv2Batch& b, int R, int nblk, int hs, int ld_h1, int ld_out, hipStream_t s) {

@@ -18,6 +18,12 @@ onto the compute stream before the optimizer step.
 xGMI is point-to-point (7 links per GPU); RCCL's ring all-reduce is per-link bound, so a few
 large buckets (25-50 MB) beat many small ones: at C1 (84 MB of fp32 gradient) that is about
 three buckets per step.
+
+Determinism: the deterministic training mode (`MultimodalTransformer.set_deterministic`,
+include/mmt.h) fixes the order of every sum inside one rank's backward. It does NOT cover this
+module's all-reduce: RCCL may add the ranks' slices in an order that depends on the algorithm and
+topology it picks, so at world size > 1 the averaged gradient is reproducible only as far as RCCL
+is. At world size 1 nothing is exchanged and the guarantee holds unchanged.
 """
 import torch
 import torch.distributed as dist

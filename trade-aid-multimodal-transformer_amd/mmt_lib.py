@@ -72,6 +72,8 @@ _SIGS = {
     "mmt_probe_read": (c_i32, [c_vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(c_i64)]),
     "mmt_probe_enable": (c_i32, [c_vp, c_i32]),
     "mmt_set_side_stream": (c_i32, [c_vp, c_i32]),
+    "mmt_set_deterministic": (c_i32, [c_vp, c_i32]),
+    "mmt_get_deterministic": (c_i32, [c_vp]),
     "mmt_probe_count": (c_i32, [c_vp]),
     "mmt_probe_read_at": (c_i32, [c_vp, c_i32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(c_i64),
                                   ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
@@ -121,6 +123,7 @@ _SIGS = {
     "mmt_op_qkv2_fwd": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_i32]),
     "mmt_op_qkv2_bwd": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp]),
     "mmt_op_colsum": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_f32]),
+    "mmt_op_ordered_sum": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_i64, c_vp]),
     "mmt_op_cross_entropy": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp]),
     "mmt_op_embedding_fwd": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "mmt_op_embedding_bwd": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),

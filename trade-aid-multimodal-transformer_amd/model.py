@@ -32,7 +32,8 @@ import torch
 import torch.nn as nn
 
 import mmt_lib as ML
-from config_utils import _get_block_size, _get_dropout, _get_n_embd, _get_n_head, _get_n_layer, _get_precision
+from config_utils import (_get_block_size, _get_deterministic, _get_dropout, _get_n_embd, _get_n_head, _get_n_layer,
+                          _get_precision)
 
 
 class _MmtStep(torch.autograd.Function):
@@ -95,6 +96,8 @@ class MultimodalTransformer(nn.Module):
         if not ctx:
             raise ML.MmtError("mmt_create failed: " + L.mmt_create_error().decode())
         self._ctx = ctypes.c_void_p(ctx)
+        self.deterministic = False
+        self.set_deterministic(_get_deterministic())
         n = L.mmt_param_count(self._ctx)
         self._n_active = L.mmt_param_active_count(self._ctx)
         self._tensors = []
@@ -121,6 +124,13 @@ class MultimodalTransformer(nn.Module):
         self._gen = 0
         self._last = None
         self._grad_sync = None  # mmt_dist.GradSync when data parallel
+
+    def set_deterministic(self, on):
+        """Deterministic training mode (include/mmt.h, mmt_set_deterministic): bit-identical gradients
+        for identical inputs, parameters and dropout seed. Applies from the next forward on (a forward
+        and its backward always run under one setting)."""
+        ML.check(ML.lib().mmt_set_deterministic(self._ctx, 1 if on else 0), self._ctx, "mmt_set_deterministic")
+        self.deterministic = bool(ML.lib().mmt_get_deterministic(self._ctx))
 
     # ------------------------------------------------------------------ layout / state_dict
     def _make_tril_keys(self):
