@@ -208,7 +208,9 @@ int mmt_exact_walk(void* stream, int32_t nmod, int32_t* const* data, const int64
                    const int32_t* vocab, uint32_t* mt_state, const uint32_t* words, int64_t nwords, void* scratch,
                    int64_t scratch_bytes, int32_t* status);
 /* tuning knob: bit 0 / bit 1 = the slice-streamed hs-64 attention dK/dV / dQ pass, bit 2 = dK/dV at 3 waves
- * per SIMD, bit 3 = the slice-streamed hs-64 forward (default 15); returns the old value */
+ * per SIMD, bit 3 = the slice-streamed hs-64 forward, bit 5 = the one-pass hs-64 backward at T <= 512 with one
+ * KV stream, bit 6 = the one-pass hs-32 backward at T <= 256, bit 7 = that kernel also for several KV streams
+ * (default 79 = 15 | 64; env MMT_ATTN_RING); returns the old value */
 int mmt_attn_set_ring(int v);
 /* tuning knob: attention dropout keep-bit tiles made per wave by attn_mask_kernel (1, 2, 4, 8 or 16; 0 = the env
  * MMT_MASK_G, default 16 at T >= 1024, else 8). The bits do not depend on it. Returns the old value */

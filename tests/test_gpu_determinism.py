@@ -207,8 +207,8 @@ def test_attn_qkv2_fused_matches_separate(name):
 
 @pytest.mark.parametrize("name", ["f_small", "f_c1"])
 def test_attn_mask_tiles_per_wave_same_bits(name):
-    """attn_mask_kernel makes G keep-bit tiles per wave (mmt_attn_set_mask_g; default 8), walking key
-    tile, query tile, (b, h) and KV stream in the wave. The bits are a hash of their coordinates only,
+    """attn_mask_kernel makes G keep-bit tiles per wave (mmt_attn_set_mask_g; default 16 at T >= 1024, else
+    8), walking key tile, query tile, (b, h) and KV stream in the wave. The bits are a hash of their coordinates only,
     so every G gives the same forward bitwise (G = 1: one tile per wave, the round-5 form; G = 8 wraps
     the 36-tile triangle of T = 256 and f_small's cross-attention stream boundaries inside waves)."""
     L = ML.lib()

@@ -4,6 +4,8 @@ shapes and init kinds (mmt_create needs no device: device tables are created laz
 import ctypes
 import os
 import re
+import subprocess
+import sys
 
 import pytest
 import torch
@@ -103,3 +105,40 @@ def test_backward_stage_ranges_tile_the_active_prefix():
         assert ranges[-1][1] == L.mmt_param_active_count(ctx)
     finally:
         L.mmt_destroy(ctx)
+
+
+# (environment variable, setter that returns the previous value, default, a distinct legal value)
+ENV_KNOBS = [
+    ("MMT_ATTN_RING", "mmt_attn_set_ring", 79, 15),
+    ("MMT_RELU_BITS", "mmt_set_relu_bits", 0, 1),
+    ("MMT_DROP_COPY_FUSE", "mmt_set_drop_copy_fuse", 1, 0),
+    ("MMT_ATTN_QKV2", "mmt_set_attn_qkv2", 1, 0),
+    ("MMT_MLP2_BM", "mmt_mlp2_set_bm", 128, 64),
+    ("MMT_QKV2_COAL", "mmt_qkv2_set_coal", 2, 1),
+    ("MMT_EMB_SORT", "mmt_emb_set_sort", 1, 0),
+    ("MMT_GEMM_T2", "mmt_gemm_set_t2", 0, 1),
+]
+
+
+def _knobs_in_child(extra_env):
+    """The knobs' start values in a fresh process: each setter's first call returns what the library read
+    from the environment when it was loaded. The child only loads the library (no torch, no device)."""
+    code = ("import ctypes, sys\n"
+            "L = ctypes.CDLL(sys.argv[1])\n"
+            "for n in sys.argv[2:]:\n"
+            "    f = getattr(L, n); f.restype = ctypes.c_int; f.argtypes = [ctypes.c_int]\n"
+            "    print(n, f(0))\n")
+    env = {k: v for k, v in os.environ.items() if not k.startswith("MMT_")}
+    env.update(extra_env)
+    out = subprocess.run([sys.executable, "-c", code, ML.LIB_PATH] + [k[1] for k in ENV_KNOBS], env=env, check=True,
+                         capture_output=True, text=True, timeout=60).stdout
+    return {n: int(v) for n, v in (line.split() for line in out.splitlines())}
+
+
+def test_env_knob_defaults_and_overrides():
+    got = _knobs_in_child({})
+    assert got == {setter: dflt for _, setter, dflt, _ in ENV_KNOBS}
+    for var, setter, dflt, val in ENV_KNOBS:
+        assert val != dflt
+        got = _knobs_in_child({var: str(val)})  # nothing set but the variable under test
+        assert got == {s: (val if s == setter else d) for _, s, d, _ in ENV_KNOBS}, var

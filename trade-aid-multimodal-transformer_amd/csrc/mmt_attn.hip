@@ -1078,6 +1078,9 @@ __global__ __launch_bounds__(256, MMT_DKDV1_MINB(HS)) void attn_bwd_dkdv1_kernel
 // LDS 78 KiB (two workgroups per CU): Q / dO images 2 x 18 KiB, tables 2 KiB, slots 4 x 2 KiB, dQ
 // partials 2 x 4 x 4 KiB. dS is accumulated divided by the dropout scale sc (as the dK/dV pass:
 // dS / sc = Z P dP - P D'), so dK and dQ take the factor sc at the end.
+// The alternatives that were measured and lost (a walk without per-step barriers, a two-tile body,
+// separate masked / unmasked bodies, a reversed walk in every second workgroup) are recorded with
+// their numbers in DESIGN.md section 3, round 6.
 // =============================================================================================
 namespace {
 typedef int32_t ai32x4 __attribute__((ext_vector_type(4)));
@@ -1137,51 +1140,19 @@ __device__ __forceinline__ float a_sum32(float v) {
 }
 }  // namespace
 
-#ifndef MMT_F32_BRANCH
-#define MMT_F32_BRANCH 0
-#endif
-#ifndef MMT_F32_REV
-#define MMT_F32_REV 0
-#endif
-#ifndef MMT_F32_Q2_NOATOM
-#define MMT_F32_Q2_NOATOM 0  // timing experiment: the stage-2 dW2 sums not added (wrong gradient)
-#endif
-#ifndef MMT_F32_PAIR
-#define MMT_F32_PAIR 0  // 1: the two-tile body where both owned key tiles are active (register copies: slower)
-#endif
 // MS: several KV streams (cross-attention); Q2: the Q/K/V stage-2 backward fused into the epilogue
 // (AttnProblem::q2_*, self-attention only)
-#ifndef MMT_F32_NB
-// 1: one KV stream walked without per-step barriers, dQ summed by LDS float atomics (ds_add_f32). Measured
-// (tools/attn_bench.py c1, profiles/r6pq_fused32_nb.txt): 93 -> 309 us with the atomics, 80 us with plain
-// stores in their place (wrong sums: the walk itself would gain 14 %); the LDS float atomics cost the
-// difference. 2: the free walk with per-step partials summed by each query tile's last contributor
-// (correct; 93.9 -> 111.8 us: the one-wave sum sits on the critical path). The per-step partials and
-// barrier stay
-#define MMT_F32_NB 0
-#endif
 // DET (Q2 only; deterministic mode, mmt_det.h): a separate instantiation whose stage-2 epilogue stores the
 // workgroup's dW2 / db1 sums as partials (partial index = batch element b) instead of adding them by atomics
 template <bool DROP, bool MS, bool Q2, bool DET = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd_fused32(AttnBatch batch, int T, int H, float scale) {
   static_assert(!(MS && Q2), "the stage-2 backward follows the self-attention only");
   static_assert(!DET || Q2, "only the stage-2 epilogue has sums to store");
-  // NB (off: see MMT_F32_NB): every wave walks its own (query tile, key tile) products without waiting for the others: the
-  // Q / dO images are complete before the walk, and the dQ contributions go into per-tile fp32 sums
-  // in LDS ([8 tiles][32 d][32 q], ds_add_f32) instead of per-step partials reduced behind a barrier.
-  // The per-step barrier held every wave to the step's slowest (2 tiles against 0-1 elsewhere: 12
-  // tile times per walk where each wave owns 9)
-  constexpr bool NB = !MS && MMT_F32_NB == 1;
-  // NB2 (MMT_F32_NB=2): the same free walk with the per-step partials kept (two slots per wave, tile qt in
-  // slot (qt - w) & 1) and summed by the LAST contributor of each query tile (an LDS arrival counter per
-  // tile); a wave reuses a slot only after the tile that held it was summed (a done flag per tile)
-  constexpr bool NB2 = !MS && MMT_F32_NB == 2;
   constexpr int IMG = 8 * SL_SLICE;               // 256 rows x 32 columns as slice images
   constexpr int OFF_DO = IMG, OFF_TAB = 2 * IMG;  // tables: -LSE2 [256], -D (-D / sc under dropout) [256]
   constexpr int OFF_DS = OFF_TAB + 2048;          // per-wave [32][32] bf16 transpose slots
   constexpr int OFF_DQ = OFF_DS + 4 * 2048;       // dQ partials [2 steps][4 waves][32 q][32 d] fp32
-  constexpr int OFF_SYNC = OFF_DQ + 8 * 4096;     // NB2: arrival counters [8], done flags [8]
-  constexpr int BYTES = OFF_SYNC + (MMT_F32_NB == 2 ? 64 : 0);
+  constexpr int BYTES = OFF_DQ + 8 * 4096;
   static_assert(2 * BYTES <= 160 * 1024, "two workgroups per CU");
   constexpr int EPW = 40;                          // epilogue transpose row stride (bf16)
   static_assert(4 * 32 * EPW * 2 <= 4 * 4096, "epilogue transposes alias one parity of the dQ partials");
@@ -1194,13 +1165,11 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_fused32(AttnBatch batch, int 
   const int r = lane & 31, h = lane >> 5;
   const int64_t rowbase = (int64_t)b * T;
   const float c2 = scale * kLog2e;
-  const bool ragged = (T & 31) != 0;
   const int kts[2] = {w, 7 - w};
-  // walk direction: MMT_F32_REV sends the second slot's workgroups of the first generation (blocks
-  // 256 .. 511: one per CU) down from the last query tile, so the two co-resident workgroups are in
-  // opposite phases of the causal imbalance (light first steps vs heavy last steps)
-  const bool rev = MMT_F32_REV && ((blockIdx.x >> 8) & 1);
-  auto step_qt = [&](int i) { return rev ? nt - 1 - i : i; };
+  // vector-memory operations a wave may leave in flight at step qt's barrier, behind its piece of slice
+  // qt + 1: the pieces of slices qt + 2 .. nt - 1 and (not Q2: no dQ stores in the loop) the dQ stores of
+  // steps 0 .. qt - 1
+  auto in_flight = [&](int qt) { return Q2 ? nt - 2 - qt : nt - 2; };
 
   // Prologue. Every global load of the kernel is issued here and waited for (pinned) BEFORE the Q / dO
   // slices go out by LDS-DMA (the compiler counts only its own loads, so a wait it places while DMAs it
@@ -1222,11 +1191,10 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_fused32(AttnBatch batch, int 
 #pragma unroll
   for (int t = 0; t < 2; ++t)
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {  // step i's query tile
-      const int q = step_qt(i);
-      mwq[t][i] = 0u;
-      if (DROP && i < nt && kts[t] <= q)
-        mwq[t][i] = P.dmask[j][((int64_t)bh * ntri + q * (q + 1) / 2 + kts[t]) * 32 + key_dword(r)];
+    for (int q = 0; q < 8; ++q) {  // step q walks query tile q
+      mwq[t][q] = 0u;
+      if (DROP && q < nt && kts[t] <= q)
+        mwq[t][q] = P.dmask[j][((int64_t)bh * ntri + q * (q + 1) / 2 + kts[t]) * 32 + key_dword(r)];
     }
   bf16x8 kf[2][2], vf[2][2];
 #pragma unroll
@@ -1306,8 +1274,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_fused32(AttnBatch batch, int 
     const ai32x4 rs = a_rsrc((op ? P.dout : P.q) + rowbase * ld + head * 32, (int64_t)T * ld * 2);
     const int prow = lane >> 1, pcol = 8 * ((lane & 1) ^ ((prow >> 3) & 1));
     char* dst = lds + op * OFF_DO + cb * SL_SUB;
-    for (int i = 0; i < nt; ++i) {  // in step order
-      const int sl = step_qt(i);
+    for (int sl = 0; sl < nt; ++sl) {  // in step order
       const int grow = sl * 32 + prow;
       const int voff = grow < T ? (grow * ld + cb * 16 + pcol) * 2 : A_OOB;
       a_dma16(rs, __builtin_amdgcn_readfirstlane(a_lds_u32(dst + sl * SL_SLICE)), voff);
@@ -1351,28 +1318,20 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_fused32(AttnBatch batch, int 
     for (int s = 0; s < 2; ++s) ktf[t][s] = join4(lds_tr16(slot + o_da0 + 1024 * s), lds_tr16(slot + o_da1 + 1024 * s));
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   }
-  if (NB || NB2) {  // the whole Q / dO images before the walk; the dQ sums / the sync words start at zero
-    if (NB) {
-#pragma unroll
-      for (int k = 0; k < 8; ++k) *reinterpret_cast<f32x4*>(lds + OFF_DQ + k * 4096 + tid * 16) = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-    if (NB2 && tid < 16) reinterpret_cast<int*>(lds + OFF_SYNC)[tid] = 0;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  } else if (j == 0) a_wait_vm(nt - 1);  // this wave's piece of slice 0 (the younger nt - 1 pieces stay in flight)
+  if (j == 0) a_wait_vm(nt - 1);  // this wave's piece of slice 0 (the younger nt - 1 pieces stay in flight)
   else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the previous stream's dQ-sum stores are done
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();  // everyone's slice-0 pieces and table entries (later streams: and every
                                  // wave is past the previous stream's epilogue)
 
   // element e of a tile accumulator is query row (e & 3) + 8 (e >> 2) + 4 h of the tile, key r: bit e
-  // of m_diag keeps the diagonal tile's causal half, bit e of m_rows the rows of a ragged last query
-  // tile that lie before T (its keys past T then lie above the diagonal)
-  uint32_t m_diag = 0, m_rows = 0;
+  // of m_diag keeps the diagonal tile's causal half. A ragged last query tile needs no mask of its own:
+  // its rows past T have -inf LSE-table entries, and its keys past T lie above the diagonal
+  uint32_t m_diag = 0;
 #pragma unroll
   for (int e = 0; e < 16; ++e) {
     const int row = (e & 3) + 8 * (e >> 2) + 4 * h;
     m_diag |= (uint32_t)(r <= row) << e;
-    m_rows |= (uint32_t)((nt - 1) * 32 + row < T) << e;
   }
   const bf16_t* qimg = reinterpret_cast<const bf16_t*>(lds);
   const bf16_t* dimg = reinterpret_cast<const bf16_t*>(lds + OFF_DO);
@@ -1380,10 +1339,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_fused32(AttnBatch batch, int 
 #pragma unroll
   for (int t = 0; t < 2; ++t) { zero16(dk[t]); zero16(dv[t]); }
 
-  // one owned key tile (t) against query tile qt; mw: the tile's keep bits (key r, this lane's half),
-  // mk: the causal / ragged mask bits of a MASKED tile
-  auto tile = [&](auto mc, int qt, int t, uint32_t mw, uint32_t mk, f32x16& dqp, bool diag) {
-    constexpr bool MASKED = decltype(mc)::value;
+  // one owned key tile (t) against query tile qt; mw: the tile's keep bits (key r, this lane's half);
+  // diag: the tile on the causal diagonal (kt == qt)
+  auto tile = [&](int qt, int t, uint32_t mw, f32x16& dqp, bool diag) {
     asm volatile("" ::: "memory");  // the slot's previous reads stay ahead of this tile's writes
     const int q0 = qt * 32;
     bf16x8 qr[2], dr[2];
@@ -1400,10 +1358,10 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_fused32(AttnBatch batch, int 
       sacc = mfma32(qr[s], kf[t][s], sacc);    // S[q][key]
       dpacc = mfma32(dr[s], vf[t][s], dpacc);  // dP[q][key]
     }
-    if (!MASKED && MMT_F32_BRANCH == 0 && diag) {  // wave-uniform: the diagonal tile
+    if (diag) {  // wave-uniform: scores above the diagonal become -inf, touching only the score accumulator
       asm volatile("" ::: "memory");  // a real branch: selects on every tile cost 16 VALU
 #pragma unroll
-      for (int e = 0; e < 16; ++e) sacc[e] = (mk >> e) & 1 ? sacc[e] : -INFINITY;
+      for (int e = 0; e < 16; ++e) sacc[e] = (m_diag >> e) & 1 ? sacc[e] : -INFINITY;
     }
     uint32_t pp[8], dd[8];  // packed bf16 pairs of Z P (dV operand) and dS / sc (dK operand)
 #pragma unroll
@@ -1416,8 +1374,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_fused32(AttnBatch batch, int 
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
           const int e = 4 * gg + e4 + u;
-          float pv = ex2(__builtin_fmaf(sacc[e], c2, l4[e4 + u]));
-          if (MASKED) pv = keep_f(pv, __builtin_amdgcn_sbfe((int)mk, e, 1));
+          const float pv = ex2(__builtin_fmaf(sacc[e], c2, l4[e4 + u]));
           if (DROP) {
             int kb = __builtin_amdgcn_sbfe((int)mw, 8 * gg + e4 + u, 1);  // all ones iff kept
             asm volatile("" : "+v"(kb));
@@ -1456,220 +1413,13 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_fused32(AttnBatch batch, int 
     }
   };
 
-  // both owned key tiles against query tile qt in one straight-line body (qt >= 7 - w): the Q / dO row and
-  // transposed fragments and the LSE / D rows are read once for the two tiles, and the two tiles' S / dP ->
-  // softmax -> dV / dK chains are independent, so one's MFMAs overlap the other's VALU in the wave
-  auto tile2 = [&](int qt, uint32_t mwa, uint32_t mwb, f32x16& dqp, bool diagA, bool diagB) {
-    asm volatile("" ::: "memory");
-    const int q0 = qt * 32;
-    bf16x8 qr[2], dr[2];
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      qr[s] = sl_row(qimg, q0, r, s, h);
-      dr[s] = sl_row(dimg, q0, r, s, h);
-    }
-    f32x16 sacc[2], dpacc[2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      zero16(sacc[t]);
-      zero16(dpacc[t]);
-    }
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        sacc[t] = mfma32(qr[s], kf[t][s], sacc[t]);
-        dpacc[t] = mfma32(dr[s], vf[t][s], dpacc[t]);
-      }
-    if (diagA || diagB) {  // wave-uniform
-      asm volatile("" ::: "memory");
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int e = 0; e < 16; ++e)
-          sacc[t][e] = ((t ? diagB : diagA) && !((m_diag >> e) & 1)) ? -INFINITY : sacc[t][e];
-    }
-    uint32_t pp[2][8], dd[2][8];
-#pragma unroll
-    for (int gg = 0; gg < 4; ++gg) {
-      const f32x4 l4 = *reinterpret_cast<const f32x4*>(tab + q0 + 8 * gg + 4 * h);
-      const f32x4 d4 = *reinterpret_cast<const f32x4*>(tab + 256 + q0 + 8 * gg + 4 * h);
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        const uint32_t mw = t ? mwb : mwa;
-#pragma unroll
-        for (int e4 = 0; e4 < 4; e4 += 2) {
-          float pm[2], ds[2];
-#pragma unroll
-          for (int u = 0; u < 2; ++u) {
-            const int e = 4 * gg + e4 + u;
-            const float pv = ex2(__builtin_fmaf(sacc[t][e], c2, l4[e4 + u]));
-            if (DROP) {
-              int kb = __builtin_amdgcn_sbfe((int)mw, 8 * gg + e4 + u, 1);
-              asm volatile("" : "+v"(kb));
-              pm[u] = keep_f(pv, kb);
-              ds[u] = __builtin_fmaf(pm[u], dpacc[t][e], pv * d4[e4 + u]);
-            } else {
-              pm[u] = pv;
-              ds[u] = pv * (dpacc[t][e] + d4[e4 + u]);
-            }
-          }
-          pp[t][2 * gg + e4 / 2] = pack2bf(pm[0], pm[1]);
-          dd[t][2 * gg + e4 / 2] = pack2bf(ds[0], ds[1]);
-        }
-      }
-    }
-    bf16x8 dot[2], qtr[2];
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      dot[s] = sl_tr(dimg, q0, s, lane);
-      qtr[s] = sl_tr(qimg, q0, s, lane);
-    }
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      // tile t's dS through the slot (tile 1 writes after tile 0's dS^T reads: in-order LDS per wave)
-#pragma unroll
-      for (int gg = 0; gg < 4; ++gg)
-        *reinterpret_cast<u32x2*>(slot + sw(2 * gg + h)) = u32x2{dd[t][2 * gg], dd[t][2 * gg + 1]};
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        const bf16x8 pf = __builtin_bit_cast(bf16x8, u32x4{pp[t][4 * s], pp[t][4 * s + 1], pp[t][4 * s + 2], pp[t][4 * s + 3]});
-        const bf16x8 df = __builtin_bit_cast(bf16x8, u32x4{dd[t][4 * s], dd[t][4 * s + 1], dd[t][4 * s + 2], dd[t][4 * s + 3]});
-        dv[t] = mfma32(pf, dot[s], dv[t]);
-        dk[t] = mfma32(df, qtr[s], dk[t]);
-      }
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        const bf16x8 da = join4(lds_tr16(slot + o_da0 + 1024 * s), lds_tr16(slot + o_da1 + 1024 * s));
-        dqp = mfma32(ktf[t][s], da, dqp);
-      }
-      asm volatile("" ::: "memory");
-    }
-  };
-
   const float dqs = DROP ? scale * P.drop_scale : scale;
   const ai32x4 rdq = a_rsrc(P.dq + rowbase * P.dq_ld + head * 32, (int64_t)T * P.dq_ld * 2);
   const int R = 8 * w + (lane >> 3), cq = lane & 7;  // this wave's dQ rows / 16-B column chunk
-#ifndef MMT_F32_SKIP
-#define MMT_F32_SKIP 0
-#endif
-  if constexpr (NB) {
+  // The walk: all waves take query tile qt in step qt, one barrier per step. The diagonal tile's causal
+  // mask is the only one (tile()); the dQ partials are double-buffered by step parity.
 #pragma unroll 1
-    for (int i = 0; i < nt; ++i) {
-      const int qt = i;
-      const uint32_t cA = mwq[0][0] >> (4 * h), cB = mwq[1][0] >> (4 * h);
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int q = 0; q < 7; ++q) mwq[t][q] = mwq[t][q + 1];
-      if (kts[0] > qt) continue;  // wave-uniform: no owned key tile at or below query tile qt yet
-      f32x16 dqp;
-      zero16(dqp);
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        const int kt = kts[t];
-        if (kt < nt && kt <= qt) tile(std::false_type{}, qt, t, t ? cB : cA, m_diag, dqp, kt == qt);
-      }
-      // dQ^T[d][q] of the tile: element e is d = (e & 3) + 8 (e >> 2) + 4 h, lane r is q; 32 lanes a bank row
-      float* acc = reinterpret_cast<float*>(lds + OFF_DQ + qt * 4096) + 4 * h * 32 + r;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-#ifdef MMT_F32_NB_NOATOM  // timing experiment: plain stores (wrong sums)
-        acc[((e & 3) + 8 * (e >> 2)) * 32] = dqp[e];
-#else
-        __hip_atomic_fetch_add(acc + ((e & 3) + 8 * (e >> 2)) * 32, dqp[e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#endif
-      }
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();  // every dQ contribution is in
-    // the wave's two query tiles (the rows of its key tiles): lane (r, h) row r, columns 16 h .. 16 h + 15,
-    // scaled to bf16 into the spent Q image (Q2: the stage-2 operand) or stored
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      const int qt = kts[t];
-      if (qt >= nt) continue;
-      const float* acc = reinterpret_cast<const float*>(lds + OFF_DQ + qt * 4096) + 16 * h * 32 + r;
-      uint32_t pk[8];
-#pragma unroll
-      for (int k = 0; k < 8; ++k) pk[k] = pack2bf(acc[(2 * k) * 32] * dqs, acc[(2 * k + 1) * 32] * dqs);
-      if (Q2) {
-        *reinterpret_cast<u32x4*>(lds + qt * SL_SLICE + sl_off(r, 2 * h)) = u32x4{pk[0], pk[1], pk[2], pk[3]};
-        *reinterpret_cast<u32x4*>(lds + qt * SL_SLICE + sl_off(r, 2 * h + 1)) = u32x4{pk[4], pk[5], pk[6], pk[7]};
-      } else {
-        const int tq = qt * 32 + r;
-        if (tq < T) {
-          u32x2* d = reinterpret_cast<u32x2*>(P.dq + (rowbase + tq) * P.dq_ld + head * 32 + 16 * h);
-#pragma unroll
-          for (int k = 0; k < 4; ++k) d[k] = u32x2{pk[2 * k], pk[2 * k + 1]};
-        }
-      }
-    }
-    // the dQ sums are spent before the epilogue transposes / stage-2 images reuse their LDS
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-  } else if constexpr (NB2) {
-    int* const cnt = reinterpret_cast<int*>(lds + OFF_SYNC);
-    int* const done = cnt + 8;
-#pragma unroll 1
-    for (int i = 0; i < nt; ++i) {
-      const int qt = i;
-      const uint32_t cA = mwq[0][0] >> (4 * h), cB = mwq[1][0] >> (4 * h);
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int q = 0; q < 7; ++q) mwq[t][q] = mwq[t][q + 1];
-      if (kts[0] > qt) continue;  // wave-uniform: not a contributor of query tile qt
-      f32x16 dqp;
-      zero16(dqp);
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        const int kt = kts[t];
-        if (kt < nt && kt <= qt) tile(std::false_type{}, qt, t, t ? cB : cA, m_diag, dqp, kt == qt);
-      }
-      // the slot last held tile qt - 2: wait until its sum has read it (bounded: a lost flag cannot hang)
-      if (qt - 2 >= w) {
-        for (int it = 0; it < (1 << 22); ++it) {
-          if (__hip_atomic_load(done + qt - 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) break;
-          __builtin_amdgcn_s_sleep(1);
-        }
-      }
-      char* part = lds + OFF_DQ + (((qt - w) & 1) * 4 + w) * 4096;
-#pragma unroll
-      for (int gg = 0; gg < 4; ++gg)
-        *reinterpret_cast<f32x4*>(part + r * 128 + (((2 * gg + h) ^ (r & 7)) << 4)) =
-            f32x4{dqp[4 * gg], dqp[4 * gg + 1], dqp[4 * gg + 2], dqp[4 * gg + 3]};
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the partial is in before the arrival counts it
-      int old = 0;
-      if (lane == 0) old = __hip_atomic_fetch_add(cnt + qt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      old = __builtin_amdgcn_readfirstlane(old);
-      const int nc = min(qt + 1, 4);  // contributors: waves u <= qt
-      if (old == nc - 1) {  // the last one: sum the tile (4 passes of 8 rows), then free the slots
-#pragma unroll
-        for (int ps = 0; ps < 4; ++ps) {
-          const int R = 8 * ps + (lane >> 3), cq = lane & 7;
-          f32x4 a = {0.f, 0.f, 0.f, 0.f};
-          for (int u = 0; u < nc; ++u)
-            a += *reinterpret_cast<const f32x4*>(lds + OFF_DQ + (((qt - u) & 1) * 4 + u) * 4096 + R * 128 + ((cq ^ (R & 7)) << 4));
-          const int tq = qt * 32 + R;
-          if (Q2) {
-            *reinterpret_cast<u32x2*>(lds + qt * SL_SLICE + sl_off(R, cq >> 1) + (cq & 1) * 8) =
-                u32x2{pack2bf(a[0] * dqs, a[1] * dqs), pack2bf(a[2] * dqs, a[3] * dqs)};
-          } else {
-            a_bst8(rdq, tq < T ? (tq * P.dq_ld + 4 * cq) * 2 : A_OOB,
-                   u32x2{pack2bf(a[0] * dqs, a[1] * dqs), pack2bf(a[2] * dqs, a[3] * dqs)});
-          }
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the partial reads are done
-        if (lane == 0) __hip_atomic_store(done + qt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      }
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();  // every tile is summed (each inside its last contributor's walk)
-  } else
-#pragma unroll 1
-  for (int i = 0; i < (MMT_F32_SKIP ? 0 : nt); ++i) {
-    const int qt = step_qt(i);
+  for (int qt = 0; qt < nt; ++qt) {
     const uint32_t cA = mwq[0][0] >> (4 * h), cB = mwq[1][0] >> (4 * h);
 #pragma unroll
     for (int t = 0; t < 2; ++t)
@@ -1677,51 +1427,26 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_fused32(AttnBatch batch, int 
       for (int q = 0; q < 7; ++q) mwq[t][q] = mwq[t][q + 1];
     f32x16 dqp;
     zero16(dqp);
-    const bool last_ragged = ragged && qt == nt - 1;
-#if MMT_F32_PAIR
-    if (kts[1] < nt && kts[1] <= qt) {  // both tiles (kts[0] < kts[1])
-      tile2(qt, cA, cB, dqp, kts[0] == qt, kts[1] == qt);
-    } else if (kts[0] <= qt) {
-      tile(std::false_type{}, qt, 0, cA, m_diag, dqp, kts[0] == qt);
-    }
-#else
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
       const int kt = kts[t];
-      if (kt < nt && kt <= qt) {
-        const uint32_t mw = t ? cB : cA;
-        const uint32_t mk = (kt == qt ? m_diag : 0xffffu) & (last_ragged ? m_rows : 0xffffu);
-#if MMT_F32_BRANCH == 1
-        // separate masked / unmasked tile bodies: the accumulators then take register copies at the joins
-        if (kt == qt || last_ragged) tile(std::true_type{}, qt, t, mw, mk, dqp, false);
-        else tile(std::false_type{}, qt, t, mw, mk, dqp, false);
-#elif MMT_F32_BRANCH == 2
-        tile(std::true_type{}, qt, t, mw, mk, dqp, false);  // one body, the mask applied on every tile
-#else
-        // one body; the diagonal tile's scores above the diagonal become -inf in a branch that touches
-        // only the score accumulator (rows past T: -inf LSE-table entries)
-        tile(std::false_type{}, qt, t, mw, m_diag, dqp, kt == qt);
-#endif
-      }
+      if (kt < nt && kt <= qt) tile(qt, t, t ? cB : cA, dqp, kt == qt);
     }
-#endif
-    char* part = lds + OFF_DQ + ((i & 1) * 4 + w) * 4096;
+    char* part = lds + OFF_DQ + ((qt & 1) * 4 + w) * 4096;
     if (w <= qt) {  // this wave had a tile in the step (its key tile w is the lower one)
 #pragma unroll
       for (int gg = 0; gg < 4; ++gg)
         *reinterpret_cast<f32x4*>(part + r * 128 + (((2 * gg + h) ^ (r & 7)) << 4)) =
             f32x4{dqp[4 * gg], dqp[4 * gg + 1], dqp[4 * gg + 2], dqp[4 * gg + 3]};
     }
-    // this wave's piece of slice qt + 1: younger are the pieces of slices qt + 2 .. nt - 1 and the dQ
-    // stores of steps 0 .. qt - 1, nt - 2 operations at every step
-    if (j == 0 && i + 1 < nt) a_wait_vm(Q2 ? nt - 2 - i : nt - 2);  // Q2: no dQ stores in the loop
+    if (j == 0 && qt + 1 < nt) a_wait_vm(in_flight(qt));  // this wave's piece of slice qt + 1
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();  // every partial of step qt is written; slice qt + 1 landed
     {
       const int nw = min(qt + 1, 4);
       f32x4 a = {0.f, 0.f, 0.f, 0.f};
       for (int u = 0; u < nw; ++u)
-        a += *reinterpret_cast<const f32x4*>(lds + OFF_DQ + ((i & 1) * 4 + u) * 4096 + R * 128 + ((cq ^ (R & 7)) << 4));
+        a += *reinterpret_cast<const f32x4*>(lds + OFF_DQ + ((qt & 1) * 4 + u) * 4096 + R * 128 + ((cq ^ (R & 7)) << 4));
       const int tq = qt * 32 + R;
       if (Q2) {  // dQ rows into the (spent) Q slice of this step, for the stage-2 backward after the walk
         *reinterpret_cast<u32x2*>(lds + qt * SL_SLICE + sl_off(R, cq >> 1) + (cq & 1) * 8) =
@@ -1887,11 +1612,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_fused32(AttnBatch batch, int 
     for (int q = tid; q < 3 * 512; q += 256) {
       const float v = (red[q] + red[1536 + q]) + (red[3072 + q] + red[4608 + q]);
       const int kd = q / 512, oi = q % 512;
-#if !MMT_F32_Q2_NOATOM
       __hip_atomic_fetch_add(dw2 + (kd * H + head) * 512 + oi, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
-      if (v == 12345.f) dw2[0] = v;  // timing experiment only: keeps the sums live
-#endif
     }
   } else {
   // dK / dV of the wave's key tiles, transposed through LDS into row-major 16-B pieces (as the dK/dV
@@ -1929,15 +1650,12 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_fused32(AttnBatch batch, int 
 // dK/dV pass at 3 waves per SIMD, bit 3: the slice-streamed hs-64 forward, bit 5: the one-pass hs-64
 // backward at T <= 512 with one KV stream, bit 6: the one-pass hs-32 backward at T <= 256, bit 7: that
 // kernel also for several KV streams): MMT_ATTN_RING, or mmt_attn_set_ring() for in-process A/B
-static int g_attn_ring = [] {
-  const char* e = getenv("MMT_ATTN_RING");
-  // both hs-64 passes on the rings (dQ: two query tiles per wave), dK/dV at 3 waves per SIMD
-  // (standalone backward: target 277 -> 273 us, C3 cross-attention 2461 -> 2298, C4 2237 -> 2116;
-  // C3 step -1.5 %: profiles/r3u_ring_ab.txt), and the forward on the ring too (round 4: target
-  // 20.42 -> 20.34 ms, C3 157.3 -> 153.8 ms same box, profiles/r4m_ab.txt)
-  // bit 6 (round 6): the one-pass hs-32 backward
-  return e ? atoi(e) : 15 | 64;
-}();
+// default: both hs-64 passes on the rings (dQ: two query tiles per wave), dK/dV at 3 waves per SIMD
+// (standalone backward: target 277 -> 273 us, C3 cross-attention 2461 -> 2298, C4 2237 -> 2116;
+// C3 step -1.5 %: profiles/r3u_ring_ab.txt), and the forward on the ring too (round 4: target
+// 20.42 -> 20.34 ms, C3 157.3 -> 153.8 ms same box, profiles/r4m_ab.txt)
+// bit 6 (round 6): the one-pass hs-32 backward
+static int g_attn_ring = mmt_env_int("MMT_ATTN_RING", 15 | 64);
 extern "C" int mmt_attn_set_ring(int v) {
   const int old = g_attn_ring;
   g_attn_ring = v;
@@ -2233,10 +1951,7 @@ hipError_t mmt_launch_attn_mask(const AttnBatch& b, int B, int T, int H, hipStre
   const int64_t nt = (T + 31) / 32;
   const int64_t tiles = (int64_t)B * H * (nt * (nt + 1) / 2) * ns;
   // tiles per wave (MMT_MASK_G or mmt_attn_set_mask_g: 1, 2, 4, 8 or 16)
-  static const int g_env = [] {
-    const char* e = getenv("MMT_MASK_G");
-    return e ? atoi(e) : 0;
-  }();
+  static const int g_env = mmt_env_int("MMT_MASK_G", 0);
   // (16 against 8 at T = 1024 / 4096: C3 140.3-140.4 -> 139.3-140.0 ms, C4 319.4-319.5 -> 317.6-318.7; at C1
   // (T = 256) equal within noise, so 8 below T = 1024: profiles/r6aq_mask_g16_ab.txt)
   const int g_def = T >= 1024 ? 16 : 8;

@@ -20,6 +20,12 @@ typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 #define MMT_WAVE 64
 #define MMT_MAX_GROUP 8
 
+// integer environment knob (host): atoi of the variable when it is set, dflt otherwise
+inline int mmt_env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
+
 __device__ __forceinline__ float bf2f(bf16_t x) { return __uint_as_float(((uint32_t)x) << 16); }
 __device__ __forceinline__ bf16_t f2bf(float f) {
   __bf16 b = (__bf16)f;  // v_cvt_pk_bf16_f32 (RNE, NaN-preserving) on gfx950

@@ -215,13 +215,10 @@ int64_t mmt_ln_bwd_det_floats(int count, int R, int C) { return (int64_t)count *
 hipError_t mmt_launch_ln_bwd(const LnBatch& b0, int R, int C, hipStream_t s) {
   if (C % 4 != 0 || C > 1024 || b0.count == 0) return C % 4 ? hipErrorInvalidValue : hipSuccess;
   // 4 rows per block per pass; the grid is capped so the dgamma/dbeta atomics stay few
-  static const int cap = [] {
-    // blocks per problem: every block adds its dgamma/dbeta(/dsum) partials with one atomic per
-    // column, so the cap bounds the same-address atomic chain (C1, 4 problems: 4096 blocks 228 us,
-    // 1024 75 us, 512 52 us, 256 45 us = 5.2 TB/s)
-    const char* e = getenv("MMT_LNB_CAP");
-    return e ? atoi(e) : 256;
-  }();
+  // blocks per problem: every block adds its dgamma/dbeta(/dsum) partials with one atomic per
+  // column, so the cap bounds the same-address atomic chain (C1, 4 problems: 4096 blocks 228 us,
+  // 1024 75 us, 512 52 us, 256 45 us = 5.2 TB/s)
+  static const int cap = mmt_env_int("MMT_LNB_CAP", 256);
   int blocks = (R + 3) / 4;
   if (blocks > cap) blocks = cap;
   LnBatch b = b0;
@@ -647,10 +644,7 @@ __global__ __launch_bounds__(256) void emb_det_sum_kernel(EmbBatch batch, int R,
 
 // the sorted path applies when every problem has int scratch for the permutation and a vocabulary
 // the histogram holds (MMT_EMB_SORT=0: the LDS-slab kernels, A/B)
-static int g_emb_sort = [] {
-  const char* e = getenv("MMT_EMB_SORT");
-  return e ? atoi(e) : 1;
-}();
+static int g_emb_sort = mmt_env_int("MMT_EMB_SORT", 1);
 extern "C" int mmt_emb_set_sort(int on) {
   const int old = g_emb_sort;
   g_emb_sort = on;

@@ -116,10 +116,7 @@ struct Plan {
 // per context: the bit rows are allocated only then); off by default: on the final round-5 build the
 // bf16 aux measured faster (same box, profiles/r5am_relu_bits_final_ab.txt: C1 8.502 -> 8.477 ms,
 // target 19.770 -> 19.505 ms), where the first version had been 0.1-0.7 % faster than the aux
-static int g_relu_bits = [] {
-  const char* e = getenv("MMT_RELU_BITS");
-  return e ? atoi(e) : 0;
-}();
+static int g_relu_bits = mmt_env_int("MMT_RELU_BITS", 0);
 extern "C" int mmt_set_relu_bits(int on) {
   const int old = g_relu_bits;
   g_relu_bits = on;
@@ -128,10 +125,7 @@ extern "C" int mmt_set_relu_bits(int on) {
 // the FFN backward's dropout-masked bf16 residual-gradient copy (+ FFN output-bias gradient) in the
 // epilogue of the last cross-attention K/V dX launch into that gradient (1, default, env
 // MMT_DROP_COPY_FUSE) or a separate drop_copy pass (0)
-static int g_drop_copy_fuse = [] {
-  const char* e = getenv("MMT_DROP_COPY_FUSE");
-  return e ? atoi(e) : 1;
-}();
+static int g_drop_copy_fuse = mmt_env_int("MMT_DROP_COPY_FUSE", 1);
 extern "C" int mmt_set_drop_copy_fuse(int on) {
   const int old = g_drop_copy_fuse;
   g_drop_copy_fuse = on;
@@ -140,10 +134,7 @@ extern "C" int mmt_set_drop_copy_fuse(int on) {
 
 // hs 32: the Q/K/V stage-2 backward in the one-pass attention backward's epilogue (1, default, env
 // MMT_ATTN_QKV2) or the separate qkv2 backward over the bf16 dQ / dK / dV (0); read at every step
-static int g_attn_qkv2 = [] {
-  const char* e = getenv("MMT_ATTN_QKV2");
-  return e ? atoi(e) : 1;
-}();
+static int g_attn_qkv2 = mmt_env_int("MMT_ATTN_QKV2", 1);
 extern "C" int mmt_set_attn_qkv2(int on) {
   const int old = g_attn_qkv2;
   g_attn_qkv2 = on;
@@ -776,10 +767,7 @@ struct Runner {
   // the two passes. The fused launch never materialises dy (the fp32 round trip of the two-pass form)
   void gemm_ln_bwd(const GemmBatch& dx, const LnBatch& lb, int R, int C, const char* gname, const char* lname) {
     if (rc != MMT_OK) return;
-    static const bool fuse = [] {
-      const char* e = getenv("MMT_LN_FUSE");
-      return e ? atoi(e) != 0 : true;
-    }();
+    static const bool fuse = mmt_env_int("MMT_LN_FUSE", 1) != 0;
     if (fuse && lb.count == dx.count) {
       GemmBatch f = dx;
       for (int g = 0; g < f.count; ++g) {
@@ -822,14 +810,8 @@ struct Runner {
     // operands read transposed cannot hide what the two 2-3 blocks-per-CU GEMMs overlap, profiles/r5h_*),
     // but in the C1 step beside the side stream it wins: 7.975 / 7.982 -> 7.949 / 7.960 ms (round 6,
     // profiles/r6x_c1_env_ab.txt); at C = 512 it stays two GEMMs
-    static const bool on = [] {
-      const char* e = getenv("MMT_MLP2");
-      return e ? atoi(e) != 0 : true;
-    }();
-    static const int bwd_mode = [] {
-      const char* e = getenv("MMT_MLP2_BWD");
-      return e ? atoi(e) : 2;
-    }();
+    static const bool on = mmt_env_int("MMT_MLP2", 1) != 0;
+    static const int bwd_mode = mmt_env_int("MMT_MLP2_BWD", 2);
     const bool on_bwd = bwd_mode == 1 || (bwd_mode == 2 && n >= 1 && g1s[0].N == 128);
     if (rc != MMT_OK || !on || (bwd && !on_bwd) || n < 1) return false;
     Mlp2Batch chunk[(MMT_MAX_GROUP + MMT_MLP2_GROUP - 1) / MMT_MLP2_GROUP] = {};
@@ -999,18 +981,12 @@ int run_forward(mmt_ctx* c, Runner& r, const int64_t* const* idx, const int64_t*
   // where the later layers' pile beside layer 0 grows past what one layer's GEMMs hide: C4 (24 layers) 312.4 ->
   // 308.6 ms, C3 (12) 141.1 -> 140.5-140.9, target (6) 19.07 -> 19.04, C1 (6) 7.87 -> 7.90
   // (profiles/r6ab_mask_ab.txt, r6ae_c4_mask_ab.txt); MMT_MASK_AHEAD=0 / 1 forces it
-  static const int mask_ahead_env = [] {
-    const char* e = getenv("MMT_MASK_AHEAD");
-    return e ? atoi(e) : -1;
-  }();
+  static const int mask_ahead_env = mmt_env_int("MMT_MASK_AHEAD", -1);
   // (2: layer l + 1's bits forked after layer l's self-attention forward, so they overlap that layer's
   // GEMMs, which take the tile hint until the next join, rather than its attention)
   const int ahead_mode = mask_ahead_env >= 0 ? mask_ahead_env : (c->L >= 12 ? 1 : 0);
   const bool mask_ahead = ahead_mode != 0;
-  static const int mask_t2 = [] {
-    const char* e = getenv("MMT_MASK_T2");
-    return e ? atoi(e) : 1;
-  }();
+  static const int mask_t2 = mmt_env_int("MMT_MASK_T2", 1);
   auto gen_masks = [&](int ll) {
     if (ll <= 1 || mask_ahead) ss = r.side();  // layer 0: one fork; layers 1..L-1: one fork for all
     const LM* xl = &c->lm[(size_t)ll * M];
@@ -1068,11 +1044,7 @@ int run_forward(mmt_ctx* c, Runner& r, const int64_t* const* idx, const int64_t*
   // LayerNorm forwards already done by the previous residual GEMM's epilogue (lnf_fused: the post
   // block's); fused only in bf16 at C == 256 (whole rows per 256x256 tile), MMT_LN_FUSE=0 or
   // MMT_LN_FUSE_FWD=0 disables
-  static const int ln_fuse = [] {
-    const char* e = getenv("MMT_LN_FUSE");
-    const char* f = getenv("MMT_LN_FUSE_FWD");
-    return (e ? atoi(e) != 0 : true) ? (f ? atoi(f) : 1) : 0;
-  }();
+  static const int ln_fuse = mmt_env_int("MMT_LN_FUSE", 1) != 0 ? mmt_env_int("MMT_LN_FUSE_FWD", 1) : 0;
   // C = 512 (128 x 512 tile) only with MMT_LN_FUSE_FWD=2: measured slower on the 2-stage ring
   // (target 20.09 -> 20.43 ms, profiles/r3u_ab.txt)
   const bool fuse_fwd = ln_fuse && !f8 && (C == 256 || (C == 512 && ln_fuse == 2));
@@ -1097,10 +1069,7 @@ int run_forward(mmt_ctx* c, Runner& r, const int64_t* const* idx, const int64_t*
     GemmBatch g{}; g.count = M;
     // per-head stage 2 (model.py:39, 44, 49) fused into the stage-1 GEMM's epilogue at hs 32 / 64
     // (qkv2_fused), else its own launch; MMT_QKV2_FUSE=0 keeps the separate kernel
-    static const bool qkv2_fuse = [] {
-      const char* e = getenv("MMT_QKV2_FUSE");
-      return e ? atoi(e) != 0 : true;
-    }();
+    static const bool qkv2_fuse = mmt_env_int("MMT_QKV2_FUSE", 1) != 0;
     for (int i = 0; i < M; ++i) {
       g.p[i] = f8 ? gp_f8(r.W<uint8_t>(a[i].a8), C, r.W<uint8_t>(a[i].as8), ldsC, w8, x[i].W1, R)
                   : gp_fwd(r.W<bf16_t>(a[i].a), C, wpk, x[i].W1, R);
@@ -1153,10 +1122,7 @@ int run_forward(mmt_ctx* c, Runner& r, const int64_t* const* idx, const int64_t*
     }
     // ln2 in the fused out-projection's epilogue (MMT_LN2_FUSE=0: the separate ln_fwd pass; fp8 keeps
     // it, the pass also writes the MX-fp8 copy)
-    static const bool ln2_env = [] {
-      const char* e = getenv("MMT_LN2_FUSE");
-      return e ? atoi(e) != 0 : true;
-    }();
+    static const bool ln2_env = mmt_env_int("MMT_LN2_FUSE", 1) != 0;
     const bool ln2_fuse = ln2_env && !f8;
     bool ln2_done = false;
     {
@@ -1782,10 +1748,7 @@ int run_backward_stage(mmt_ctx* c, Runner& r, int stage, const float* loss_grads
   // MMT_DW_ATTN_SMALL=1: the FFN weight gradients (the side-stream launches still running when the
   // self-attention backward starts) on the 128 x 128 tile, whose 64 KiB of LDS leave room on their CUs for
   // one of the attention backward's 80 KiB workgroups
-  static const int dw_attn_small = [] {
-    const char* e = getenv("MMT_DW_ATTN_SMALL");
-    return e ? atoi(e) : 0;
-  }();
+  static const int dw_attn_small = mmt_env_int("MMT_DW_ATTN_SMALL", 0);
   const int ffn_dw_hint = dw_attn_small ? 2 : 0;
   r.dwgemm(dw, "ffn2_dw", ffn_dw_hint);
   r.gemm(dx, true, false, EPI_DRELU_BF16, 1, "ffn2_dx");
@@ -1944,10 +1907,7 @@ int ensure_device_tables(mmt_ctx* c) {
 // the side stream (weight-gradient GEMMs in the backward, dropout keep bits in the forward), made
 // lazily on the caller's current device; MMT_SIDE_STREAM=0 runs everything on the caller's stream
 void ensure_side(mmt_ctx* c) {
-  static const bool use_side = [] {
-    const char* e = getenv("MMT_SIDE_STREAM");
-    return !e || atoi(e) != 0;
-  }();
+  static const bool use_side = mmt_env_int("MMT_SIDE_STREAM", 1) != 0;
   int dev = -1;
   if (!use_side || hipGetDevice(&dev) != hipSuccess || (c->side && c->side_device == dev)) return;
   if (c->side) (void)hipStreamDestroy(c->side);
@@ -2167,10 +2127,7 @@ int mmt_backward_stage(mmt_ctx* c, void* stream, int32_t stage, const float* los
     r.ok(hipStreamWaitEvent(r.s, c->stage_ev[stage & 1], 0), "stream wait");
   // MMT_FLUSH_HOLD=1: one side-stream fork per stage (every stage but the last layer's, whose weight
   // gradients would otherwise only start after its data-gradient chain, at the end of the step)
-  static const int flush_hold = [] {
-    const char* e = getenv("MMT_FLUSH_HOLD");
-    return e ? atoi(e) : 0;
-  }();
+  static const int flush_hold = mmt_env_int("MMT_FLUSH_HOLD", 0);
   r.hold = defer && flush_hold && stage < c->L;
   const int rc = run_backward_stage(c, r, stage, loss_grads, grads);
   r.hold = false;
@@ -2269,10 +2226,7 @@ extern "C" int mmt_probe_set(mmt_ctx* c, const char* label) {
   }
   // event pairs for the recorded launches, made here (event creation is a host call of tens of
   // microseconds: inside the timed loop it starved the GPU); recording stops when they run out
-  static const size_t pool = [] {
-    const char* e = getenv("MMT_PROBE_EVENTS");
-    return (size_t)(e ? atoi(e) : 4096);
-  }();
+  static const size_t pool = (size_t)mmt_env_int("MMT_PROBE_EVENTS", 4096);
   while (!c->probe_pats.empty() && c->probe_pool.size() < pool) {
     hipEvent_t a, b;
     if (hipEventCreate(&a) != hipSuccess) break;

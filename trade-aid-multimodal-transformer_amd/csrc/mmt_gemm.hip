@@ -565,10 +565,7 @@ static int auto_splits(const GemmBatch& b, int splits) {
   max_tiles<TL>(b, &tiles);
   for (int g = 0; g < b.count; ++g) maxk = b.p[g].K > maxk ? b.p[g].K : maxk;
   if (tiles <= 0) return 1;
-  static const int env_target = [] {
-    const char* e = getenv("MMT_WGRAD_BLOCKS");  // tuning knob: blocks per weight-gradient launch
-    return e ? atoi(e) : 0;
-  }();
+  static const int env_target = mmt_env_int("MMT_WGRAD_BLOCKS", 0);  // tuning knob: blocks per weight-gradient launch
   // ~128 blocks: the weight gradients run on the side stream next to the data-gradient chain, so
   // half the chip for longer beats the whole chip with twice the split-K slab traffic (measured at
   // C1: 128 -> 9.97-10.28 ms/step, 256 -> 10.21-10.50, 64 -> 10.6)
@@ -590,10 +587,7 @@ static int auto_splits(const GemmBatch& b, int splits) {
 // deeper ring keeps three in flight; C1 *_dw family 3.44 -> 3.20 ms/step live, C3 73.8 -> 69.4),
 // BK 64 x 2 for the rest (the forward / data-gradient 256 x 256 launches measured 0.3-0.9 % slower
 // at BK 32 x 4 in C3 / C4: profiles/r4z_big_variant_ab.txt). MMT_GEMM_BIG_VARIANT sets all of them.
-static int g_big_variant = [] {
-  const char* e = getenv("MMT_GEMM_BIG_VARIANT");
-  return e ? atoi(e) : -1;
-}();
+static int g_big_variant = mmt_env_int("MMT_GEMM_BIG_VARIANT", -1);
 
 // default 128 x 128 pipelines (build-time, tools/build_variant.py A/B): bf16-output epilogues at 3
 // blocks per CU (variant 6: BK 32 x 2), the others at 2 (variant 0: BK 64 x 2). Deeper rings lose
@@ -620,20 +614,14 @@ static bool gemm8_ln_on();
 static bool gemm8_on() {
   // default on (round 5): C4 355 -> 350 ms/step, C3 153.3 -> 152.4, target / C1 neutral (same-box A/B,
   // profiles/r5_gemm8_mlp2_ab.txt); MMT_GEMM8=0 restores the 2-stage 256 x 256 ring everywhere
-  static const int env = [] {
-    const char* e = getenv("MMT_GEMM8");
-    return e ? atoi(e) : 1;
-  }();
+  static const int env = mmt_env_int("MMT_GEMM8", 1);
   return g_gemm8_rt >= 0 ? g_gemm8_rt != 0 : env != 0;
 }
 
 // the row-wide (N = 256) LayerNorm-fused launches on the ping-pong kernel: MMT_GEMM8_LN=0 keeps them on the
 // 2-stage ring (variant bit 17 / 18 still force the ping-pong kernel on / off for the tests)
 static bool gemm8_ln_on() {
-  static const bool env = [] {
-    const char* e = getenv("MMT_GEMM8_LN");
-    return e ? atoi(e) != 0 : true;
-  }();
+  static const bool env = mmt_env_int("MMT_GEMM8_LN", 1) != 0;
   if (g_gemm8_rt >= 0) return g_gemm8_rt == 1;
   return gemm8_on() && env;
 }
@@ -641,19 +629,13 @@ static bool gemm8_ln_on() {
 // K threshold 1024 (round 2 c): at K = 512 (d512 forward GEMMs and data gradients) the 128x128 tile at
 // 2-3 blocks per CU overlaps one block's epilogue with the others' K loops and shares the chip with
 // the side stream better than the single 256x256 block per CU (target step 23.13 -> 22.73 ms)
-static int g_big_kmin = [] {
-  const char* e = getenv("MMT_GEMM_BIG_KMIN");
-  return e ? atoi(e) : 1024;
-}();
+static int g_big_kmin = mmt_env_int("MMT_GEMM_BIG_KMIN", 1024);
 // MMT_GEMM_T2=1: the big launches with K below the 256 x 256 tile's threshold (K = 512: the d512 FFN and
 // cross-attention K/V products the ping-pong kernel takes by default) on a 128 x 256 tile of 4 waves (TileL's
 // per-wave 128 x 64) at two workgroups per CU (BK 32 x 3 stages: 72 KiB each), so one workgroup's prologue /
 // epilogue overlaps the other's K loop
 using TileM = TileCfg<1, 4, 4, 2>;
-static int g_gemm_t2 = [] {
-  const char* e = getenv("MMT_GEMM_T2");
-  return e ? atoi(e) : 0;
-}();
+static int g_gemm_t2 = mmt_env_int("MMT_GEMM_T2", 0);
 extern "C" int mmt_gemm_set_t2(int v) {
   const int old = g_gemm_t2;
   g_gemm_t2 = v;
@@ -684,10 +666,7 @@ static hipError_t launch_t(const GemmBatch& b, int splits, bool big, hipStream_t
     // main stream's attention backward the step measured slower (C1 attention backward 198 -> 207 us live,
     // the *_dw family 107 -> 113 us; profiles/r5_gemm8_mlp2_ab.txt)
     if constexpr (SWAP && gemm8_supports(A_KC, B_KC, EPI)) {
-      static const bool dw8 = [] {
-        const char* e = getenv("MMT_GEMM8_DW");
-        return e ? atoi(e) != 0 : false;
-      }();
+      static const bool dw8 = mmt_env_int("MMT_GEMM8_DW", 0) != 0;
       // (mmt_gemm_set_variant bit 17 forces it everywhere: the kernel tests)
       if (gemm8_on() && (A_KC || dw8 || g_gemm8_rt == 1)) return mmt_launch_gemm8(b, EPI, A_KC, B_KC, grid, s);
     }
@@ -714,10 +693,8 @@ static hipError_t launch_t(const GemmBatch& b, int splits, bool big, hipStream_t
   // or residual operand or store fp32 measured faster at 2 blocks per CU with the 64-deep ring
   // (profiles/r2_gemm_bench.txt)
   constexpr bool occ3 = EPI == EPI_STORE_BF16 || EPI == EPI_BIAS_TANH_BF16 || EPI == EPI_BIAS_RELU_BF16;
-  static const int env_dw = [] {  // tuning knob: pipeline variant of the 128x128 weight-gradient GEMMs
-    const char* e = getenv("MMT_GEMM_DW_VARIANT");
-    return e ? atoi(e) : -1;
-  }();
+  // tuning knob: pipeline variant of the 128x128 weight-gradient GEMMs
+  static const int env_dw = mmt_env_int("MMT_GEMM_DW_VARIANT", -1);
   // (a 256 x 128 tile at two blocks per CU won standalone on the target ffn0, 214 -> 194 us, but not in
   // the step beside the side stream, 20.21 -> 20.37 ms: profiles/r3y_tilem_ab.txt; removed in round 4)
   // (the ReLU' epilogue reading bits has no 16-B aux operand left, but at 3 blocks per CU it measured
@@ -740,23 +717,14 @@ static hipError_t launch_t(const GemmBatch& b, int splits, bool big, hipStream_t
 // tile policy: the 256x256 tile where every problem of the launch fills it (M, N >= 256) and the
 // K loop is long enough to amortise its prologue/epilogue (K >= g_big_kmin; weight gradients
 // always qualify: K = B*T). MMT_GEMM_BIG=0 disables it, MMT_GEMM_BIG_KMIN sets the K threshold.
-static int g_big_mode = [] {
-  const char* e = getenv("MMT_GEMM_BIG");
-  return e ? atoi(e) : 1;
-}();
+static int g_big_mode = mmt_env_int("MMT_GEMM_BIG", 1);
 
 // K threshold of the ping-pong 256 x 256 kernel for launches with many tiles: at K = 512 it wins where
 // the launch has >= 4 tiles per CU (the target's ffn0 and ffn2 dX: 221 -> 177 and 252 -> 230 us
 // standalone; smaller launches leave CUs idle or lose the 128 x 128 tile's 2-3 blocks per CU beside the
 // side stream: every K = 512 launch on it measured +1 % on the target step)
-static int g_gemm8_kmin = [] {
-  const char* e = getenv("MMT_GEMM8_KMIN");
-  return e ? atoi(e) : 512;
-}();
-static int g_gemm8_min_tiles = [] {
-  const char* e = getenv("MMT_GEMM8_MIN_TILES");
-  return e ? atoi(e) : 1024;
-}();
+static int g_gemm8_kmin = mmt_env_int("MMT_GEMM8_KMIN", 512);
+static int g_gemm8_min_tiles = mmt_env_int("MMT_GEMM8_MIN_TILES", 1024);
 static bool use_big(const GemmBatch& b) {
   if (!g_big_mode || b.count == 0) return false;
   bool big = true, qkv2 = false;
@@ -953,10 +921,7 @@ __global__ __launch_bounds__(256) void slab_reduce_kernel(SlabBatch b) {
 
 // MMT_DW_SMALL=1: every weight gradient on the 128 x 128 tile (4x the tiles of the 256 x 256 one, so a
 // quarter of the K splits and of the split-K slab traffic at the ~128-block side-stream target)
-static const int g_dw_small = [] {
-  const char* e = getenv("MMT_DW_SMALL");
-  return e ? atoi(e) : 0;
-}();
+static const int g_dw_small = mmt_env_int("MMT_DW_SMALL", 0);
 // (GemmBatch::tile_hint 2: this launch on the 128 x 128 tile, 64 KiB of LDS, which fits on a CU beside the
 // main stream's 80 KiB attention-backward workgroups where the 256 x 256 one's 128 KiB does not)
 static bool use_big_dw(const GemmBatch& b) { return !g_dw_small && b.tile_hint != 2 && use_big(b); }
@@ -979,10 +944,7 @@ hipError_t mmt_launch_gemm_wgrad(const GemmBatch& b, float* slab, int64_t slab_b
     splits = 1;
   }
   // XCD-major remap of the (tile, split, problem) grid (MMT_DW_XCD_PLANE=0 turns it off)
-  static const int xcd_plane = [] {
-    const char* e = getenv("MMT_DW_XCD_PLANE");
-    return e ? atoi(e) : 1;
-  }();
+  static const int xcd_plane = mmt_env_int("MMT_DW_XCD_PLANE", 1);
   if (splits <= 1) {  // one K pass: accumulate straight into the gradient
     GemmBatch d = b;
     d.xcd_plane = xcd_plane;

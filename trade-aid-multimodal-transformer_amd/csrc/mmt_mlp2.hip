@@ -562,10 +562,7 @@ bool mmt_mlp2_ok(const Mlp2Batch& b) {
 // rows per forward workgroup at C = 256 (N1 128): 128 (8 waves, 80 KiB LDS, 163 VGPRs: one workgroup per
 // CU) or 64 (4 waves, 52 KiB: three per CU, so one's epilogue stores overlap the others' MFMAs);
 // MMT_MLP2_BM, or mmt_mlp2_set_bm() for in-process A/B
-static int g_mlp2_bm = [] {
-  const char* e = getenv("MMT_MLP2_BM");
-  return e ? atoi(e) : 128;
-}();
+static int g_mlp2_bm = mmt_env_int("MMT_MLP2_BM", 128);
 extern "C" int mmt_mlp2_set_bm(int bm) {
   const int old = g_mlp2_bm;
   g_mlp2_bm = bm;

@@ -520,10 +520,8 @@ __global__ __launch_bounds__(256, MMT_QKV2B_OCC) void qkv2_bwd_v2(Qkv2Batch batc
   }
 }
 
-static int g_qkv2_coal = [] {
-  const char* e = getenv("MMT_QKV2_COAL");
-  return e ? atoi(e) : 2;  // bit 0: hs 32, bit 1: hs 64 (hs 32: C1 +0.13 %, hs 64: target -0.25 %, r5y)
-}();
+// bit 0: hs 32, bit 1: hs 64 (hs 32: C1 +0.13 %, hs 64: target -0.25 %, r5y)
+static int g_qkv2_coal = mmt_env_int("MMT_QKV2_COAL", 2);
 extern "C" int mmt_qkv2_set_coal(int on) {
   const int old = g_qkv2_coal;
   g_qkv2_coal = on;
