@@ -128,6 +128,61 @@ int mmt_backward_stage(mmt_ctx* ctx, void* stream, int32_t stage, const float* l
 int mmt_adamw_step(mmt_ctx* ctx, void* stream, float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
                    int64_t n, int64_t step, float lr, float beta1, float beta2, float eps, float weight_decay);
 
+/* ---- guarded optimizer step: gradient clipping, non-finite skip and the step count on the device ----
+ * One step of an optimizer over several flat tensors, with no device-to-host copy or sync anywhere:
+ *     mmt_grad_sqsum (add = 0) on the first gradient, mmt_grad_sqsum (add = 1) on every other one,
+ *     mmt_guard_finalize once, mmt_adamw_step_guarded on every (params, grads, moments) tuple,
+ * all on one stream. The guard state is mmt_guard_state_bytes bytes of device memory, 16-byte aligned,
+ * allocated once per optimizer and zeroed by the caller before its first step; struct mmt_guard_header
+ * sits at offset 0, MMT_GUARD_SLOTS fp64 block partials follow it. The sum of squares is taken in fp64
+ * in a fixed order (fixed grid, fixed trees, no float atomics): the norm is bit-identical run to run in
+ * both training modes, agrees with the exact value to below one fp32 ulp whatever n is, and a finite
+ * fp32 gradient never overflows it. */
+#define MMT_GUARD_SLOTS 1024
+struct mmt_guard_header {
+  float norm;              /* global L2 norm of this step's gradients, (float)sqrt(fp64 sum of squares) */
+  float coef;              /* the factor the step applies to every gradient element (1 without clipping) */
+  int32_t ok;              /* 1: the guarded steps of this optimizer step apply; 0: they return untouched */
+  int32_t reserved0;
+  int64_t applied_steps;   /* steps applied so far: the t of the bias corrections (torch's state["step"]) */
+  int64_t skipped_steps;   /* steps skipped for a non-finite norm */
+  int64_t clipped_steps;   /* applied steps with coef < 1 */
+  float bias_correction1;      /* 1 - beta1^t            (fp64, rounded to fp32 once, as mmt_adamw_step) */
+  float bias_correction2_sqrt; /* sqrt(1 - beta2^t)      (likewise) */
+  int32_t reserved1[4];
+};
+int64_t mmt_guard_state_bytes(void);
+/* Per-block sums of squares of grads[0 .. n) into the guard state's slots: add == 0 overwrites every slot
+ * (the first tensor of a step), add != 0 adds slot-wise (stream order fixes the order of those adds).
+ * grads must be 16-byte aligned; n >= 0. */
+int mmt_grad_sqsum(void* stream, const float* grads, int64_t n, int32_t add, void* guard);
+/* One workgroup: norm = (float)sqrt(sum of the slots in index order), and
+ *     coef = min(1, max_norm / (norm + 1e-6))          (torch.nn.utils.clip_grad_norm_, in fp32)
+ * or coef = 1 when max_norm <= 0 or max_norm == +inf (no clipping). A NaN norm gives a NaN coef, as in torch.
+ * skip_nonfinite != 0 and a non-finite sum (a NaN or an infinity anywhere in the gradients): ok = 0,
+ * skipped_steps += 1, applied_steps and the bias corrections stay as they are, so the skipped step does
+ * not advance the bias correction and the host need not know that it was skipped. Otherwise ok = 1,
+ * applied_steps += 1 (clipped_steps += 1 when coef < 1) and the bias corrections of t = applied_steps are
+ * computed on the device. */
+int mmt_guard_finalize(void* stream, float max_norm, int32_t skip_nonfinite, float beta1, float beta2, void* guard);
+/* mmt_adamw_step on grads * coef with the bias corrections read from the guard header; returns without
+ * reading or writing params / exp_avg / exp_avg_sq when the header's ok is 0. With coef == 1 it computes
+ * exactly what mmt_adamw_step computes at step = applied_steps. */
+int mmt_adamw_step_guarded(mmt_ctx* ctx, void* stream, float* params, const float* grads, float* exp_avg,
+                           float* exp_avg_sq, int64_t n, float lr, float beta1, float beta2, float eps,
+                           float weight_decay, const void* guard);
+/* The three calls above return MMT_ERR_INVALID before any launch for a null guard, n < 0, or a tensor or
+ * guard pointer that is not 16-byte aligned. */
+
+/* In-place gradient accumulation: with on != 0, stage 0 of mmt_backward / mmt_backward_stage does not zero
+ * `grads`, so the backward adds its gradient to what the buffer holds (every writer into `grads` adds:
+ * float atomics, the ordered sums, the split-K slab reduce and the one-pass weight-gradient epilogue all
+ * read-modify-write). The caller zeroes or overwrites the buffer before the first micro-batch (or runs that
+ * one with the switch off). Per context, off by default, read at stage 0: one backward runs under one
+ * setting. In deterministic mode the accumulated gradient is still bit-identical run to run. */
+int mmt_set_grad_accumulate(mmt_ctx* ctx, int32_t on);
+int32_t mmt_get_grad_accumulate(const mmt_ctx* ctx);
+
 /* directional metric for one numeric modality: logits fp32 [batch, T, V]; xb/yb int64 [batch, T];
  * vocab fp64 [V]; accumulates wins_losses[0..1] (int32) and certainty_sum (fp64) on device */
 int mmt_eval_direction(mmt_ctx* ctx, void* stream, int32_t batch, int32_t T, int32_t V, const float* logits,

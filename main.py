@@ -19,6 +19,7 @@ Inside a reference checkout the reference's own main.py can instead import this 
 training_utils and AdamW directly and keep its ingest unchanged.
 """
 import argparse
+import contextlib
 import json
 import os
 import sys
@@ -80,9 +81,23 @@ def run(cfg, data, log=print):
     log(f"  Parameters: {nparam / 1e6:.1f}M")
     log("")
 
+    # build-only keys: guarded optimizer step and in-place gradient accumulation (all off by default: the
+    # loop below is then the reference's line for line)
+    grad_clip = config_utils._get_grad_clip()
+    accum = config_utils._get_grad_accum_steps()
+    skip_nonfinite = config_utils._get_skip_nonfinite_steps()
+    guarded = grad_clip is not None or accum > 1 or skip_nonfinite
+
+    def make_optimizer(mm):
+        if not guarded:
+            return mmt_optim.AdamW(mm.parameters(), lr=cfg["learning_rate"])
+        # accumulation alone still reports the gradient norm: an infinite bound never clips
+        return mmt_optim.AdamW(mm.parameters(), lr=cfg["learning_rate"], skip_nonfinite=skip_nonfinite,
+                               max_grad_norm=grad_clip if grad_clip is not None else float("inf"))
+
     def fresh():
         mm = MultimodalTransformer(M, V, params).to(device)
-        return mm, mmt_optim.AdamW(mm.parameters(), lr=cfg["learning_rate"])
+        return mm, make_optimizer(mm)
 
     if cfg["create_new_model"] == 1:
         log("Model: Creating new transformer...")
@@ -94,7 +109,7 @@ def run(cfg, data, log=print):
         try:
             m.load_state_dict(torch.load(model_file_name, weights_only=True, map_location="cpu"))
             log("Model: Loaded successfully")
-            optimizer = mmt_optim.AdamW(m.parameters(), lr=cfg["learning_rate"])
+            optimizer = make_optimizer(m)
             log("Optimizer: Created with loaded parameters")
         except FileNotFoundError:
             log("Model: File not found, creating new model instead")
@@ -125,6 +140,8 @@ def run(cfg, data, log=print):
     log("  - Note: ** Intensive computation ahead **")
     log("")
     best_val, patience, no_improve = float("inf"), 1000, 0
+    m.set_grad_accumulation(accum > 1)
+    seen_clipped = seen_skipped = 0  # the guarded optimizer's counts at the previous evaluation
     history = []
     for it in range(max_iters):
         if it % 100 == 0:
@@ -139,16 +156,23 @@ def run(cfg, data, log=print):
                          if bad >> i & 1]
                 log(f"Warning: non-finite loss since the last evaluation in: {', '.join(names)} | {now}")
             history.append((it, losses["train"], losses["val"]))
+            guard_note = ""
+            if guarded:  # the loop syncs here anyway
+                _, skipped, clipped = optimizer.counters()
+                norm = optimizer.last_grad_norm
+                guard_note = (f"| GradNorm: {'n/a' if norm is None else format(float(norm), '.4f')} "
+                              f"| Clipped: {clipped - seen_clipped} | Skipped: {skipped - seen_skipped} ")
+                seen_clipped, seen_skipped = clipped, skipped  # both lines below carry the note
             if not (np.isnan(losses["train"]) or np.isnan(losses["val"])):
                 log(f"\nLOSS METRICS: Step {it}/{max_iters} | Train: {losses['train']:.4f} | Val: {losses['val']:.4f} "
-                    f"| Time: {now}")
+                    f"{guard_note}| Time: {now}")
                 log("-" * 80)
                 if out_name != "":
                     with open(out_path, "a", encoding="utf-8") as f:
                         f.write(f"\nSTEP {it:,}/{max_iters:,} ({it / max_iters * 100:.1f}% Complete) | Training Loss: "
                                 f"{losses['train']:.6f} | Validation Loss: {losses['val']:.6f} | {now}\n\n")
             else:
-                log(f"Warning: Step {it} losses are NaN, skipping save | {now}")
+                log(f"Warning: Step {it} losses are NaN, skipping save {guard_note}| {now}")
             if not np.isnan(losses["val"]):
                 if losses["val"] < best_val:
                     best_val, no_improve = losses["val"], 0
@@ -164,6 +188,23 @@ def run(cfg, data, log=print):
             log(f"Saved: Model checkpoint ({round(os.path.getsize(model_file_name) / 1024 ** 2, 2)} MB) | "
                 f"{datetime.now().strftime('%H:%M:%S')}")
             log("")
+        if guarded:
+            # grad_accum_steps micro-batches (each its own get_batch, forward and scaled backward, added in
+            # place into flat_params.grad), then one guarded step
+            optimizer.zero_grad(set_to_none=True)
+            for k in range(accum):
+                xb_list, yb_list = get_batch("train", 1)
+                logits_list, losses_list = m(xb_list, yb_list)
+                if not (losses_list and all(l is not None for l in losses_list)):
+                    log("Warning: Training step losses not calculated, skipping backpropagation")
+                    break
+                total_loss = sum(losses_list) if accum == 1 else sum(losses_list) / accum
+                # data parallel: exchange once, at the last micro-batch (no_sync changes nothing otherwise)
+                with (m.no_sync() if k < accum - 1 else contextlib.nullcontext()):
+                    total_loss.backward()
+            else:
+                optimizer.step()
+            continue
         xb_list, yb_list = get_batch("train", 1)
         logits_list, losses_list = m(xb_list, yb_list)
         if losses_list and all(l is not None for l in losses_list):

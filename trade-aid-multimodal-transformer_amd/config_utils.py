@@ -14,7 +14,10 @@ _DEFAULTS = {
                          "model_file_name": "model.pth", "create_new_model": 1, "save_model": 1, "device": "cpu"},
     "data_splitting": {"validation_size": 0.1, "num_validation_files": 0},
     "training_parameters": {"batch_size": 32, "block_size": 64, "max_iters": 5000, "eval_interval": 500,
-                            "eval_iters": 40, "learning_rate": 3e-4},
+                            "eval_iters": 40, "learning_rate": 3e-4,
+                            # build-only keys (the reference ignores unknown keys): the guarded optimizer step
+                            # (mmt_optim.AdamW max_grad_norm / skip_nonfinite) and in-place gradient accumulation
+                            "grad_clip": None, "grad_accum_steps": 1, "skip_nonfinite_steps": False},
     "model_architecture": {"n_embd": 384, "n_head": 6, "n_layer": 6, "dropout": 0.2,
                            "fixed_values": [-0.5, -0.2, -0.1, 0, 0.1, 0.2, 0.5],
                            # build-only key (the reference ignores unknown keys): "bf16" | "fp8"
@@ -114,3 +117,35 @@ def _get_deterministic():
         if t in ("0", "false", "off", "no"):
             return False
     raise ValueError(f"deterministic must be a boolean (0/1, false/true, off/on, no/yes), got {v!r}")
+
+
+def _get_grad_clip():
+    """Build-only knob: the global gradient-norm bound of the guarded optimizer step (torch's
+    clip_grad_norm_ formula, on the device; mmt_optim.AdamW max_grad_norm). A positive float, or None
+    (default, also when the key is absent): no clipping."""
+    v = _get_config().get("grad_clip", None)
+    if v is None:
+        return None
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v or v <= 0:
+        raise ValueError(f"grad_clip must be a positive number or null, got {v!r}")
+    return float(v)
+
+
+def _get_grad_accum_steps():
+    """Build-only knob: micro-batches per optimizer step (in-place gradient accumulation,
+    MultimodalTransformer.set_grad_accumulation). An integer >= 1; default 1 (also when the key is absent)."""
+    v = _get_config().get("grad_accum_steps", 1)
+    if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+        raise ValueError(f"grad_accum_steps must be an integer >= 1, got {v!r}")
+    return v
+
+
+def _get_skip_nonfinite_steps():
+    """Build-only knob: True skips, on the device, an optimizer step whose gradient norm is NaN / Inf
+    (mmt_optim.AdamW skip_nonfinite). Default False (also when the key is absent)."""
+    v = _get_config().get("skip_nonfinite_steps", False)
+    if isinstance(v, bool):
+        return v
+    if isinstance(v, int) and v in (0, 1):
+        return bool(v)
+    raise ValueError(f"skip_nonfinite_steps must be a boolean, got {v!r}")

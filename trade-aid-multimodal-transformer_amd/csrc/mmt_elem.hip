@@ -6,6 +6,7 @@
 
 #include <algorithm>
 
+#include "mmt.h"
 #include "mmt_common.h"
 #include "mmt_kernels.h"
 
@@ -1154,6 +1155,169 @@ hipError_t mmt_launch_adamw(float* p, const float* g, float* m, float* v, int64_
   if (blocks > 4096) blocks = 4096;
   hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)blocks), dim3(256), 0, s, p, g, m, v, n4, n, lr, b1, b2, eps, wd,
                      bc1, bc2_sqrt);
+  return hipGetLastError();
+}
+
+// ============================================================================================
+// Guarded optimizer step (mmt.h: mmt_grad_sqsum / mmt_guard_finalize / mmt_adamw_step_guarded): the global
+// gradient norm, torch's clip_grad_norm_ coefficient, the non-finite skip and the step counter, all on the
+// device. Guard state = mmt_guard_header (64 B) + MMT_GUARD_SLOTS fp64 block partials.
+//   grad_sqsum_kernel     slot[block] (+)= sum of g^2 over the block's elements. The grid is ALWAYS
+//                         MMT_GUARD_SLOTS blocks, so which thread reads which element depends on n alone; the
+//                         sums are fp64 from the per-thread accumulator on (a finite fp32 gradient cannot
+//                         overflow them, and the rounding stays far below an fp32 ulp of the norm); fixed xor
+//                         tree in the wave, the four wave sums through LDS, one plain store per block. No float
+//                         atomic, no workgroup waits for another: bit-identical run to run (the rule of mmt_det.h)
+//   guard_finalize_kernel one workgroup: the slots in index order through the same fixed tree -> norm, coef,
+//                         ok, counters, and the bias corrections of the applied step count
+//   adamw_guarded_kernel  adamw_kernel's body on g * coef, returning at once when ok == 0
+// ============================================================================================
+static_assert(sizeof(mmt_guard_header) == 64, "the slots start at byte 64 of the guard state");
+
+__device__ __forceinline__ double wave_sum_f64(double x) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);  // the same tree in every lane
+  return x;
+}
+// sum over the 256 threads of the block, valid in thread 0
+__device__ __forceinline__ double block_sum_f64(double x, double* sh) {
+  x = wave_sum_f64(x);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = x;
+  __syncthreads();
+  return (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+
+#define GUARD_U 4  // 16-byte loads in flight per thread
+__global__ __launch_bounds__(256) void grad_sqsum_kernel(const float* __restrict__ g, int64_t n4, int64_t n, int add,
+                                                         double* __restrict__ slots) {
+  __shared__ double sh[4];
+  const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  constexpr int64_t stride = (int64_t)MMT_GUARD_SLOTS * 256;
+  double acc[GUARD_U];
+#pragma unroll
+  for (int u = 0; u < GUARD_U; ++u) acc[u] = 0.0;
+  for (int64_t i = gid; i < n4; i += GUARD_U * stride) {
+    f32x4 x[GUARD_U];
+#pragma unroll
+    for (int u = 0; u < GUARD_U; ++u)
+      x[u] = i + u * stride < n4 ? reinterpret_cast<const f32x4*>(g)[i + u * stride] : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int u = 0; u < GUARD_U; ++u) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const double d = (double)x[u][e];
+        acc[u] += d * d;
+      }
+    }
+  }
+  // scalar tail (at most three elements)
+  const int64_t t = n4 * 4 + gid;
+  if (t < n) {
+    const double d = (double)g[t];
+    acc[0] += d * d;
+  }
+  const double s = block_sum_f64((acc[0] + acc[1]) + (acc[2] + acc[3]), sh);
+  if (threadIdx.x == 0) slots[blockIdx.x] = add ? slots[blockIdx.x] + s : s;
+}
+
+__global__ __launch_bounds__(256) void guard_finalize_kernel(mmt_guard_header* __restrict__ h,
+                                                             const double* __restrict__ slots, float max_norm,
+                                                             int skip_nonfinite, float b1, float b2) {
+  __shared__ double sh[4];
+  static_assert(MMT_GUARD_SLOTS % 256 == 0, "a whole number of slots per thread");
+  constexpr int PER = MMT_GUARD_SLOTS / 256;
+  double a = 0.0;
+#pragma unroll
+  for (int k = 0; k < PER; ++k) a += slots[threadIdx.x * PER + k];  // index order
+  const double sum = block_sum_f64(a, sh);
+  if (threadIdx.x != 0) return;
+  const float norm = (float)sqrt(sum);
+  float coef = 1.f;
+  if (max_norm > 0.f && max_norm < INFINITY) {
+    coef = max_norm / (norm + 1e-6f);  // torch.nn.utils.clip_grad_norm_; a NaN norm stays a NaN coefficient
+    if (coef > 1.f) coef = 1.f;
+  }
+  h->norm = norm;
+  h->coef = coef;
+  const bool finite = sum - sum == 0.0;  // false for +inf and NaN
+  if (skip_nonfinite && !finite) {
+    h->ok = 0;
+    h->skipped_steps += 1;
+    return;
+  }
+  h->ok = 1;
+  const int64_t t = h->applied_steps + 1;
+  h->applied_steps = t;
+  if (coef < 1.f) h->clipped_steps += 1;
+  // as mmt_adamw_step computes them on the host: fp64, each rounded to fp32 once
+  h->bias_correction1 = (float)(1.0 - pow((double)b1, (double)t));
+  h->bias_correction2_sqrt = (float)sqrt(1.0 - pow((double)b2, (double)t));
+}
+
+__global__ __launch_bounds__(256) void adamw_guarded_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                            float* __restrict__ m, float* __restrict__ v, int64_t n4,
+                                                            int64_t n, float lr, float b1, float b2, float eps, float wd,
+                                                            const mmt_guard_header* __restrict__ h) {
+  // one uniform load per value, kept in registers
+  const int ok = h->ok;
+  if (ok == 0) return;  // skipped step: p, m and v are neither read nor written
+  const float coef = h->coef, bc1 = h->bias_correction1, bc2_sqrt = h->bias_correction2_sqrt;
+  const float step_size = lr / bc1;
+  const float decay = 1.f - lr * wd;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+    f32x4 pp = reinterpret_cast<f32x4*>(p)[i];
+    f32x4 gg = reinterpret_cast<const f32x4*>(g)[i];
+    f32x4 mm = reinterpret_cast<f32x4*>(m)[i];
+    f32x4 vv = reinterpret_cast<f32x4*>(v)[i];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      gg[e] *= coef;
+      pp[e] *= decay;
+      mm[e] += (gg[e] - mm[e]) * (1.f - b1);
+      vv[e] = vv[e] * b2 + (1.f - b2) * gg[e] * gg[e];
+      const float denom = sqrtf(vv[e]) / bc2_sqrt + eps;
+      pp[e] -= step_size * mm[e] / denom;
+    }
+    reinterpret_cast<f32x4*>(p)[i] = pp;
+    reinterpret_cast<f32x4*>(m)[i] = mm;
+    reinterpret_cast<f32x4*>(v)[i] = vv;
+  }
+  // scalar tail
+  const int64_t t = n4 * 4 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t < n) {
+    float pp = p[t] * decay;
+    const float gg = g[t] * coef;
+    float mm = m[t] + (gg - m[t]) * (1.f - b1);
+    float vv = v[t] * b2 + (1.f - b2) * gg * gg;
+    pp -= step_size * mm / (sqrtf(vv) / bc2_sqrt + eps);
+    p[t] = pp; m[t] = mm; v[t] = vv;
+  }
+}
+
+hipError_t mmt_launch_grad_sqsum(const float* g, int64_t n, int add, void* guard, hipStream_t s) {
+  if (add && n == 0) return hipSuccess;  // adds nothing (add == 0 still overwrites every slot)
+  double* slots = reinterpret_cast<double*>(static_cast<char*>(guard) + sizeof(mmt_guard_header));
+  hipLaunchKernelGGL(grad_sqsum_kernel, dim3(MMT_GUARD_SLOTS), dim3(256), 0, s, g, n / 4, n, add, slots);
+  return hipGetLastError();
+}
+
+hipError_t mmt_launch_guard_finalize(void* guard, float max_norm, int skip_nonfinite, float b1, float b2,
+                                     hipStream_t s) {
+  const double* slots = reinterpret_cast<const double*>(static_cast<char*>(guard) + sizeof(mmt_guard_header));
+  hipLaunchKernelGGL(guard_finalize_kernel, dim3(1), dim3(256), 0, s, static_cast<mmt_guard_header*>(guard), slots,
+                     max_norm, skip_nonfinite, b1, b2);
+  return hipGetLastError();
+}
+
+hipError_t mmt_launch_adamw_guarded(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1,
+                                    float b2, float eps, float wd, const void* guard, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  const int64_t n4 = n / 4;
+  int64_t blocks = (n4 + 255) / 256;
+  if (blocks < 1) blocks = 1;
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(adamw_guarded_kernel, dim3((unsigned)blocks), dim3(256), 0, s, p, g, m, v, n4, n, lr, b1, b2, eps,
+                     wd, static_cast<const mmt_guard_header*>(guard));
   return hipGetLastError();
 }
 

@@ -220,6 +220,8 @@ struct mmt_ctx {
   // latched into det by the next mmt_forward (a forward and its backward always run under one setting)
   bool det = false;
   bool det_req = false;
+  // mmt_set_grad_accumulate: stage 0 of the backward leaves `grads` as it is (every writer adds)
+  bool grad_accum = false;
 };
 
 namespace {
@@ -1532,7 +1534,8 @@ int run_backward_stage(mmt_ctx* c, Runner& r, int stage, const float* loss_grads
   const int par = stage & 1;  // copy of the side-stream-read scratch this stage writes (Plan)
   if (stage == 0) {
     c->d16 = 0;
-    HIPCHK(c, hipMemsetAsync(grads, 0, sizeof(float) * c->nactive, r.s));  // the active prefix only
+    // the active prefix only; in-place accumulation (mmt_set_grad_accumulate) adds to what is there
+    if (!c->grad_accum) HIPCHK(c, hipMemsetAsync(grads, 0, sizeof(float) * c->nactive, r.s));
     // the token-table gradient's row sort (stable: a fixed summation order) needs only the forward's
     // token ids: it runs now on the side stream, off the critical path (27.6 us serial at C1 as the
     // embedding stage's first launch in round 5)
@@ -2167,6 +2170,35 @@ int mmt_adamw_step(mmt_ctx* c, void* stream, float* params, const float* grads, 
   return MMT_OK;
 }
 
+int64_t mmt_guard_state_bytes(void) {
+  return (int64_t)sizeof(mmt_guard_header) + (int64_t)MMT_GUARD_SLOTS * (int64_t)sizeof(double);
+}
+
+static bool misaligned16(const void* p) { return ((uintptr_t)p & 15) != 0; }
+
+int mmt_grad_sqsum(void* stream, const float* grads, int64_t n, int32_t add, void* guard) {
+  if (!guard || n < 0 || (n > 0 && !grads) || misaligned16(grads) || misaligned16(guard)) return MMT_ERR_INVALID;
+  return mmt_launch_grad_sqsum(grads, n, add != 0, guard, (hipStream_t)stream) == hipSuccess ? MMT_OK : MMT_ERR_HIP;
+}
+
+int mmt_guard_finalize(void* stream, float max_norm, int32_t skip_nonfinite, float beta1, float beta2, void* guard) {
+  if (!guard || misaligned16(guard)) return MMT_ERR_INVALID;
+  return mmt_launch_guard_finalize(guard, max_norm, skip_nonfinite != 0, beta1, beta2, (hipStream_t)stream) == hipSuccess
+             ? MMT_OK
+             : MMT_ERR_HIP;
+}
+
+int mmt_adamw_step_guarded(mmt_ctx* c, void* stream, float* params, const float* grads, float* m, float* v, int64_t n,
+                           float lr, float b1, float b2, float eps, float wd, const void* guard) {
+  if (!guard || n < 0 || !params || !grads || !m || !v)
+    return fail(c, MMT_ERR_INVALID, "mmt_adamw_step_guarded: bad argument");
+  if (misaligned16(params) || misaligned16(grads) || misaligned16(m) || misaligned16(v) || misaligned16(guard))
+    return fail(c, MMT_ERR_INVALID, "mmt_adamw_step_guarded: pointers must be 16-byte aligned");
+  const hipError_t e = mmt_launch_adamw_guarded(params, grads, m, v, n, lr, b1, b2, eps, wd, guard, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(c, MMT_ERR_HIP, std::string("adamw_guarded: ") + hipGetErrorString(e));
+  return MMT_OK;
+}
+
 int mmt_eval_direction(mmt_ctx* c, void* stream, int32_t batch, int32_t T, int32_t V, const float* logits,
                        const int64_t* xb, const int64_t* yb, const double* vocab, int32_t is_percent,
                        int32_t* wins_losses, double* certainty_sum) {
@@ -2207,6 +2239,14 @@ extern "C" int mmt_set_deterministic(mmt_ctx* c, int32_t on) {
   return MMT_OK;
 }
 extern "C" int32_t mmt_get_deterministic(const mmt_ctx* c) { return c && c->det_req ? 1 : 0; }
+
+// in-place gradient accumulation (mmt.h): read at stage 0 of the backward, per context
+extern "C" int mmt_set_grad_accumulate(mmt_ctx* c, int32_t on) {
+  if (!c) return MMT_ERR_INVALID;
+  c->grad_accum = on != 0;
+  return MMT_OK;
+}
+extern "C" int32_t mmt_get_grad_accumulate(const mmt_ctx* c) { return c && c->grad_accum ? 1 : 0; }
 
 extern "C" int mmt_probe_set(mmt_ctx* c, const char* label) {
   if (!c) return MMT_ERR_INVALID;

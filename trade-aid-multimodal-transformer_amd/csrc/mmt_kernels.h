@@ -389,6 +389,12 @@ hipError_t mmt_launch_drop_copy(const DropCopyBatch& b, int R, int C, hipStream_
 
 hipError_t mmt_launch_adamw(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2,
                             float eps, float wd, float bc1, float bc2_sqrt, hipStream_t s);
+// guarded optimizer step (mmt.h): `guard` = mmt_guard_header + MMT_GUARD_SLOTS fp64 block partials
+hipError_t mmt_launch_grad_sqsum(const float* g, int64_t n, int add, void* guard, hipStream_t s);
+hipError_t mmt_launch_guard_finalize(void* guard, float max_norm, int skip_nonfinite, float b1, float b2,
+                                     hipStream_t s);
+hipError_t mmt_launch_adamw_guarded(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1,
+                                    float b2, float eps, float wd, const void* guard, hipStream_t s);
 
 hipError_t mmt_launch_eval_direction(const float* logits, const int64_t* xb, const int64_t* yb, const double* vocab,
                                      int B, int T, int V, int is_pct, int* wins_losses, double* certainty,

@@ -40,6 +40,24 @@ class MmtConfig(ctypes.Structure):
     ]
 
 
+class MmtGuardHeader(ctypes.Structure):
+    """struct mmt_guard_header (include/mmt.h): offset 0 of an optimizer's guard state."""
+    _fields_ = [
+        ("norm", c_f32),
+        ("coef", c_f32),
+        ("ok", c_i32),
+        ("reserved0", c_i32),
+        ("applied_steps", c_i64),
+        ("skipped_steps", c_i64),
+        ("clipped_steps", c_i64),
+        ("bias_correction1", c_f32),
+        ("bias_correction2_sqrt", c_f32),
+        ("reserved1", c_i32 * 4),
+    ]
+
+
+GUARD_SLOTS = 1024  # MMT_GUARD_SLOTS: fp64 block partials after the header
+
 EPI = {
     "store_bf16": 0, "bias_tanh_bf16": 1, "bias_relu_bf16": 2, "bias_resid_f32": 3, "store_f32": 4,
     "dtanh_bf16": 5, "drelu_bf16": 6, "acc_f32": 7, "atomic_f32": 8,
@@ -66,6 +84,13 @@ _SIGS = {
     "mmt_backward_stage_range": (c_i32, [c_vp, c_i32, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),
     "mmt_backward_stage": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "mmt_adamw_step": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_f32, c_f32, c_f32, c_f32, c_f32]),
+    "mmt_guard_state_bytes": (c_i64, []),
+    "mmt_grad_sqsum": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp]),
+    "mmt_guard_finalize": (c_i32, [c_vp, c_f32, c_i32, c_f32, c_f32, c_vp]),
+    "mmt_adamw_step_guarded": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_f32, c_f32, c_f32, c_f32, c_f32,
+                                       c_vp]),
+    "mmt_set_grad_accumulate": (c_i32, [c_vp, c_i32]),
+    "mmt_get_grad_accumulate": (c_i32, [c_vp]),
     "mmt_eval_direction": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),
     "mmt_set_dropout_seed": (c_i32, [c_vp, ctypes.c_uint64]),
     "mmt_probe_set": (c_i32, [c_vp, c_cp]),

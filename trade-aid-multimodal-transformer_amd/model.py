@@ -26,6 +26,7 @@ Differences that are by design:
   * generate keeps a KV cache (one prefill forward, then one position per token through
     mmt_decode_step) while the sequence fits the block; the reference re-runs the forward.
 """
+import contextlib
 import ctypes
 
 import torch
@@ -37,7 +38,8 @@ from config_utils import (_get_block_size, _get_deterministic, _get_dropout, _ge
 
 
 class _MmtStep(torch.autograd.Function):
-    """One forward through the C-ABI; its backward is mmt_backward into a fresh flat grad."""
+    """One forward through the C-ABI; its backward is mmt_backward into a fresh flat grad (or, with
+    set_grad_accumulation on, in place into flat_params.grad: then no gradient is returned for `flat`)."""
 
     @staticmethod
     def forward(ctx, flat, owner, training, n_mod, *tensors):
@@ -124,6 +126,9 @@ class MultimodalTransformer(nn.Module):
         self._gen = 0
         self._last = None
         self._grad_sync = None  # mmt_dist.GradSync when data parallel
+        self.grad_accumulation = False  # set_grad_accumulation: the backward writes into flat_params.grad in place
+        self._grad_buf = None  # the in-place mode's persistent gradient buffer (becomes .grad when .grad is None)
+        self._no_sync = False  # inside no_sync(): no gradient exchange
 
     def set_deterministic(self, on):
         """Deterministic training mode (include/mmt.h, mmt_set_deterministic): bit-identical gradients
@@ -319,12 +324,74 @@ class MultimodalTransformer(nn.Module):
             out.append((b.value, e.value))
         return out
 
+    def set_grad_accumulation(self, on):
+        """In-place gradient accumulation (include/mmt.h, mmt_set_grad_accumulate). When on, the backward
+        writes straight into `flat_params.grad` instead of handing autograd a fresh gradient that
+        AccumulateGrad adds in another pass: if `.grad` is None the engine overwrites a persistent buffer
+        the model owns and that buffer becomes `.grad`; otherwise the engine adds into `.grad` in place.
+        `zero_grad(set_to_none=True)` between optimizer steps keeps its meaning (the next backward
+        overwrites), `reference_grad_views()` keeps working. Averaging over k micro-batches is the caller's
+        loss scale: `(sum(losses) / k).backward()` costs nothing extra, the engine differentiates
+        sum_i loss_grads[i] * loss_i anyway.
+        In this mode autograd sees no gradient for `flat_params`, so tensor hooks registered on it do not
+        fire with a gradient (torch skips them or calls them with None, depending on its version; read
+        `flat_params.grad` after the backward instead), and a `.grad` kept from before a `zero_grad(set_to_none=True)` is the model's buffer: the next
+        backward overwrites it (clone it to keep it)."""
+        self.grad_accumulation = bool(on)
+
+    @contextlib.contextmanager
+    def no_sync(self):
+        """In the spirit of DistributedDataParallel.no_sync: inside the context a data-parallel model
+        (mmt_dist.enable_data_parallel) runs the unstaged backward and exchanges nothing; the first backward
+        outside it all-reduces what has accumulated. Needs set_grad_accumulation(True) when data parallel
+        (the all-reduce must see the accumulated sums, not the last micro-batch alone). Without data
+        parallelism it changes nothing."""
+        if self._grad_sync is not None and not self.grad_accumulation:
+            raise RuntimeError("no_sync() on a data-parallel model needs set_grad_accumulation(True)")
+        old = self._no_sync
+        self._no_sync = True
+        try:
+            yield
+        finally:
+            self._no_sync = old
+
+    def _grad_target(self, flat):
+        """(buffer the engine writes, accumulate?) of the in-place mode."""
+        p = self.flat_params
+        if p.grad is None:
+            b = self._grad_buf
+            if b is None or b.device != flat.device or b.numel() != flat.numel():
+                b = self._grad_buf = torch.empty_like(flat.detach())
+            return b, False
+        g = p.grad
+        if g.dtype != torch.float32 or g.device != flat.device or not g.is_contiguous() or g.numel() != flat.numel():
+            raise RuntimeError("gradient accumulation needs flat_params.grad as a contiguous fp32 tensor on the "
+                               "model's device")
+        return g, True
+
     def _launch_backward(self, g_losses):
         L = ML.lib()
         flat = self._last[0]
         g = g_losses.detach().to(dtype=torch.float32).contiguous()
-        grad = torch.empty_like(flat)
-        sync = self._grad_sync
+        inplace = self.grad_accumulation
+        if inplace:
+            grad, acc = self._grad_target(flat)
+            ML.check(L.mmt_set_grad_accumulate(self._ctx, 1 if acc else 0), self._ctx, "mmt_set_grad_accumulate")
+        else:
+            grad = torch.empty_like(flat)
+        sync = None if self._no_sync else self._grad_sync
+        try:
+            grad = self._run_backward(L, flat, g, grad, sync)
+        finally:
+            if inplace:
+                L.mmt_set_grad_accumulate(self._ctx, 0)
+        if inplace:
+            if self.flat_params.grad is None:
+                self.flat_params.grad = grad
+            return None  # nothing for AccumulateGrad to add
+        return grad
+
+    def _run_backward(self, L, flat, g, grad, sync):
         with torch.cuda.device(flat.device):
             if sync is None:
                 rc = L.mmt_backward(self._ctx, ML.stream_ptr(flat.device), ML.ptr(g), ML.ptr(flat), ML.ptr(grad),
