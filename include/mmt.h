@@ -174,6 +174,62 @@ int mmt_adamw_step_guarded(mmt_ctx* ctx, void* stream, float* params, const floa
 /* The three calls above return MMT_ERR_INVALID before any launch for a null guard, n < 0, or a tensor or
  * guard pointer that is not 16-byte aligned. */
 
+/* ---- per-tensor statistics of a flat fp32 buffer, and the first-fault record ----
+ * One streaming read of x[0 .. n) gives, for every segment of a segment table, the fp64 sum of squares and the
+ * largest magnitude of its finite elements, its NaN and Inf counts and the position of its first non-finite
+ * element. Asynchronous on `stream`, no device-to-host copy, no sync.
+ *
+ * Segments: seg_begin is a device array of nseg + 1 ascending offsets; segment s is x[seg_begin[s] ..
+ * seg_begin[s + 1]). Offsets need not be multiples of 4 and a segment may be empty. Tensors that are padded
+ * apart are described by giving every gap a segment of its own (an unnamed one: the caller ignores its
+ * statistics); elements below seg_begin[0] or from seg_begin[nseg] on belong to no segment. What lies in a gap
+ * or outside the table influences no other segment's statistics. Offsets are clamped to [0, n] on the device.
+ *
+ * A record is mmt_stats_record_bytes(nseg) bytes, 16-byte aligned: struct mmt_stats_header at offset 0, then
+ * mmt_tensor_stat[nseg]. The scratch is mmt_stats_scratch_bytes(n, nseg) bytes, 16-byte aligned, contents
+ * undefined before and after a call (one 32-byte partial per overlapping (chunk of MMT_STATS_CHUNK elements,
+ * segment) pair). x must be 16-byte aligned.
+ *
+ * mode MMT_STATS_ALWAYS: the record is overwritten and valid = 1. `guard` (nullable) is an optimizer's guard
+ * state: its applied / skipped counts are copied into the header (0 without one).
+ * mode MMT_STATS_ON_SKIP (needs a guard; call it after mmt_guard_finalize and before the guarded steps, the
+ * gradients are intact there): the record is written only when the guard header's ok == 0 AND the record's
+ * valid == 0; otherwise the launches return after one uniform load each, make no pass over x and leave the
+ * record byte for byte as it was. So the first skipped step after arming is kept until the caller re-arms
+ * with a 4-byte memset of `valid` to 0 on the same stream.
+ *
+ * Three launches: per-chunk segmented partials (fp64 from the per-thread accumulator on, fixed trees, plain
+ * stores), one wave per segment that adds its chunk partials in a fixed order, and a one-thread commit that
+ * alone writes the header. No float atomics, no workgroup waits for another, and no workgroup reads a word
+ * another workgroup of the same call writes: the record is bit-identical run to run for identical input.
+ * sqsum is within (elements of the segment) * 2^-53 relative of the exact sum (each fp32 square is exact in
+ * fp64, all terms are non-negative); the other fields are exact.
+ * MMT_ERR_INVALID before any launch for: a null x with n > 0, a null seg_begin / scratch / record, n < 0,
+ * nseg < 0, an unknown mode, x / scratch / record not 16-byte aligned, guard not 16-byte aligned, ON_SKIP
+ * without a guard. nseg == 0 is valid and writes the header only. */
+struct mmt_tensor_stat {      /* 40 bytes, one per segment */
+  double sqsum;               /* fp64 sum of x^2 over the FINITE elements of the segment */
+  int64_t nan_count;
+  int64_t inf_count;          /* +Inf and -Inf */
+  int64_t first_bad;          /* index inside the segment of its first non-finite element, -1: none */
+  float absmax;               /* max |x| over the finite elements, 0 when there is none */
+  float reserved;
+};
+struct mmt_stats_header {     /* 32 bytes at offset 0 of a stats record; mmt_tensor_stat[nseg] follow */
+  int32_t valid;              /* 0: empty / armed, 1: holds a snapshot */
+  int32_t nseg;
+  int64_t applied_steps;      /* the guard header's counters when the snapshot was taken (0 without a guard) */
+  int64_t skipped_steps;
+  int64_t reserved;
+};
+#define MMT_STATS_CHUNK 4096  /* elements per first-pass workgroup */
+enum { MMT_STATS_ALWAYS = 0, MMT_STATS_ON_SKIP = 1 };
+int64_t mmt_stats_chunk(void); /* MMT_STATS_CHUNK, for callers that cannot read this header */
+int64_t mmt_stats_record_bytes(int32_t nseg);           /* -1 for nseg < 0 */
+int64_t mmt_stats_scratch_bytes(int64_t n, int32_t nseg); /* -1 for n < 0 or nseg < 0 */
+int mmt_tensor_stats(void* stream, const float* x, int64_t n, const int64_t* seg_begin /* device, [nseg + 1] */,
+                     int32_t nseg, int32_t mode, const void* guard /* nullable */, void* scratch, void* record);
+
 /* In-place gradient accumulation: with on != 0, stage 0 of mmt_backward / mmt_backward_stage does not zero
  * `grads`, so the backward adds its gradient to what the buffer holds (every writer into `grads` adds:
  * float atomics, the ordered sums, the split-K slab reduce and the one-pass weight-gradient epilogue all

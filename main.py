@@ -86,14 +86,21 @@ def run(cfg, data, log=print):
     grad_clip = config_utils._get_grad_clip()
     accum = config_utils._get_grad_accum_steps()
     skip_nonfinite = config_utils._get_skip_nonfinite_steps()
-    guarded = grad_clip is not None or accum > 1 or skip_nonfinite
+    grad_stats = config_utils._get_grad_stats()  # per-tensor gradient statistics (mmt_stats), "off" by default
+    if grad_stats == "skipped":
+        skip_nonfinite = True  # the record is of the first SKIPPED step: the mode implies the skip
+    guarded = grad_clip is not None or accum > 1 or skip_nonfinite or grad_stats != "off"
 
     def make_optimizer(mm):
         if not guarded:
             return mmt_optim.AdamW(mm.parameters(), lr=cfg["learning_rate"])
         # accumulation alone still reports the gradient norm: an infinite bound never clips
+        stats = None
+        if grad_stats != "off":
+            import mmt_stats
+            stats = mmt_stats.TensorStats(mm, mode=grad_stats)
         return mmt_optim.AdamW(mm.parameters(), lr=cfg["learning_rate"], skip_nonfinite=skip_nonfinite,
-                               max_grad_norm=grad_clip if grad_clip is not None else float("inf"))
+                               max_grad_norm=grad_clip if grad_clip is not None else float("inf"), stats=stats)
 
     def fresh():
         mm = MultimodalTransformer(M, V, params).to(device)
@@ -163,6 +170,10 @@ def run(cfg, data, log=print):
                 guard_note = (f"| GradNorm: {'n/a' if norm is None else format(float(norm), '.4f')} "
                               f"| Clipped: {clipped - seen_clipped} | Skipped: {skipped - seen_skipped} ")
                 seen_clipped, seen_skipped = clipped, skipped  # both lines below carry the note
+                if optimizer.stats is not None:
+                    report = optimizer.stats.read(rearm=True)  # one D2H copy; None while nothing was recorded
+                    if report is not None:
+                        log(f"GRAD STATS: Step {it}/{max_iters} | {report.format(max_names=8)}")
             if not (np.isnan(losses["train"]) or np.isnan(losses["val"])):
                 log(f"\nLOSS METRICS: Step {it}/{max_iters} | Train: {losses['train']:.4f} | Val: {losses['val']:.4f} "
                     f"{guard_note}| Time: {now}")

@@ -17,7 +17,9 @@ _DEFAULTS = {
                             "eval_iters": 40, "learning_rate": 3e-4,
                             # build-only keys (the reference ignores unknown keys): the guarded optimizer step
                             # (mmt_optim.AdamW max_grad_norm / skip_nonfinite) and in-place gradient accumulation
-                            "grad_clip": None, "grad_accum_steps": 1, "skip_nonfinite_steps": False},
+                            "grad_clip": None, "grad_accum_steps": 1, "skip_nonfinite_steps": False,
+                            # build-only key: per-tensor gradient statistics (mmt_stats.TensorStats)
+                            "grad_stats": "off"},
     "model_architecture": {"n_embd": 384, "n_head": 6, "n_layer": 6, "dropout": 0.2,
                            "fixed_values": [-0.5, -0.2, -0.1, 0, 0.1, 0.2, 0.5],
                            # build-only key (the reference ignores unknown keys): "bf16" | "fp8"
@@ -149,3 +151,15 @@ def _get_skip_nonfinite_steps():
     if isinstance(v, int) and v in (0, 1):
         return bool(v)
     raise ValueError(f"skip_nonfinite_steps must be a boolean, got {v!r}")
+
+
+def _get_grad_stats():
+    """Build-only knob: per-tensor gradient statistics on the device (mmt_stats.TensorStats handed to
+    mmt_optim.AdamW). "off" (default, also when the key is absent), "skipped" (the first skipped step since the
+    last evaluation is kept; main.run turns skip_nonfinite_steps on with it) or "every" (the latest step)."""
+    v = _get_config().get("grad_stats", "off")
+    if v is False:  # YAML reads a bare `off` as a boolean
+        return "off"
+    if not isinstance(v, str) or v not in ("off", "skipped", "every"):
+        raise ValueError(f"grad_stats must be 'off', 'skipped' or 'every', got {v!r}")
+    return v

@@ -58,6 +58,33 @@ class MmtGuardHeader(ctypes.Structure):
 
 GUARD_SLOTS = 1024  # MMT_GUARD_SLOTS: fp64 block partials after the header
 
+
+class MmtTensorStat(ctypes.Structure):
+    """struct mmt_tensor_stat (include/mmt.h): one per segment of a stats record, after the header."""
+    _fields_ = [
+        ("sqsum", ctypes.c_double),
+        ("nan_count", c_i64),
+        ("inf_count", c_i64),
+        ("first_bad", c_i64),
+        ("absmax", c_f32),
+        ("reserved", c_f32),
+    ]
+
+
+class MmtStatsHeader(ctypes.Structure):
+    """struct mmt_stats_header (include/mmt.h): offset 0 of a stats record."""
+    _fields_ = [
+        ("valid", c_i32),
+        ("nseg", c_i32),
+        ("applied_steps", c_i64),
+        ("skipped_steps", c_i64),
+        ("reserved", c_i64),
+    ]
+
+
+STATS_CHUNK = 4096  # MMT_STATS_CHUNK: elements per first-pass workgroup of mmt_tensor_stats
+STATS_ALWAYS, STATS_ON_SKIP = 0, 1  # mmt_tensor_stats modes
+
 EPI = {
     "store_bf16": 0, "bias_tanh_bf16": 1, "bias_relu_bf16": 2, "bias_resid_f32": 3, "store_f32": 4,
     "dtanh_bf16": 5, "drelu_bf16": 6, "acc_f32": 7, "atomic_f32": 8,
@@ -89,6 +116,10 @@ _SIGS = {
     "mmt_guard_finalize": (c_i32, [c_vp, c_f32, c_i32, c_f32, c_f32, c_vp]),
     "mmt_adamw_step_guarded": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_f32, c_f32, c_f32, c_f32, c_f32,
                                        c_vp]),
+    "mmt_stats_chunk": (c_i64, []),
+    "mmt_stats_record_bytes": (c_i64, [c_i32]),
+    "mmt_stats_scratch_bytes": (c_i64, [c_i64, c_i32]),
+    "mmt_tensor_stats": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "mmt_set_grad_accumulate": (c_i32, [c_vp, c_i32]),
     "mmt_get_grad_accumulate": (c_i32, [c_vp]),
     "mmt_eval_direction": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),

@@ -16,6 +16,12 @@ when the norm is NaN / Inf and skip_nonfinite is set. Nothing is copied to the h
 the step count lives on the device (as in torch's capturable AdamW), so a skipped step does not advance
 the bias correction. `last_grad_norm` is a 0-dim device tensor; `counters()` is the only call that syncs.
 With both options at their defaults step() is the plain path above, unchanged.
+
+Statistics (opt-in: `stats=mmt_stats.TensorStats(model, mode)`). step() enqueues the per-tensor statistics of
+the gradient of that model's `flat_params`: on the guarded path between mmt_guard_finalize and the first
+guarded step (mode "skipped": only the first step the guard skips is recorded, on the device, until the
+record is re-armed; mode "every": every step), on the plain path before the step (mode "every" only). Still
+no copy to the host and no sync: `stats.read()` is the call that syncs.
 """
 import math
 
@@ -28,7 +34,7 @@ _HDR_COUNTERS = (16, 40)  # byte range of applied / skipped / clipped steps in s
 
 class AdamW(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None,
-                 skip_nonfinite=False):
+                 skip_nonfinite=False, stats=None):
         if lr < 0.0:
             raise ValueError(f"Invalid learning rate: {lr}")
         if max_grad_norm is not None:
@@ -43,6 +49,13 @@ class AdamW(torch.optim.Optimizer):
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
         self.skip_nonfinite = skip_nonfinite
         self.guarded = self.max_grad_norm is not None or skip_nonfinite
+        if stats is not None:
+            if getattr(stats, "mode", None) not in ("skipped", "every") or not callable(getattr(stats, "record", None)):
+                raise TypeError(f"stats must be an mmt_stats.TensorStats or None, got {stats!r}")
+            if stats.mode == "skipped" and not self.guarded:
+                raise ValueError("stats in mode 'skipped' records the first step the guard skips: it needs a "
+                                 "guarded optimizer (skip_nonfinite=True; mode 'every' runs on any optimizer)")
+        self.stats = stats
         if self.guarded:
             self._check_betas()
         self._guard = None          # device guard state (mmt_guard_state_bytes), made at the first guarded step
@@ -74,6 +87,8 @@ class AdamW(torch.optim.Optimizer):
                     st["exp_avg_sq"] = torch.zeros_like(p)
                 st["step"] += 1
                 n = p.numel()
+                if self.stats is not None and p is self.stats.model.flat_params:
+                    self.stats.record(g)
                 rc = L.mmt_adamw_step(None, ML.stream_ptr(p.device), ML.ptr(p), ML.ptr(g), ML.ptr(st["exp_avg"]),
                                       ML.ptr(st["exp_avg_sq"]), n, st["step"], group["lr"], b1, b2, group["eps"],
                                       group["weight_decay"])
@@ -130,6 +145,10 @@ class AdamW(torch.optim.Optimizer):
             max_norm = self.max_grad_norm if self.max_grad_norm is not None else 0.0
             ML.check(L.mmt_guard_finalize(s, max_norm, 1 if self.skip_nonfinite else 0, b1, b2, gp), None,
                      "mmt_guard_finalize")
+            if self.stats is not None:  # the verdict is in, the gradients are still intact
+                for group, p in work:
+                    if p is self.stats.model.flat_params:
+                        self.stats.record(p.grad, guard)
             for group, p in work:
                 st = self.state[p]
                 if "exp_avg" not in st:

@@ -324,6 +324,50 @@ class MultimodalTransformer(nn.Module):
             out.append((b.value, e.value))
         return out
 
+    def tensor_segments(self):
+        """Every reference tensor of the active prefix (the part of the flat buffer that gets gradients), in
+        offset order: a dict with `names`, `begins`, `ends` (element offsets into flat_params / its gradient),
+        and the segment table of mmt_tensor_stats: `bounds` (the tensors and the gaps between them, see
+        mmt_stats.build_segments), `named` (index in the table of each tensor) and `device` (the table as an
+        int64 device tensor, made once per device and cached). The tensors are asserted disjoint."""
+        import mmt_stats
+        dev = self.flat_params.device
+        seg = getattr(self, "_segments", None)
+        if seg is None:
+            rows = []
+            for name, off, shp, _ in self._tensors:
+                if off >= self._n_active:
+                    continue
+                n = 1
+                for s in shp:
+                    n *= s
+                rows.append((off, off + n, name))
+            rows.sort()
+            names, begins, ends = [r[2] for r in rows], [r[0] for r in rows], [r[1] for r in rows]
+            bounds, named = mmt_stats.build_segments(names, begins, ends)  # raises when two tensors overlap
+            assert not ends or ends[-1] <= self._n_active
+            seg = self._segments = {"names": names, "begins": begins, "ends": ends, "bounds": bounds, "named": named,
+                                    "device": None}
+        if dev.type == "cuda" and (seg["device"] is None or seg["device"].device != dev):
+            seg["device"] = torch.tensor(seg["bounds"], dtype=torch.int64).to(dev)
+        return seg
+
+    def tensor_stats(self, which="grad"):
+        """A one-shot snapshot of the per-tensor statistics of the gradient ("grad") or of the parameters
+        ("param"): an mmt_stats.StatsReport (sum of squares, largest magnitude, NaN / Inf counts and the first
+        non-finite position per reference tensor, rollups per backward stage). One device pass, one sync."""
+        import mmt_stats
+        if which not in ("grad", "param"):
+            raise ValueError(f"tensor_stats: which must be 'grad' or 'param', got {which!r}")
+        buf = self.flat_params.grad if which == "grad" else self.flat_params.detach()
+        if buf is None:
+            raise RuntimeError("tensor_stats('grad'): flat_params.grad is None (run a backward first)")
+        st = getattr(self, "_stats_oneshot", None)
+        if st is None or st._rec is None or st._rec.device != buf.device:
+            st = self._stats_oneshot = mmt_stats.TensorStats(self, mode="every")
+        st.record(buf)
+        return st.read(rearm=True)
+
     def set_grad_accumulation(self, on):
         """In-place gradient accumulation (include/mmt.h, mmt_set_grad_accumulate). When on, the backward
         writes straight into `flat_params.grad` instead of handing autograd a fresh gradient that
