@@ -415,6 +415,18 @@ int mmt_op_attention_bwd_ws(void* stream, int32_t B, int32_t T, int32_t H, int32
                             const float* const* lse, const void* dout, int32_t dout_ld, float* const* dvec, void* dq,
                             int32_t dq_ld, void* const* dk, void* const* dv, int32_t dkv_ld, int32_t dkv_hstride,
                             float* dq32, int32_t dq32_ld);
+/* hs-32 causal self-attention (T <= 256) with Q / K / V made on chip: in place of q / k / v the kernels take
+ * the stage-1 rows h1 (bf16 [B*T][ld_h1], ld_h1 % 8 == 0, 16-B aligned; column block blk = kind * H + head of
+ * 16 columns, kinds K, Q, V; pad columns and rows past the batch are never read) and w2 (fp32 [3 H][32][16],
+ * 16-B aligned) and compute X = bf16(h1_blk bf16(W2_blk)^T) per (batch, head) themselves: the same bits as
+ * mmt_op_qkv2_fwd's rows. The backward returns the stage-2 gradients: dh1 (bf16, ld_h1; only the 3 H 16 columns
+ * are written), dw2 and db1 (fp32 [3 H][32][16] and [3 H * 16], accumulated by atomics). MMT_ERR_UNSUPPORTED
+ * when the shape or the alignment does not fit (or mmt_attn_set_ring bit 6 is off, for the backward). */
+int mmt_op_attention_fwd_h1(void* stream, int32_t B, int32_t T, int32_t H, const void* h1, int32_t ld_h1,
+                            const float* w2, void* o, int32_t o_ld, float* lse);
+int mmt_op_attention_bwd_h1(void* stream, int32_t B, int32_t T, int32_t H, const void* h1, int32_t ld_h1,
+                            const float* w2, const void* o, int32_t o_ld, const float* lse, const void* dout,
+                            int32_t dout_ld, void* dh1, float* dw2, float* db1);
 int mmt_op_qkv2_fwd(void* stream, int32_t R, int32_t nblk, int32_t hs, const void* h1, int32_t ld_h1,
                     const float* w2, void* out, int32_t ld_out);
 int mmt_op_qkv2_bwd(void* stream, int32_t R, int32_t nblk, int32_t hs, const void* h1, int32_t ld_h1,
@@ -455,6 +467,14 @@ int mmt_set_drop_copy_fuse(int on);
 // (dX W2) * tanh', dW2, db1) in the one-pass attention backward's epilogue, dQ / dK / dV never written;
 // 0 = the separate stage-2 backward over bf16 dQ / dK / dV. Read at every step; returns the previous value
 int mmt_set_attn_qkv2(int on);
+// hs 32 self-attention, T <= 256, bf16, forwards with training != 0, where mmt_set_attn_qkv2's path runs: the
+// attention kernels make Q / K / V themselves from the stage-1 rows h1 and the head's W2 blocks (the same bits
+// the stage-1 GEMM's epilogue stores). Bit 0: the forward does; bit 1: the one-pass backward does. With both
+// bits (3, default, env MMT_ATTN_QKV_ONCHIP) the GEMM drops its stage-2 epilogue and the Q/K/V rows are never
+// written: mmt_decode_step after such a forward fails with MMT_ERR_INVALID (prefill with training = 0). One
+// bit alone still writes them (for measuring each kernel's share). Latched by mmt_forward for that forward
+// and its backward; returns the previous value (tests, A/B)
+int mmt_set_attn_qkv_onchip(int bits);
 // rows per workgroup of the fused out-projection MLP forward at C = 256 (mmt_op_mlp2 and the engine's):
 // 128 (8 waves, one workgroup per CU) or 64 (4 waves, three per CU); default 128 (env MMT_MLP2_BM);
 // returns the previous value (tests, A/B)

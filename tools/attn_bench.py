@@ -6,6 +6,11 @@ Times mmt_op_attention_fwd / _bwd (the engine's kernels, one grouped problem wit
 batch) with HIP events on the current stream, for each value of the attention variant knob
 (mmt_attn_set_ring), interleaved over rounds; prints us and causal-useful TFLOP/s (forward
 2 B H T^2 hs per stream, backward 2.5x that: SURVEY.md §8d).
+
+c1_oc is C1's self-attention with Q / K / V made on chip (mmt_op_attention_fwd_h1 / _bwd_h1: the kernels read the
+stage-1 rows h1 and W2). Its forward compares with c1's directly; its backward includes the Q/K/V stage-2 backward
+(dh1, dW2, db1 in the epilogue, no dQ / dK / dV stores), which c1's standalone backward does not. The primitive
+ops carry no dropout, so both run without keep bits.
 """
 import argparse
 import ctypes
@@ -22,6 +27,7 @@ import mmt_lib as ML  # noqa: E402
 SHAPES = {
     # name: (B (modalities x batch), T, H, hs, streams)
     "c1": (256, 256, 8, 32, 1),
+    "c1_oc": (256, 256, 8, 32, 0),  # streams 0: the on-chip Q/K/V variant (one KV stream)
     "c1_ca": (64, 256, 8, 32, 3),  # C1's cross-attention: one query modality, 3 KV streams
     "target": (128, 512, 8, 64, 1),
     "c3": (128, 1024, 8, 64, 1),
@@ -79,6 +85,29 @@ def setup(B, T, H, hs, ns):
     return fwd, bwd, keep + [o, oj, lse, dvec, do, dq32]
 
 
+def setup_onchip(B, T, H):
+    """C1-style self-attention from h1 [R][3 H 16] and W2 [3 H][32][16] (mmt_op_attention_fwd_h1 / _bwd_h1)."""
+    C, R, dev = H * 32, B * T, "cuda"
+    ld = 3 * H * 16
+    h1 = torch.tanh(torch.randn(R, ld, device=dev)).to(torch.bfloat16)
+    w2 = torch.randn(3 * H, 32, 16, device=dev) * 0.2
+    o = torch.zeros(R, C, dtype=torch.bfloat16, device=dev)
+    lse = torch.zeros(B * H * T, device=dev)
+    do = torch.randn(R, C, device=dev).to(torch.bfloat16)
+    dh1 = torch.zeros(R, ld, dtype=torch.bfloat16, device=dev)
+    dw2, db1 = torch.zeros_like(w2), torch.zeros(ld, device=dev)
+    L = ML.lib()
+    s = ML.stream_ptr()
+
+    def fwd():
+        assert L.mmt_op_attention_fwd_h1(s, B, T, H, ML.ptr(h1), ld, ML.ptr(w2), ML.ptr(o), C, ML.ptr(lse)) == 0
+
+    def bwd():
+        assert L.mmt_op_attention_bwd_h1(s, B, T, H, ML.ptr(h1), ld, ML.ptr(w2), ML.ptr(o), C, ML.ptr(lse), ML.ptr(do), C,
+                                         ML.ptr(dh1), ML.ptr(dw2), ML.ptr(db1)) == 0
+    return fwd, bwd, [h1, w2, o, lse, do, dh1, dw2, db1]
+
+
 def timeit(fn, reps):
     for _ in range(2):
         fn()
@@ -103,8 +132,8 @@ def main():
     rings = [int(x) for x in a.rings.split(",")]
     for name in a.shapes.split(","):
         B, T, H, hs, ns = SHAPES[name]
-        fwd, bwd, _keep = setup(B, T, H, hs, ns)
-        fl = 2.0 * B * H * ns * T * T * hs
+        fwd, bwd, _keep = setup(B, T, H, hs, ns) if ns else setup_onchip(B, T, H)
+        fl = 2.0 * B * H * max(ns, 1) * T * T * hs
         fwd()
         torch.cuda.synchronize()
         res = {}

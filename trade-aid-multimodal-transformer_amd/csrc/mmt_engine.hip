@@ -141,6 +141,16 @@ extern "C" int mmt_set_attn_qkv2(int on) {
   return old;
 }
 
+// hs 32 self-attention at T <= 256 in training forwards: Q / K / V made on chip from h1 and W2 (AttnProblem::oc_*)
+// by the forward (bit 0) and by the one-pass backward (bit 1); with both bits the stage-1 GEMM drops its stage-2
+// epilogue and the Q/K/V rows are never written (env MMT_ATTN_QKV_ONCHIP). Latched by mmt_forward.
+static int g_attn_qkv_onchip = mmt_env_int("MMT_ATTN_QKV_ONCHIP", 3) & 3;
+extern "C" int mmt_set_attn_qkv_onchip(int bits) {
+  const int old = g_attn_qkv_onchip;
+  g_attn_qkv_onchip = bits & 3;
+  return old;
+}
+
 struct mmt_ctx {
   mmt_config cfg;
   int M, C, H, L, T, hs, hh;
@@ -222,6 +232,10 @@ struct mmt_ctx {
   bool det_req = false;
   // mmt_set_grad_accumulate: stage 0 of the backward leaves `grads` as it is (every writer adds)
   bool grad_accum = false;
+  // on-chip self-attention Q/K/V (mmt_set_attn_qkv_onchip): onchip_req is the knob as mmt_forward found it (0
+  // for a training == 0 forward, whose saved Q/K/V are the decode cache); onchip is what the forward's layers
+  // then ran with (0 where the path does not apply), and its backward follows it. 3: Q/K/V were not written
+  int onchip_req = 0, onchip = 0;
 };
 
 namespace {
@@ -624,6 +638,11 @@ void gemm_cost(const GemmBatch& b, int epi, double* fl, double* by) {
     // fused LayerNorm backward: LN input and the accumulated gradient read, that gradient (+ its bf16
     // copy) written, row statistics read
     if (epi == EPI_LN_BWD_F32) x += M * N * 8.0 + (P.o16 ? M * N * 2.0 : 0.0) + M * 8.0;
+    // per-head Q/K/V stage 2 in the epilogue: 2 N output columns written, W2 (fp32 [N / hh][2 hh][hh]) read
+    if (P.qkv2_out) {
+      x += M * 2.0 * N * 2.0 + 2.0 * N * P.qkv2_hh * 4.0;
+      *fl += 2.0 * M * 2.0 * N * P.qkv2_hh;
+    }
     *by += x;
   }
 }
@@ -659,6 +678,14 @@ void attn_cost(const AttnBatch& ab, int B, int T, int H, int hs, bool bwd, bool 
       const double hh = hs / 2;
       x += -rows * C * 2.0 * 3.0 + 2.0 * rows * 3.0 * H * hh * 2.0 + 3.0 * H * hs * hh * 4.0 * 2.0;
       *fl += 2.0 * 2.0 * rows * 3.0 * C * hh;
+    }
+    if (ab.p[g].oc_w2) {
+      // Q / K / V made on chip: their rows are not read; the forward reads h1 and W2 in their place (the
+      // backward's epilogue counts both already); flops: X = h1 W2^T
+      const double hh = hs / 2;
+      x -= rows * C * 2.0 * 3.0;
+      if (!bwd) x += rows * 3.0 * H * hh * 2.0 + 3.0 * H * hs * hh * 4.0;
+      *fl += 2.0 * rows * 3.0 * C * hh;
     }
     *by += x;
   }
@@ -1079,22 +1106,6 @@ int run_forward(mmt_ctx* c, Runner& r, const int64_t* const* idx, const int64_t*
     }
     // (the 128 x 128 bf16 tile only: not on the fp8 kernel, not where the GEMM takes the 256 x 256 tile)
     const bool fuse_qkv2 = qkv2_fuse && (c->hh == 16 || c->hh == 32) && !f8 && !mmt_gemm_wgrad_big(g);
-    for (int i = 0; i < M; ++i) {
-      if (fuse_qkv2) {
-        g.p[i].qkv2_w2 = r.P(x[i].w2); g.p[i].qkv2_out = r.W<bf16_t>(a[i].qkv);
-        g.p[i].qkv2_ld = 3 * C; g.p[i].qkv2_hh = c->hh;
-      }
-    }
-    if (f8) r.gemm8(g, EPI_BIAS_TANH_BF16, "qkv1");
-    else r.gemm(g, true, true, EPI_BIAS_TANH_BF16, 1, "qkv1");
-    for (int i = 0; i < M; ++i) g.p[i].qkv2_out = nullptr;  // g is reused by the next GEMMs
-    if (!fuse_qkv2) {
-      Qkv2Batch qb{}; qb.count = M;
-      for (int i = 0; i < M; ++i) {
-        qb.p[i].h1 = r.W<bf16_t>(a[i].h1); qb.p[i].w2 = r.P(x[i].w2); qb.p[i].out = r.W<bf16_t>(a[i].qkv);
-      }
-      r.ok(mmt_launch_qkv2_fwd(qb, R, 3 * H, hs, ldh1, 3 * C, r.s), "qkv2_fwd");
-    }
     AttnBatch ab{}; ab.count = M;
     for (int i = 0; i < M; ++i) {
       AttnProblem& q = ab.p[i];
@@ -1103,6 +1114,40 @@ int run_forward(mmt_ctx* c, Runner& r, const int64_t* const* idx, const int64_t*
       q.o = r.W<bf16_t>(a[i].o); q.o_ld = C; q.lse[0] = r.W<float>(a[i].lse); q.nstreams = 1;
       r.set_drop(q, l, i, DS_SA_PROB);
       if (r.drop) q.dmask[0] = r.W<uint32_t>(a[i].dm);
+    }
+    // Q / K / V on chip (mmt_set_attn_qkv_onchip; training forwards only): exactly where this GEMM would make
+    // them in its epilogue and the backward will take the one-pass hs-32 kernel with the stage-2 backward in it.
+    // Bit 0: the attention forward makes them from h1 and W2; bit 1: the backward will; both: stage 2 leaves this
+    // GEMM and the rows are never written. The same for every layer, kept in c->onchip for the backward.
+    int oc = 0;
+    if (c->onchip_req && fuse_qkv2 && g_attn_qkv2 && mmt_attn_bwd_fuses_qkv2(ab, T, hs) && !(ldh1 & 7)) {
+      oc = c->onchip_req;
+      for (int i = 0; i < M; ++i)
+        if (((uintptr_t)r.W<bf16_t>(a[i].h1) | (uintptr_t)r.P(x[i].w2)) & 15) oc = 0;
+    }
+    if (l == 0) c->onchip = oc;
+    else if (oc != c->onchip) {
+      r.rc = fail(c, MMT_ERR_STATE, "mmt_forward: the layers disagree on the on-chip Q/K/V path");
+      break;
+    }
+    for (int i = 0; i < M; ++i) {
+      if (fuse_qkv2 && oc != 3) {
+        g.p[i].qkv2_w2 = r.P(x[i].w2); g.p[i].qkv2_out = r.W<bf16_t>(a[i].qkv);
+        g.p[i].qkv2_ld = 3 * C; g.p[i].qkv2_hh = c->hh;
+      }
+      // both bits: no stage 2 and no Q/K/V store, but h1 bit for bit as the fused launch rounds it
+      if (oc == 3) g.p[i].qkv2_h1_only = 1;
+      if (oc & 1) { ab.p[i].oc_h1 = r.W<bf16_t>(a[i].h1); ab.p[i].oc_ld = ldh1; ab.p[i].oc_w2 = r.P(x[i].w2); }
+    }
+    if (f8) r.gemm8(g, EPI_BIAS_TANH_BF16, "qkv1");
+    else r.gemm(g, true, true, EPI_BIAS_TANH_BF16, 1, "qkv1");
+    for (int i = 0; i < M; ++i) { g.p[i].qkv2_out = nullptr; g.p[i].qkv2_h1_only = 0; }  // g is reused by the next GEMMs
+    if (!fuse_qkv2) {
+      Qkv2Batch qb{}; qb.count = M;
+      for (int i = 0; i < M; ++i) {
+        qb.p[i].h1 = r.W<bf16_t>(a[i].h1); qb.p[i].w2 = r.P(x[i].w2); qb.p[i].out = r.W<bf16_t>(a[i].qkv);
+      }
+      r.ok(mmt_launch_qkv2_fwd(qb, R, 3 * H, hs, ldh1, 3 * C, r.s), "qkv2_fwd");
     }
     if (r.drop && (l <= 1 || mask_ahead)) {
       r.join();  // this layer's keep bits (SA and CA) are in (layer 1: every later layer's too)
@@ -1820,7 +1865,12 @@ int run_backward_stage(mmt_ctx* c, Runner& r, int stage, const float* loss_grads
       AttnProblem& q = ab.p[i];
       q.q2_h1 = r.W<bf16_t>(a[i].h1); q.q2_dh1 = r.W<bf16_t>(p.gh1[par][i]); q.q2_ld = ldh1;
       q.q2_w2 = r.P(x[i].w2); q.q2_dw2 = grads + x[i].w2; q.q2_db1 = grads + x[i].b1;
+      // Q / K / V on chip, as the forward latched it (bit 1: this kernel makes them from h1 and W2)
+      if (c->onchip & 2) { q.oc_h1 = q.q2_h1; q.oc_ld = ldh1; q.oc_w2 = q.q2_w2; }
     }
+  if (c->onchip == 3 && !q2)  // (the knobs the forward decided on were changed since)
+    return fail(c, MMT_ERR_STATE, "mmt_backward: the forward kept Q/K/V on chip (mmt_set_attn_qkv_onchip) and the "
+                                  "backward that makes them again (mmt_set_attn_qkv2, mmt_attn_set_ring bit 6) is off");
   Qkv2Batch qb{}; qb.count = M;
   for (int i = 0; i < M; ++i) {
     qb.p[i].h1 = r.W<bf16_t>(a[i].h1); qb.p[i].w2 = r.P(x[i].w2); qb.p[i].dout = r.W<bf16_t>(p.gqkv[i]);
@@ -2034,6 +2084,8 @@ int mmt_forward(mmt_ctx* c, void* stream, int32_t batch, const int64_t* const* i
   if (rc) return rc;
   c->side_off = c->side_off_req;
   c->det = c->det_req;
+  c->onchip_req = training ? g_attn_qkv_onchip : 0;
+  c->onchip = 0;
   Runner r{c, (hipStream_t)stream, workspace, params, nullptr, batch, batch * c->T};
   // dropout (training mode only, as nn.Dropout): one seed per training forward, reused by its backward
   r.drop = training && c->cfg.dropout > 0.f;
@@ -2062,6 +2114,10 @@ int mmt_decode_step(mmt_ctx* c, void* stream, int32_t batch, int32_t pos, const 
   if (!idx || !params || !logits || !workspace) return fail(c, MMT_ERR_INVALID, "mmt_decode_step: null argument");
   if (c->plan.B != batch || !c->cache_ready)
     return fail(c, MMT_ERR_STATE, "mmt_decode_step: run mmt_forward (prefill) on this batch and workspace first");
+  if (c->onchip == 3)
+    return fail(c, MMT_ERR_INVALID, "mmt_decode_step: the last forward (training != 0) kept the self-attention Q/K/V on "
+                                    "chip (mmt_set_attn_qkv_onchip), so the workspace holds no K/V cache: run the "
+                                    "prefill with training = 0");
   if (c->fwd_drop)
     return fail(c, MMT_ERR_STATE, "mmt_decode_step: the prefill forward sampled dropout (training mode); decode "
                                   "has eval semantics: run the prefill with training = 0");

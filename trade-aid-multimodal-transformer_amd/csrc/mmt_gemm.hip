@@ -270,7 +270,7 @@ __global__ __launch_bounds__(TL::NT, MINB) void gemm_kernel(GemmBatch batch) {
     // fused Q/K/V stage 2: the accumulators start at bias / alpha, so the epilogue (short of
     // registers at 3 blocks per CU) holds no bias values
     if (P.qkv2_out) qkv2_stage_w2<TL>(P, lds + LDS_MAIN, n0, tid);  // read after the epilogue's barrier
-    if (P.qkv2_out && P.bias) {
+    if ((P.qkv2_out || P.qkv2_h1_only) && P.bias) {  // (h1 only: the same h1 bits without stage 2)
       const float ia = 1.0f / P.alpha;
       const int hh = (tid & 63) >> 5;
 #pragma unroll
@@ -370,6 +370,14 @@ __global__ __launch_bounds__(TL::NT, MINB) void gemm_kernel(GemmBatch batch) {
   if constexpr (SWAP && EPI == EPI_BIAS_TANH_BF16 && TL::NW == 4 && TL::BN == 128) {
     if (P.qkv2_out) {  // the per-head stage 2 of Q/K/V (uniform per problem)
       qkv2_fused<TL>(P, acc, lds, lds + LDS_MAIN, alpha, m0, n0, lane, wave);
+      epilogue_swap<TL, EPI, EPI_ROWS, true>(P, acc, lds, o32, alpha, m0, n0, tid, lane, wave, det_of(batch, prob));
+    } else if (P.qkv2_h1_only) {  // qkv2_fused's activation (the bias is in the accumulators), no stage 2
+#pragma unroll
+      for (int i = 0; i < AI; ++i)
+#pragma unroll
+        for (int j = 0; j < AJ; ++j)
+#pragma unroll
+          for (int e = 0; e < 16; ++e) acc[i][j][e] = fast_tanh(alpha * acc[i][j][e]);
       epilogue_swap<TL, EPI, EPI_ROWS, true>(P, acc, lds, o32, alpha, m0, n0, tid, lane, wave, det_of(batch, prob));
     } else {
       epilogue_swap<TL, EPI, EPI_ROWS>(P, acc, lds, o32, alpha, m0, n0, tid, lane, wave, det_of(batch, prob));
@@ -733,7 +741,7 @@ static bool use_big(const GemmBatch& b) {
     const GemmProblem& P = b.p[g];
     if (P.M < TileL::BM || P.N < TileL::BN) return false;
     if (P.K < g_big_kmin && !g_force_big_rt) big = false;
-    qkv2 = qkv2 || P.qkv2_out != nullptr;
+    qkv2 = qkv2 || P.qkv2_out != nullptr || P.qkv2_h1_only;
     tiles += ((P.M + 255) / 256) * ((P.N + 255) / 256);
   }
   if (big) return true;
@@ -747,7 +755,8 @@ static bool use_big(const GemmBatch& b) {
 // the fused per-head Q/K/V stage 2 (qkv2_fused): forward tanh epilogue only, hh 16 or 32, 16-B stores,
 // whole hh-blocks (N % hh == 0)
 static bool qkv2_ok(const GemmProblem& P, int epi, bool fwd) {
-  if (!P.qkv2_out) return true;
+  // (h1 only: the fused launch's accumulator start and activation without stage 2, same kernel)
+  if (!P.qkv2_out) return !P.qkv2_h1_only || (epi == EPI_BIAS_TANH_BF16 && fwd && !P.alpha_ptr && P.alpha != 0.0f);
   // (no alpha_ptr, alpha != 0: the accumulators start at bias / alpha)
   return epi == EPI_BIAS_TANH_BF16 && fwd && (P.qkv2_hh == 16 || P.qkv2_hh == 32) && P.N % P.qkv2_hh == 0 &&
          !P.alpha_ptr && P.alpha != 0.0f &&
@@ -825,7 +834,7 @@ static hipError_t launch_gemm_any(const GemmBatch& b, bool a_kc, bool b_kc, int 
   }
   const bool big = use_big(b);
   for (int g = 0; g < b.count; ++g)
-    if (big && b.p[g].qkv2_out) return hipErrorInvalidValue;  // fused stage 2: 128 x 128 tile only
+    if (big && (b.p[g].qkv2_out || b.p[g].qkv2_h1_only)) return hipErrorInvalidValue;  // fused stage 2: 128 x 128 tile only
   if (a_kc && b_kc) {
     switch (epi) {
       case EPI_STORE_BF16: return launch_t<true, true, true, EPI_STORE_BF16>(b, 1, big, s);
@@ -1085,7 +1094,7 @@ hipError_t mmt_launch_gemm_f8(const GemmBatch& b, int epi, hipStream_t s) {
         (P.lds_b & 3) || (((uintptr_t)P.sa | (uintptr_t)P.sb) & 3) || P.lds_a * 32 < P.K || P.lds_b * 32 < P.K)
       return hipErrorInvalidValue;
     if (P.o8 && ((P.N & 31) || (P.ld8 & 7) || ((uintptr_t)P.o8 & 7))) return hipErrorInvalidValue;
-    if (P.qkv2_out) return hipErrorInvalidValue;  // (no fused Q/K/V stage 2 on the fp8 kernel)
+    if (P.qkv2_out || P.qkv2_h1_only) return hipErrorInvalidValue;  // (no fused Q/K/V stage 2 on the fp8 kernel)
   }
   switch (epi) {
     case EPI_STORE_BF16: return launch_f8_tile<EPI_STORE_BF16>(b, s);

@@ -90,6 +90,11 @@ struct GemmProblem {
   const float* qkv2_w2;
   bf16_t* qkv2_out;
   int qkv2_ld, qkv2_hh;
+  // qkv2_h1_only (with null qkv2_out, on a launch that could take the fused stage 2): h1 exactly as that fused
+  // launch stores it -- the accumulators start at bias / alpha and the activation is tanh(alpha acc), where the
+  // plain epilogue computes tanh(alpha acc + bias) and rounds differently -- without stage 2 and its store
+  // (the attention kernels then make Q / K / V from h1: AttnProblem::oc_*)
+  int qkv2_h1_only;
   // ReLU masks as bits (round 5): EPI_BIAS_RELU_BF16 also writes mask8[m * ldm8 + n / 8] bit n % 8 =
   // (stored bf16 output > 0); EPI_DRELU_BF16 with mask8 set (aux null) reads those bits instead of
   // the bf16 aux rows (16x fewer bytes). SWAP epilogues only; null: off
@@ -243,6 +248,15 @@ struct AttnProblem {
   // r + 32u): key-major words at dmask[j] + 32 t (dword 2e + u, bit r: the dK/dV pass, keys on
   // lanes) and lane words at dmask[j] + 32 (ntiles + t) (16 bits per lane, bit e: forward and dQ)
   uint32_t* dmask[MMT_MAX_STREAMS];
+  // optional (one KV stream, hs 32, T <= 256): Q / K / V made on chip. When oc_w2 is set the forward
+  // (attn_fwd_kernel) and the one-pass backward (which then also needs the q2_* fields above) do not read q / k / v:
+  // each workgroup computes its (batch, head)'s rows X[r][o] = bf16(sum_i bf16(W2[blk][o][i]) h1[r][blk*16 + i])
+  // from the stage-1 rows oc_h1 (row stride oc_ld, a multiple of 8; 16-B aligned) and the head's three W2
+  // blocks (fp32 [3 H][32][16], 16-B aligned), blk = kind * H + head with kinds K, Q, V: the same MFMA, operands
+  // and rounding as the stage-1 GEMM's fused epilogue (GemmProblem::qkv2_out), so the same bits. The launch
+  // refuses (hipErrorInvalidValue) a batch it cannot run this way.
+  const bf16_t* oc_h1; int oc_ld;
+  const float* oc_w2;
 };
 // tiles of one stream's mask, and its dwords (both records; see AttnProblem::dmask)
 inline int64_t mmt_attn_mask_tiles(int B, int H, int T) {
@@ -269,6 +283,9 @@ hipError_t mmt_attn_bwd_dkdv_ring64(const AttnBatch& b, int B, int T, int H, flo
 // hs 64 dQ pass (and D_j) streaming the key slices through an LDS-DMA ring (mmt_attn2.hip)
 hipError_t mmt_attn_bwd_dq_ring64(const AttnBatch& b, int B, int T, int H, float scale, bool drop, hipStream_t s);
 hipError_t mmt_attn_fwd_ring64(const AttnBatch& b, int B, int T, int H, float scale, bool drop, hipStream_t s);
+// hs 32, T <= 256, one KV stream, Q / K / V made on chip (AttnProblem::oc_* set and checked by the caller,
+// mmt_launch_attn_fwd; mmt_attn_oc.hip)
+hipError_t mmt_attn_fwd_oc32(const AttnBatch& b, int B, int T, int H, float scale, bool drop, hipStream_t s);
 // hs 64, T <= 512, one KV stream: dQ, dK, dV in one pass, one workgroup per (batch, head) (mmt_attn2.hip)
 hipError_t mmt_attn_bwd_fused64(const AttnBatch& b, int B, int T, int H, float scale, bool drop, hipStream_t s);
 // fill dmask[j] (j < nstreams) of every problem with drop_thr != 0 from its counter hash

@@ -192,6 +192,37 @@ int mmt_op_attention_bwd_ws(void* stream, int32_t B, int32_t T, int32_t H, int32
   return e == hipErrorInvalidValue ? MMT_ERR_UNSUPPORTED : st(e);
 }
 
+// hs-32 self-attention with Q / K / V made on chip from the stage-1 rows (AttnProblem::oc_*)
+int mmt_op_attention_fwd_h1(void* stream, int32_t B, int32_t T, int32_t H, const void* h1, int32_t ld_h1, const float* w2,
+                            void* o, int32_t o_ld, float* lse) {
+  if (!h1 || !w2 || !o || !lse) return MMT_ERR_INVALID;
+  AttnBatch b{};
+  b.count = 1;
+  AttnProblem& p = b.p[0];
+  p.nstreams = 1;
+  p.oc_h1 = (const bf16_t*)h1; p.oc_ld = ld_h1; p.oc_w2 = w2;
+  p.o = (bf16_t*)o; p.o_ld = o_ld; p.lse[0] = lse;
+  const hipError_t e = mmt_launch_attn_fwd(b, B, T, H, 32, 1.0f / __builtin_sqrtf(32.f), (hipStream_t)stream);
+  return e == hipErrorInvalidValue ? MMT_ERR_UNSUPPORTED : st(e);
+}
+
+int mmt_op_attention_bwd_h1(void* stream, int32_t B, int32_t T, int32_t H, const void* h1, int32_t ld_h1, const float* w2,
+                            const void* o, int32_t o_ld, const float* lse, const void* dout, int32_t dout_ld, void* dh1,
+                            float* dw2, float* db1) {
+  if (!h1 || !w2 || !o || !lse || !dout || !dh1 || !dw2 || !db1) return MMT_ERR_INVALID;
+  AttnBatch b{};
+  b.count = 1;
+  AttnProblem& p = b.p[0];
+  p.nstreams = 1;
+  p.oc_h1 = (const bf16_t*)h1; p.oc_ld = ld_h1; p.oc_w2 = w2;
+  p.q2_h1 = (const bf16_t*)h1; p.q2_ld = ld_h1; p.q2_w2 = w2;
+  p.q2_dh1 = (bf16_t*)dh1; p.q2_dw2 = dw2; p.q2_db1 = db1;
+  p.o = (bf16_t*)o; p.o_ld = o_ld; p.lse[0] = (float*)lse;
+  p.dout = (const bf16_t*)dout; p.dout_ld = dout_ld;
+  const hipError_t e = mmt_launch_attn_bwd(b, B, T, H, 32, 1.0f / __builtin_sqrtf(32.f), (hipStream_t)stream);
+  return e == hipErrorInvalidValue ? MMT_ERR_UNSUPPORTED : st(e);
+}
+
 int mmt_op_qkv2_fwd(void* stream, int32_t R, int32_t nblk, int32_t hs, const void* h1, int32_t ld_h1, const float* w2,
                     void* out, int32_t ld_out) {
   Qkv2Batch b{};

@@ -41,6 +41,7 @@ __global__ __launch_bounds__(256) void qkv2_fwd_mfma(Qkv2Batch batch, int R, int
   constexpr int SHW = KS * 16 + 8;     // h1 tile row (zero padded to the k-steps; +8 de-conflicts)
   constexpr int SOW = HS + 8;          // out tile row
   constexpr int BR = 128 * qkv2_strips(HS);
+  constexpr bool PERM = HS == 32;  // operands in the fused epilogue's K-slot order (see wa below)
   const Qkv2Problem& P = batch.p[blockIdx.z];
   // grid.x = row blocks x nblk, blk fastest in logical order (one row's blocks share its lines)
   const int tile = xcd_tile(blockIdx.x, gridDim.x);
@@ -77,7 +78,12 @@ __global__ __launch_bounds__(256) void qkv2_fwd_mfma(Qkv2Batch batch, int R, int
     for (int s = 0; s < KS; ++s)
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        const int o = ot * 32 + r, i = 16 * s + 8 * h + j;
+        // hs 32: the K-slot order of the stage-1 GEMM's fused epilogue (qkv2_fused: slot j <-> i = 4 h + j for
+        // j < 4, 8 + 4 h + j - 4 for j >= 4), so this kernel, that epilogue and the on-chip attention kernels
+        // (oc_tile) store the same bits for the same h1 and W2: the MFMA's sum depends on the slot order in its
+        // last bit (the natural order differed from the epilogue in about 5 entries per million). Decode rows
+        // made here now match the prefill's rows made by the epilogue.
+        const int o = ot * 32 + r, i = PERM ? (j < 4 ? 4 * h + j : 8 + 4 * h + j - 4) : 16 * s + 8 * h + j;
         wa[ot][s][j] = (__bf16)((o < HS && i < HH) ? w2[o * HH + i] : 0.f);
       }
   const int lr = w * 32;
@@ -99,7 +105,14 @@ __global__ __launch_bounds__(256) void qkv2_fwd_mfma(Qkv2Batch batch, int R, int
       for (int e = 0; e < 16; ++e) acc[e] = 0.f;
 #pragma unroll
       for (int s = 0; s < KS; ++s) {
-        const bf16x8 hb = *reinterpret_cast<const bf16x8*>(sh + (lr + r) * SHW + 16 * s + 8 * h);
+        bf16x8 hb;
+        if (PERM) {  // columns 4 h .. + 3 and 8 + 4 h .. + 3
+          const u32x2 lo = *reinterpret_cast<const u32x2*>(sh + (lr + r) * SHW + 4 * h);
+          const u32x2 hi = *reinterpret_cast<const u32x2*>(sh + (lr + r) * SHW + 8 + 4 * h);
+          hb = __builtin_bit_cast(bf16x8, u32x4{lo[0], lo[1], hi[0], hi[1]});
+        } else {
+          hb = *reinterpret_cast<const bf16x8*>(sh + (lr + r) * SHW + 16 * s + 8 * h);
+        }
         acc = mfma32(wa[ot][s], hb, acc);  // D[o][row]
       }
       // lane owns row (r) and o = ot*32 + (e&3) + 8(e>>2) + 4h

@@ -16,7 +16,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "build")
 LIB = os.path.join(HERE, "libmmt_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-SOURCES = ["mmt_gemm.hip", "mmt_gemm8.hip", "mmt_mlp2.hip", "mmt_attn.hip", "mmt_attn2.hip", "mmt_elem.hip", "mmt_stats.hip", "mmt_qkv2.hip", "mmt_engine.hip", "mmt_ops.hip", "mmt_batch.hip", "mmt_decode.hip"]
+SOURCES = ["mmt_gemm.hip", "mmt_gemm8.hip", "mmt_mlp2.hip", "mmt_attn.hip", "mmt_attn_oc.hip", "mmt_attn2.hip", "mmt_elem.hip", "mmt_stats.hip", "mmt_qkv2.hip", "mmt_engine.hip", "mmt_ops.hip", "mmt_batch.hip", "mmt_decode.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I" + os.path.join(REPO, "include"), "-I" + CSRC,
          "-Wall", "-Wno-unused-function", "-Wno-unused-variable", "-Wno-unused-result"]
 
@@ -27,7 +27,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I" + os.path.j
 # 16 in the qkv2 backward): 213 -> 182 instructions per dK/dV tile, no spills, occupancy equal or higher.
 # Not for mmt_attn2.hip (the one-pass kernel needs 512 registers at one wave) or the GEMM files.
 VGPR_FORM = ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]
-FILE_FLAGS = {"mmt_attn.hip": ["-fno-slp-vectorize"] + VGPR_FORM, "mmt_attn2.hip": ["-fno-slp-vectorize"],
+FILE_FLAGS = {"mmt_attn.hip": ["-fno-slp-vectorize"] + VGPR_FORM, "mmt_attn_oc.hip": ["-fno-slp-vectorize"] + VGPR_FORM,
+              "mmt_attn2.hip": ["-fno-slp-vectorize"],
               "mmt_qkv2.hip": VGPR_FORM}
 
 

@@ -149,6 +149,7 @@ _SIGS = {
     "mmt_set_relu_bits": (c_i32, [ctypes.c_int]),
     "mmt_set_drop_copy_fuse": (c_i32, [ctypes.c_int]),
     "mmt_set_attn_qkv2": (c_i32, [ctypes.c_int]),
+    "mmt_set_attn_qkv_onchip": (c_i32, [ctypes.c_int]),
     "mmt_mlp2_set_bm": (c_i32, [ctypes.c_int]),
     "mmt_qkv2_set_coal": (c_i32, [ctypes.c_int]),
     "mmt_gemm_set_variant": (c_i32, [ctypes.c_int]),
@@ -176,6 +177,9 @@ _SIGS = {
                                         ctypes.POINTER(c_vp), c_i32, c_i32, c_vp, c_i32, ctypes.POINTER(c_vp),
                                         ctypes.POINTER(c_vp), c_vp, c_i32, ctypes.POINTER(c_vp), c_vp, c_i32,
                                         ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_i32, c_i32, c_vp, c_i32]),
+    "mmt_op_attention_fwd_h1": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp]),
+    "mmt_op_attention_bwd_h1": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32,
+                                        c_vp, c_vp, c_vp]),
     "mmt_op_qkv2_fwd": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_i32]),
     "mmt_op_qkv2_bwd": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp]),
     "mmt_op_colsum": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_f32]),
