@@ -378,6 +378,23 @@ int mmt_op_mlp2(void* stream, int32_t M, int32_t C, const void* x, int32_t ldx, 
 int mmt_op_mlp2_bwd(void* stream, int32_t M, int32_t C, const void* dy, int32_t lddy, const void* w2, int32_t ldw2,
                     const void* h, int32_t ldh, float alpha, const void* w0, int32_t ldw0, void* dh, int32_t lddh,
                     float* db0, void* dx);
+/* the FFN forward as ONE launch (the engine's forward path at C = 256, mmt_set_ffn_fused; replaces the pair
+ * mmt_op_gemm(bias_relu_bf16) + mmt_op_gemm(bias_resid_f32) and gives its bits, reference model.py:162-175, 225),
+ * for `count` (1..4) problems that share the weights, problem g with M[g] rows:
+ *   h[g][M, 4C] = bf16(relu(x[g][M, C] W0[4C, C]^T + b0))        (stored: the backward reads it)
+ *   out[g][M, C] = resid[g] + keep(m, n) * (h W2[C, 4C]^T + b2)   (fp32; hash dropout of drop_key / drop_thr,
+ *                  kept values times drop_scale, 0: off), out16[g] (array or entries nullable) its bf16 copy;
+ *   lnf_y[g] (array nullable) = bf16(LayerNorm(out) * lnf_gamma + lnf_beta), lnf_mean[g] / lnf_rstd[g] its
+ *   row statistics (all of lnf_* or none)
+ * with h walked through LDS in 128-column chunks and never read back. x, h, resid, out, out16, lnf_y, lnf_mean,
+ * lnf_rstd are host arrays of `count` device pointers. C must be 256 (else MMT_ERR_UNSUPPORTED; so are
+ * misaligned pointers or strides); row strides ldx, ldw0 (W0), ldw2 (W2), ldh (h); out / resid / out16 /
+ * lnf_y have stride C. */
+int mmt_op_ffn(void* stream, int32_t count, const int32_t* M, int32_t C, const void* const* x, int32_t ldx,
+               const void* w0, int32_t ldw0, const float* b0, const void* w2, int32_t ldw2, const float* b2,
+               void* const* h, int32_t ldh, const float* const* resid, float* const* out, void* const* out16,
+               uint32_t drop_key, uint32_t drop_thr, float drop_scale, const float* lnf_gamma, const float* lnf_beta,
+               void* const* lnf_y, float* const* lnf_mean, float* const* lnf_rstd);
 int mmt_op_layernorm_fwd(void* stream, int32_t R, int32_t C, const float* x, const float* gamma, const float* beta,
                          void* y16, float* mean, float* rstd);
 int mmt_op_layernorm_bwd(void* stream, int32_t R, int32_t C, const float* x, const float* gamma, const float* mean,
@@ -479,6 +496,12 @@ int mmt_set_attn_qkv_onchip(int bits);
 // 128 (8 waves, one workgroup per CU) or 64 (4 waves, three per CU); default 128 (env MMT_MLP2_BM);
 // returns the previous value (tests, A/B)
 int mmt_mlp2_set_bm(int bm);
+// the FFN forward at C = 256, bf16, ReLU bits off (training and eval forwards; decode keeps its own GEMMs):
+// 1 (default, env MMT_FFN_FUSED) = one launch per layer (ffn_fwd_kernel: the hidden activation walks through
+// LDS, is stored for the backward and never read back), 0 = the ffn0 + ffn2 GEMM pair. Both give the same bits
+// where ffn2 runs with its fused LayerNorm on the ping-pong kernel (the default). Read at every forward; returns
+// the previous value (tests, A/B)
+int mmt_set_ffn_fused(int on);
 
 /* ---- MX-fp8 primitives (C4's fp8 path; BASELINE configs[4]) --------------------------------
  * MX-fp8 = OCP e4m3fn bytes + one E8M0 exponent byte (bias 127) per 32 consecutive K elements of a

@@ -144,6 +144,13 @@ extern "C" int mmt_set_attn_qkv2(int on) {
 // hs 32 self-attention at T <= 256 in training forwards: Q / K / V made on chip from h1 and W2 (AttnProblem::oc_*)
 // by the forward (bit 0) and by the one-pass backward (bit 1); with both bits the stage-1 GEMM drops its stage-2
 // epilogue and the Q/K/V rows are never written (env MMT_ATTN_QKV_ONCHIP). Latched by mmt_forward.
+// the FFN forward as one launch at C = 256 (include/mmt.h: mmt_set_ffn_fused)
+static int g_ffn_fused = mmt_env_int("MMT_FFN_FUSED", 1);
+extern "C" int mmt_set_ffn_fused(int on) {
+  const int old = g_ffn_fused;
+  g_ffn_fused = on;
+  return old;
+}
 static int g_attn_qkv_onchip = mmt_env_int("MMT_ATTN_QKV_ONCHIP", 3) & 3;
 extern "C" int mmt_set_attn_qkv_onchip(int bits) {
   const int old = g_attn_qkv_onchip;
@@ -869,6 +876,35 @@ struct Runner {
     }
     return true;
   }
+  // the FFN forward Linear(C, 4C) -> ReLU -> Linear(4C, C) + dropout + residual (+ the next LayerNorm) as one
+  // launch (mmt_launch_ffn: the hidden activation is stored for the backward but never read back); g1s the
+  // ffn0 problems, g2s the ffn2 problems. false (nothing launched) when the shape is outside the kernel
+  bool ffn(const GemmProblem* g1s, const GemmProblem* g2s, int n, const char* what) {
+    if (rc != MMT_OK || n < 1) return false;
+    Mlp2Batch chunk[(MMT_MAX_GROUP + MMT_MLP2_GROUP - 1) / MMT_MLP2_GROUP] = {};
+    const int nch = (n + MMT_MLP2_GROUP - 1) / MMT_MLP2_GROUP;
+    for (int i = 0; i < n; ++i) {
+      Mlp2Batch& b = chunk[i / MMT_MLP2_GROUP];
+      b.g1[b.count] = g1s[i];
+      b.g2[b.count] = g2s[i];
+      ++b.count;
+    }
+    for (int k = 0; k < nch; ++k)
+      if (!mmt_ffn_ok(chunk[k])) return false;
+    const int id = probe_begin(what, s);
+    for (int k = 0; k < nch; ++k) ok(mmt_launch_ffn(chunk[k], s), what);
+    if (id >= 0) {
+      double fl = 0, by = 0;
+      GemmBatch g1{}, g2{};
+      g1.count = g2.count = n;
+      for (int g = 0; g < n; ++g) { g1.p[g] = g1s[g]; g2.p[g] = g2s[g]; }
+      gemm_cost(g1, EPI_BIAS_RELU_BF16, &fl, &by);
+      gemm_cost(g2, EPI_BIAS_RESID_F32, &fl, &by);
+      for (int g = 0; g < n; ++g) by -= (double)g2s[g].M * g2s[g].K * 2.0;  // h is not read back
+      probe_end(id, s, fl, by);
+    }
+    return true;
+  }
   // forward residual GEMM with the next LayerNorm's forward fused (mmt_launch_gemm_resid_ln)
   bool gemm_resid_ln(const GemmBatch& b, const char* what) {
     if (rc != MMT_OK || !mmt_gemm_resid_ln_ok(b)) return false;
@@ -1214,8 +1250,11 @@ int run_forward(mmt_ctx* c, Runner& r, const int64_t* const* idx, const int64_t*
       if (r.c->relu_bits) { g.p[i].mask8 = r.W<uint8_t>(a[i].fm); g.p[i].ldm8 = 4 * C / 8; }
       if (f8) { g.p[i].o8 = r.W<uint8_t>(a[i].f8); g.p[i].ld8 = 4 * C; g.p[i].s8 = r.W<uint8_t>(a[i].fs8); g.p[i].lds8 = ldsF; }
     }
-    if (f8) r.gemm8(g, EPI_BIAS_RELU_BF16, "ffn0");
-    else r.gemm(g, true, true, EPI_BIAS_RELU_BF16, 1, "ffn0");
+    const GemmBatch gf0 = g;  // the ffn0 problems: launched below, alone or inside the one-launch FFN
+    auto run_ffn0 = [&] {
+      if (f8) r.gemm8(gf0, EPI_BIAS_RELU_BF16, "ffn0");
+      else r.gemm(gf0, true, true, EPI_BIAS_RELU_BF16, 1, "ffn0");
+    };
     for (int i = 0; i < M; ++i) g.p[i].mask8 = nullptr;  // g is reused
     for (int i = 0; i < M; ++i) {
       g.p[i] = f8 ? gp_f8(r.W<uint8_t>(a[i].f8), 4 * C, r.W<uint8_t>(a[i].fs8), ldsF, w8, x[i].F2, R)
@@ -1244,7 +1283,13 @@ int run_forward(mmt_ctx* c, Runner& r, const int64_t* const* idx, const int64_t*
           q.lnf_mean = r.W<float>(p.meanf[i]); q.lnf_rstd = r.W<float>(p.rstdf[i]);
         }
       }
-      if (r.gemm_resid_ln(g, "ffn2")) {
+    }
+    // both products as one launch (mmt_set_ffn_fused; C = 256, bf16, no ReLU bits: ffn_fwd_kernel, the bits of
+    // the pair below); false (nothing launched) for every other shape or a field it does not implement
+    const bool ffn_one = !f8 && !c->relu_bits && C == 256 && g_ffn_fused != 0 && r.ffn(gf0.p, g.p, M, "ffn");
+    if (!ffn_one) run_ffn0();
+    if (fuse_fwd) {
+      if (ffn_one || r.gemm_resid_ln(g, "ffn2")) {
         for (int i = 0; i < M; ++i) {
           if (c->any_cross && x[i].cross) lnc_done = true;
           else if (l + 1 < c->L) ln1_done[i] = 1;
@@ -1254,10 +1299,9 @@ int run_forward(mmt_ctx* c, Runner& r, const int64_t* const* idx, const int64_t*
         for (int i = 0; i < M; ++i) g.p[i].lnf_y = nullptr;
         r.gemm(g, true, true, EPI_BIAS_RESID_F32, 1, "ffn2");
       }
-    } else if (f8) {
-      r.gemm8(g, EPI_BIAS_RESID_F32, "ffn2");
-    } else {
-      r.gemm(g, true, true, EPI_BIAS_RESID_F32, 1, "ffn2");
+    } else if (!ffn_one) {
+      if (f8) r.gemm8(g, EPI_BIAS_RESID_F32, "ffn2");
+      else r.gemm(g, true, true, EPI_BIAS_RESID_F32, 1, "ffn2");
     }
     for (int i = 0; i < M; ++i) g.p[i].lnf_y = nullptr;  // g is reused: no stale LayerNorm outputs
     std::vector<const float*> xout(M);

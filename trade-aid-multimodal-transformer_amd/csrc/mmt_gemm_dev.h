@@ -252,6 +252,21 @@ __device__ __forceinline__ void stage_acc(f32x4 (&acc)[4][8], float* ct, int pas
       *reinterpret_cast<f32x4*>(ct + ml * CT + wc * 64 + 16 * nb + 4 * (lane >> 4)) = acc[nb][mb];
   }
 }
+// the same MFMA on a 128 x 256 tile (ffn_fwd_kernel's stage 2, 8 waves 2 (m) x 4 (n) of 64 x 64): acc[nb][mb]
+template <class TL, int EPI_ROWS>
+__device__ __forceinline__ void stage_acc(f32x4 (&acc)[4][4], float* ct, int pass, int lane, int wave) {
+  constexpr int CT = TL::BN + 4;
+  const int wr = wave >> 2, wc = wave & 3;
+#pragma unroll
+  for (int mb = 0; mb < 4; ++mb) {
+    const int mf = wr * 64 + 16 * mb;
+    if (mf / EPI_ROWS != pass) continue;
+    const int ml = mf - pass * EPI_ROWS + (lane & 15);
+#pragma unroll
+    for (int nb = 0; nb < 4; ++nb)
+      *reinterpret_cast<f32x4*>(ct + ml * CT + wc * 64 + 16 * nb + 4 * (lane >> 4)) = acc[nb][mb];
+  }
+}
 
 template <class TL, int EPI, int EPI_ROWS, bool PRE = false, class ACC>
 __device__ __forceinline__ void epilogue_swap(const GemmProblem& P, ACC& acc, char* lds,

@@ -156,6 +156,16 @@ hipError_t mmt_launch_mlp2(const Mlp2Batch& b, hipStream_t s);
 // weight gradient
 bool mmt_mlp2_bwd_ok(const Mlp2Batch& b);
 hipError_t mmt_launch_mlp2_bwd(const Mlp2Batch& b, hipStream_t s);
+// One-launch FFN forward at C = 256 (round 8; model.py:162-175, 225; mmt_ffn.hip): per problem
+//   h   = relu(A W0^T + b0)            (g1: the ffn0 problem: A [M][256] bf16, B = W0 [1024][256], bias b0, o16 = h out)
+//   out = epilogue(h W2^T + b2)        (g2: the ffn2 problem: A = g1.o16, B = W2 [256][1024], bias b2, the
+//                                        EPI_BIAS_RESID_F32 fields: resid, o32, optional o16 / dropout / lnf_*)
+// with h walked through LDS in 128-column chunks (stored to g1.o16 for the backward, never read back), giving
+// the bits of mmt_launch_gemm (ffn0) + mmt_launch_gemm_resid_ln (ffn2, ping-pong kernel). bf16 only, alpha 1, no
+// ReLU bits / fp8 copies; mmt_ffn_ok false or hipErrorInvalidValue otherwise (nothing launched: the caller
+// runs the two GEMMs). At most MMT_MLP2_GROUP problems per launch.
+bool mmt_ffn_ok(const Mlp2Batch& b);
+hipError_t mmt_launch_ffn(const Mlp2Batch& b, hipStream_t s);
 // forward linear Y = X W^T on MX-fp8 operands (A = X [M][K], B = W [N][K], both K-contiguous e4m3fn
 // with E8M0 exponents per 32 K elements; K % 32 == 0) via v_mfma_scale_f32_32x32x64_f8f6f4, any
 // of the bf16 GEMM's forward epilogues; fp32 accumulation

@@ -75,6 +75,34 @@ int mmt_op_mlp2(void* stream, int32_t M, int32_t C, const void* x, int32_t ldx, 
   return st(mmt_launch_mlp2(b, (hipStream_t)stream));
 }
 
+// the FFN forward (reference model.py:162-175, 225) as one launch of `count` problems that share the weights
+int mmt_op_ffn(void* stream, int32_t count, const int32_t* M, int32_t C, const void* const* x, int32_t ldx,
+               const void* w0, int32_t ldw0, const float* b0, const void* w2, int32_t ldw2, const float* b2,
+               void* const* h, int32_t ldh, const float* const* resid, float* const* out, void* const* out16,
+               uint32_t drop_key, uint32_t drop_thr, float drop_scale, const float* lnf_gamma, const float* lnf_beta,
+               void* const* lnf_y, float* const* lnf_mean, float* const* lnf_rstd) {
+  if (count < 1 || !M || !x || !h || !resid || !out || C < 2) return MMT_ERR_INVALID;
+  if (count > MMT_MLP2_GROUP || C != 256) return MMT_ERR_UNSUPPORTED;
+  Mlp2Batch b{};
+  b.count = count;
+  for (int g = 0; g < count; ++g) {
+    if (M[g] < 1) return MMT_ERR_INVALID;
+    GemmProblem& p1 = b.g1[g];
+    p1.A = (const bf16_t*)x[g]; p1.lda = ldx; p1.B = (const bf16_t*)w0; p1.ldb = ldw0; p1.bias = b0;
+    p1.o16 = (bf16_t*)h[g]; p1.ldo16 = ldh; p1.alpha = 1.f; p1.M = M[g]; p1.N = 4 * C; p1.K = C;
+    GemmProblem& p2 = b.g2[g];
+    p2.A = (const bf16_t*)h[g]; p2.lda = ldh; p2.B = (const bf16_t*)w2; p2.ldb = ldw2; p2.bias = b2;
+    p2.resid = resid[g]; p2.ldres = C; p2.o32 = out[g]; p2.ldc = C;
+    p2.o16 = out16 ? (bf16_t*)out16[g] : nullptr; p2.ldo16 = C;
+    p2.alpha = 1.f; p2.M = M[g]; p2.N = C; p2.K = 4 * C;
+    p2.drop_key = drop_key; p2.drop_thr = drop_thr; p2.drop_scale = drop_scale;
+    p2.lnf_gamma = lnf_gamma; p2.lnf_beta = lnf_beta; p2.lnf_y = lnf_y ? (bf16_t*)lnf_y[g] : nullptr;
+    p2.lnf_mean = lnf_mean ? lnf_mean[g] : nullptr; p2.lnf_rstd = lnf_rstd ? lnf_rstd[g] : nullptr;
+  }
+  if (!mmt_ffn_ok(b)) return MMT_ERR_UNSUPPORTED;
+  return st(mmt_launch_ffn(b, (hipStream_t)stream));
+}
+
 int mmt_op_mlp2_bwd(void* stream, int32_t M, int32_t C, const void* dy, int32_t lddy, const void* w2, int32_t ldw2,
                     const void* h, int32_t ldh, float alpha, const void* w0, int32_t ldw0, void* dh, int32_t lddh,
                     float* db0, void* dx) {

@@ -151,6 +151,7 @@ _SIGS = {
     "mmt_set_attn_qkv2": (c_i32, [ctypes.c_int]),
     "mmt_set_attn_qkv_onchip": (c_i32, [ctypes.c_int]),
     "mmt_mlp2_set_bm": (c_i32, [ctypes.c_int]),
+    "mmt_set_ffn_fused": (c_i32, [ctypes.c_int]),
     "mmt_qkv2_set_coal": (c_i32, [ctypes.c_int]),
     "mmt_gemm_set_variant": (c_i32, [ctypes.c_int]),
     "mmt_op_gemm": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_i32, c_vp,
@@ -162,6 +163,10 @@ _SIGS = {
                                    c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_uint32, ctypes.c_uint32, c_f32]),
     "mmt_op_mlp2": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp,
                             c_vp, c_vp, ctypes.c_uint32, ctypes.c_uint32, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "mmt_op_ffn": (c_i32, [c_vp, c_i32, ctypes.POINTER(c_i32), c_i32, ctypes.POINTER(c_vp), c_i32, c_vp, c_i32, c_vp,
+                           c_vp, c_i32, c_vp, ctypes.POINTER(c_vp), c_i32, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp),
+                           ctypes.POINTER(c_vp), ctypes.c_uint32, ctypes.c_uint32, c_f32, c_vp, c_vp,
+                           ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), ctypes.POINTER(c_vp)]),
     "mmt_op_mlp2_bwd": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_f32, c_vp, c_i32, c_vp,
                                 c_i32, c_vp, c_vp]),
     "mmt_op_layernorm_fwd": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
