@@ -18,6 +18,8 @@
  *   mmt_adamw_step                <- torch.optim.AdamW(m.parameters(), lr).step() (main.py:464, 650)
  *   mmt_decode_step               <- one token of MultimodalTransformer.generate (model.py:404-446),
  *                                    with a KV cache instead of the reference's full re-forward
+ *   mmt_sample                    <- the sampling line of generate (model.py:425-427: softmax + multinomial),
+ *                                    extended by temperature, top-k, top-p, seeded draws and log-probabilities
  *   mmt_eval_direction            <- the per-sample loop of calculate_evaluation_metrics
  *                                    (training_utils.py:259-304)
  *   mmt_op_*                      primitive kernels, exported for kernel-level parity tests.
@@ -96,6 +98,45 @@ int mmt_forward(mmt_ctx* ctx, void* stream, int32_t batch, const int64_t* const*
  * and at precision fp8 (the prefill's MX-fp8 GEMMs would not match a bf16 decode). */
 int mmt_decode_step(mmt_ctx* ctx, void* stream, int32_t batch, int32_t pos, const int64_t* const* idx,
                     const float* params, float* const* logits, void* workspace);
+
+/* Device-side sampling of generate (reference model.py:425-427: softmax of the last logits, torch.multinomial,
+ * nothing else): one token per row from fp32 logits with temperature, top-k and top-p, a draw keyed by
+ * (seed, row, position), and the log-probability of the token, in ONE launch for all rows (one 256-thread
+ * workgroup per row). Needs no context: any fp32 buffer. Row b is read at logits + b * row_stride (elements,
+ * row_stride >= V), so the last position of a prefill's [B, T, V] tensor is read in place (pointer offset
+ * (n - 1) * V, stride T * V) as well as a decode step's [B, V]. The rule, per row:
+ *   1. z_i = logits_i * (1 / temperature): 1 / temperature is one fp32 division on the host, the product one
+ *      fp32 multiply; a NaN z counts as -inf. m = max z.
+ *   2. top-k (0 < top_k < V; 0 = off): t_k = the top_k-th largest z, duplicates counted; kept = { i : z_i >= t_k }
+ *      (ties at the threshold are all kept; comparisons only, exact).
+ *   3. e_i = exp(z_i - m) on the kept set (1 where z_i == m), 0 elsewhere; S = sum e_i.
+ *   4. top-p (top_p < 1; >= 1 = off): over the distinct kept values of z in descending order, t_p = the first at
+ *      which the mass of { z_i >= t_p } reaches top_p * S; kept = { z_i >= t_p } (ties kept), S recomputed.
+ *      top_p <= 0 keeps the maximal group only.
+ *   5. key = mmt_hash(lo32(seed), hi32(seed), 0x53414D50); h = mmt_hash(key, row0 + b, pos);
+ *      u = ((h >> 8) + 0.5) * 2^-24, with mmt_hash the dropout masks' counter hash
+ *      (h = a * 0x9E3779B1 ^ (b + 0x7F4A7C15) * 0x85EBCA77 ^ (c + 0x165667B1) * 0xC2B2AE3D; h ^= h >> 16;
+ *      h *= 0x7FEB352D; h ^= h >> 15; h *= 0x846CA68B; h ^= h >> 16, all modulo 2^32).
+ *   6. the token is the first index in vocabulary order whose inclusive prefix sum of e reaches u * S; it always
+ *      has e > 0.
+ *   7. the log-probability is log(e_tok / S), fp32, under the distribution actually sampled from (computed as
+ *      (z_tok - m) - log S).
+ * temperature == 0 is greedy: the lowest index among the maxima of the raw logits (NaN as -inf), top_k and top_p
+ * ignored, the log-probability the raw log-softmax at that token. A row with no finite logit (every entry -inf or
+ * NaN) gives token 0 and log-probability NaN; no kernel traps.
+ * Outputs: the token as int64 at tok + b * tok_stride (column n of a [B, cap] sequence buffer is written in
+ * place); if tok_compact != NULL also at tok_compact[b] (what mmt_decode_step takes as idx[g] of the next
+ * position); if logprob != NULL the log-probability at logprob + b * lp_stride.
+ * The weights e are fp32 (expf), their sums fp64 over a fixed assignment and a fixed tree (no float atomics): a
+ * launch is bit-identical run to run,
+ * and row b of a launch equals the same row launched alone with row0 + b as its row0. Rows up to V = 8192 stay in
+ * LDS; larger ones (to V = 2^20, above that MMT_ERR_UNSUPPORTED) are re-read from memory.
+ * MMT_ERR_INVALID before any launch for: batch < 0, V < 1, row_stride < V, temperature negative or NaN,
+ * top_k < 0, top_p NaN, a null logits / tok with batch > 0. batch == 0 launches nothing. */
+int mmt_sample(void* stream, int32_t batch, int32_t V, const float* logits, int64_t row_stride, float temperature,
+               int32_t top_k, float top_p, uint64_t seed, uint32_t row0, uint32_t pos, int64_t* tok,
+               int64_t tok_stride, int64_t* tok_compact /* nullable */, float* logprob /* nullable */,
+               int64_t lp_stride);
 
 /* failure detection (the reference's guard is the NaN check on eval losses,
  * main.py:606): byte offset in the workspace of two int32 bitmasks (the same for every batch size;

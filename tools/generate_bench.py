@@ -1,0 +1,120 @@
+"""Tokens per second of `model.generate`: the default path (host loop: torch.softmax, torch.multinomial, a
+torch.cat per modality per token) and the device path (mmt_sample: temperature / top-k / top-p on the GPU, sequences
+in preallocated buffers, per token mmt_decode_step + mmt_sample and nothing else).
+
+C1 dimensions (d256, 8 heads, 6 layers, block 256, vocabularies 900 / 13 / 144 / 5, cross-attention on modality 0),
+B = 64, a 128-token prompt, 128 new tokens of modality 0, eval mode, freshly initialised weights. Each timed call is
+one generate with one synchronisation at its end; tokens per second counts B * new tokens.
+
+    python tools/generate_bench.py [--paths default,device] [--rounds 3] [--warmup 1] [--tree DIR] [--sampler]
+
+--tree DIR takes the package (and its built library) of another checkout of this repository, e.g. the parent
+commit, whose generate has the default path only (--paths default). --sampler adds the time of mmt_sample on its
+own per vocabulary size and setting. One JSON line per run.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+C1 = dict(n_embd=256, n_head=8, n_layer=6, block_size=256, V=[900, 13, 144, 5], cross=[True, False, False, False])
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--paths", default="default,device")
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--batch", type=int, default=64)
+    ap.add_argument("--prompt", type=int, default=128)
+    ap.add_argument("--new", type=int, default=128)
+    ap.add_argument("--tree", default=REPO)
+    ap.add_argument("--label", default="")
+    ap.add_argument("--sampler", action="store_true", help="also time mmt_sample alone (this tree only)")
+    a = ap.parse_args()
+    sys.path.insert(0, os.path.join(os.path.abspath(a.tree), "trade-aid-multimodal-transformer_amd"))
+    import torch
+    import config_utils
+    from model import MultimodalTransformer
+    dev = torch.device("cuda", 0)
+    config_utils._config_cache = {"n_embd": C1["n_embd"], "n_head": C1["n_head"], "n_layer": C1["n_layer"],
+                                  "block_size": C1["block_size"], "dropout": 0.0, "device": str(dev),
+                                  "batch_size": a.batch, "eval_iters": 1}
+    params = []
+    for c in C1["cross"]:
+        p = [None] * 12
+        p[8] = c
+        params.append(p)
+    torch.manual_seed(1234)
+    model = MultimodalTransformer(len(C1["V"]), C1["V"], params).to(dev)
+    model.eval()
+    g = torch.Generator().manual_seed(7)
+    prompt = [torch.randint(0, v, (a.batch, a.prompt), generator=g).to(dev) for v in C1["V"]]
+    calls = {
+        "default": lambda: model.generate(prompt, max_new_tokens=a.new, modality_to_generate=0),
+        "device": lambda: model.generate(prompt, max_new_tokens=a.new, modality_to_generate=0, temperature=1.0, seed=11),
+        "device_topk_topp": lambda: model.generate(prompt, max_new_tokens=a.new, modality_to_generate=0, temperature=0.8,
+                                                   top_k=50, top_p=0.9, seed=11),
+    }
+    paths = [p for p in a.paths.split(",") if p]
+    out = {p: [] for p in paths}
+    for p in paths:
+        for _ in range(a.warmup):
+            calls[p]()
+    torch.cuda.synchronize()
+    for _ in range(a.rounds):  # the paths alternate: each round brackets the others
+        for p in paths:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            seqs = calls[p]()
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            assert tuple(seqs[0].shape) == (a.batch, a.prompt + a.new)
+            out[p].append(round(a.batch * a.new / dt, 1))
+    res = {"tool": "generate_bench", "label": a.label, "device": torch.cuda.get_device_name(0),
+           "batch": a.batch, "prompt": a.prompt, "new_tokens": a.new,
+           "tokens_per_s": out, "best_tokens_per_s": {p: max(v) for p, v in out.items()}}
+    if a.sampler:
+        res["sampler_us"] = sampler_alone(torch, dev, a.batch, a.rounds)
+    print(json.dumps(res), flush=True)
+
+
+def sampler_alone(torch, dev, batch, rounds, reps=200):
+    """us per mmt_sample launch on its own (HIP events around `reps` back-to-back launches over rotating N(0, 3^2)
+    logits), per vocabulary size and setting."""
+    import mmt_lib as ML
+    import mmt_sample
+    L, st = ML.lib(), ML.stream_ptr(dev)
+    tok = torch.zeros(batch, dtype=torch.int64, device=dev)
+    lp = torch.zeros(batch, dtype=torch.float32, device=dev)
+    out = {}
+    for V in C1["V"] + [8192, 32768]:
+        bufs = [torch.randn(batch, V, device=dev) * 3.0 for _ in range(8)]
+        ptrs = [b.data_ptr() for b in bufs]
+        for name, (t, k_, p) in (("plain", (1.0, 0, 1.0)), ("top_k50", (0.8, 50, 1.0)),
+                                 ("top_k50_top_p0.9", (0.8, 50, 0.9)), ("greedy", (0.0, 0, 1.0))):
+            def one(k):
+                mmt_sample.launch(L, st, batch, V, ptrs[k % 8], V, t, k_, p, 3, 0, k, tok.data_ptr(), 1, 0, lp.data_ptr(), 1)
+
+            best = None
+            for _ in range(rounds):
+                for k in range(8):
+                    one(k)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                e0.record()
+                for k in range(reps):
+                    one(k)
+                e1.record()
+                torch.cuda.synchronize()
+                us = e0.elapsed_time(e1) / reps * 1e3
+                best = us if best is None else min(best, us)
+            out[f"V{V}_{name}"] = round(best, 2)
+    return out
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,278 @@
+// Device-side sampling of generate (mmt.h: mmt_sample): temperature, top-k, top-p, a counter-hash uniform draw,
+// the token and its log-probability, one 256-thread workgroup per row, one launch for all rows.
+//
+// No float atomics and no data-dependent summation order: every sum below runs over a fixed assignment of
+// elements to threads and a fixed tree (per-thread serial sum, xor-butterfly or shift scan inside a wave, the
+// four wave totals added left to right), so a launch is bit-identical run to run and a row's result does not
+// depend on which other rows share the launch.
+//
+// A row's scaled logits z stay in LDS for V <= SAMPLE_ONCHIP (32 KiB; C1's heads are 900 / 13 / 144 / 5); larger
+// rows re-read the logits from global memory (L2) and redo the one multiply: the same code, another accessor.
+//
+// Thresholds (top-k: the k-th largest z; top-p: the largest z whose upper set holds top_p * S) are found by a
+// bitwise search over the order-preserving 32-bit key of z: 16 rounds, two bits each, of "how many / how much mass
+// at key >= candidate" for the three candidates of the round, most significant bits first. Counts are integers, hence exact. A mass is a sum of non-negative
+// terms over a fixed tree with some leaves zeroed; round-to-nearest addition is monotone in each operand, so the
+// mass is monotone in the candidate and the search is well defined.
+//
+// The weights exp(z - m) are fp32 (expf); every sum of them (masses, S, the prefix sums) is fp64, so what
+// separates the result from the exact rule is the weights' own rounding, not the length of the row. The kernel is
+// latency-bound (a few hundred expf and ~40 barriers per row at V = 900), the fp64 adds are not what it waits for.
+#include "mmt.h"
+#include "mmt_common.h"
+
+namespace {
+
+constexpr int SAMPLE_THREADS = 256;
+constexpr int SAMPLE_WAVES = SAMPLE_THREADS / MMT_WAVE;
+constexpr int SAMPLE_ONCHIP = 8192;      // largest V whose row lives in LDS
+constexpr int SAMPLE_MAX_V = 1 << 20;    // largest V of the strided path
+constexpr uint32_t SAMPLE_SALT = 0x53414D50u;  // "SAMP"
+
+// order-preserving key: a < b (floats, no NaN) <=> okey(a) < okey(b)
+__device__ __forceinline__ uint32_t okey(float z) {
+  const uint32_t b = __float_as_uint(z);
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
+struct SampleShared {
+  float f[2][SAMPLE_WAVES];
+  double d[2][3][SAMPLE_WAVES];
+  unsigned long long q[2][SAMPLE_WAVES];
+  int i[2][SAMPLE_WAVES];
+  int j[2][SAMPLE_WAVES];
+};
+
+// block reductions: wave butterfly (every lane ends with the same value), the four wave results combined left to
+// right by every thread. The slots are double buffered by `par`, so one barrier per reduction suffices: a slot is
+// rewritten two reductions later, after a barrier every reader has passed.
+// three sums at once (the three candidates of one search round): independent chains, one barrier
+__device__ __forceinline__ void block_sum3(double (&v)[3], SampleShared& sh, int& par) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) v[k] += __shfl_xor(v[k], o, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) sh.d[par][k][threadIdx.x >> 6] = v[k];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < 3; ++k) v[k] = ((sh.d[par][k][0] + sh.d[par][k][1]) + sh.d[par][k][2]) + sh.d[par][k][3];
+  par ^= 1;
+}
+__device__ __forceinline__ float block_max(float v, SampleShared& sh, int& par) {
+  v = warp_max(v);
+  if ((threadIdx.x & 63) == 0) sh.f[par][threadIdx.x >> 6] = v;
+  __syncthreads();
+  const float r = fmaxf(fmaxf(sh.f[par][0], sh.f[par][1]), fmaxf(sh.f[par][2], sh.f[par][3]));
+  par ^= 1;
+  return r;
+}
+// three counts of at most 2^20 each, packed into 21-bit fields of one 64-bit word
+__device__ __forceinline__ unsigned long long block_count3(unsigned long long v, SampleShared& sh, int& par) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  if ((threadIdx.x & 63) == 0) sh.q[par][threadIdx.x >> 6] = v;
+  __syncthreads();
+  const unsigned long long r = sh.q[par][0] + sh.q[par][1] + sh.q[par][2] + sh.q[par][3];
+  par ^= 1;
+  return r;
+}
+
+// weight of an element relative to the row maximum m: 1 at the maximum (also when m is +inf), exp(z - m) below
+__device__ __forceinline__ float weight(float z, float m) { return z == m ? 1.0f : expf(z - m); }
+
+template <bool ONCHIP>
+__global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(
+    int V, const float* __restrict__ logits, int64_t row_stride, float inv_t, int greedy, int top_k, float top_p,
+    uint32_t key, uint32_t row0, uint32_t pos, int64_t* __restrict__ tok, int64_t tok_stride,
+    int64_t* __restrict__ tok_compact, float* __restrict__ logprob, int64_t lp_stride) {
+  __shared__ float zs[ONCHIP ? SAMPLE_ONCHIP : 1];
+  __shared__ SampleShared sh;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b = blockIdx.x;
+  const float* row = logits + (int64_t)b * row_stride;
+  int par = 0;
+
+  // step 1: z = logit * inv_t (one fp32 multiply), NaN as -inf
+  auto scaled = [&](int i) -> float {
+    const float z = row[i] * inv_t;
+    return z != z ? -INFINITY : z;
+  };
+  auto zat = [&](int i) -> float { return ONCHIP ? zs[i] : scaled(i); };
+
+  float m = -INFINITY;
+  for (int i = tid; i < V; i += SAMPLE_THREADS) {
+    const float z = scaled(i);
+    if (ONCHIP) zs[i] = z;
+    m = fmaxf(m, z);
+  }
+  m = block_max(m, sh, par);  // its barrier also publishes zs
+
+  int64_t* tok_out = tok + (int64_t)b * tok_stride;
+  if (m == -INFINITY) {  // no finite logit: token 0, log-probability NaN (uniform branch: every thread holds m)
+    if (tid == 0) {
+      *tok_out = 0;
+      if (tok_compact) tok_compact[b] = 0;
+      if (logprob) logprob[(int64_t)b * lp_stride] = __uint_as_float(0x7fc00000u);
+    }
+    return;
+  }
+
+  // step 2: top-k threshold key, the k-th largest key (duplicates counted); 0 keeps everything
+  uint32_t K = 0;
+  if (!greedy && top_k > 0 && top_k < V) {
+    for (int bit = 30; bit >= 0; bit -= 2) {  // two bits per round: the largest of three candidates that holds
+      const uint32_t c1 = K | (1u << bit), c2 = K | (2u << bit), c3 = K | (3u << bit);
+      unsigned long long n = 0;
+      for (int i = tid; i < V; i += SAMPLE_THREADS) {
+        const uint32_t k = okey(zat(i));
+        n += (k >= c1 ? 1ull : 0ull) + (k >= c2 ? 1ull << 21 : 0ull) + (k >= c3 ? 1ull << 42 : 0ull);
+      }
+      n = block_count3(n, sh, par);
+      const unsigned long long kk = (unsigned long long)top_k;
+      K = (n >> 42) >= kk ? c3 : ((n >> 21) & 0x1FFFFFull) >= kk ? c2 : (n & 0x1FFFFFull) >= kk ? c1 : K;
+    }
+  }
+
+  // steps 3, 4: the mass of { key >= max(cand, K) } over the interleaved assignment; top-p threshold key
+  if (!greedy && top_p < 1.0f) {
+    const uint32_t km = okey(m);
+    if (top_p <= 0.0f) {
+      K = km;
+    } else {
+      // s[j] = mass of { key >= l_j } for l1 <= l2 <= l3: each a sum over the same assignment and tree with the
+      // leaves below its bound zeroed
+      auto mass3 = [&](uint32_t l1, uint32_t l2, uint32_t l3, double (&s)[3]) {
+        s[0] = s[1] = s[2] = 0.0;
+        for (int i = tid; i < V; i += SAMPLE_THREADS) {
+          const float z = zat(i);
+          const uint32_t k = okey(z);
+          if (k >= l1) {
+            const double w = (double)weight(z, m);
+            s[0] += w;
+            s[1] += k >= l2 ? w : 0.0;
+            s[2] += k >= l3 ? w : 0.0;
+          }
+        }
+        block_sum3(s, sh, par);
+      };
+      double s[3];
+      mass3(K, 0xFFFFFFFFu, 0xFFFFFFFFu, s);  // no key is 0xFFFFFFFF (a NaN pattern; NaNs were replaced)
+      const double pS = (double)top_p * s[0];
+      uint32_t P = 0;
+      for (int bit = 30; bit >= 0; bit -= 2) {
+        const uint32_t c1 = P | (1u << bit), c2 = P | (2u << bit), c3 = P | (3u << bit);
+        mass3(c1 > K ? c1 : K, c2 > K ? c2 : K, c3 > K ? c3 : K, s);
+        P = s[2] >= pS ? c3 : s[1] >= pS ? c2 : s[0] >= pS ? c1 : P;
+      }
+      K = P > K ? P : K;
+      K = K < km ? K : km;  // the maximal group always stays
+    }
+  }
+
+  // steps 5, 6: prefix sums in vocabulary order. Thread t owns the contiguous chunk [t c, t c + c), c odd so the
+  // LDS reads of a wave spread over the banks; serial sum per thread, shift scan over the lanes, wave totals added
+  // left to right.
+  const int c = ((V + SAMPLE_THREADS - 1) / SAMPLE_THREADS) | 1;
+  const int64_t i0l = (int64_t)tid * c;
+  const int i0 = i0l < V ? (int)i0l : V, i1 = i0l + c < V ? (int)(i0l + c) : V;
+  double tot = 0.0;
+  bool has_max = false;
+  for (int i = i0; i < i1; ++i) {
+    const float z = zat(i);
+    tot += okey(z) >= K ? (double)weight(z, m) : 0.0;
+    has_max = has_max || z == m;
+  }
+  double inc = tot;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const double n = __shfl_up(inc, o, 64);
+    if (lane >= o) inc += n;
+  }
+  double ex = __shfl_up(inc, 1, 64);
+  if (lane == 0) ex = 0.0;
+  if (lane == 63) sh.d[par][0][wave] = inc;
+  __syncthreads();
+  const double w0 = sh.d[par][0][0], w1 = sh.d[par][0][1], w2 = sh.d[par][0][2], w3 = sh.d[par][0][3];
+  par ^= 1;
+  const double S = ((w0 + w1) + w2) + w3;
+  const double wbase = wave == 0 ? 0.0 : wave == 1 ? w0 : wave == 2 ? (w0 + w1) : ((w0 + w1) + w2);
+  const double base = wbase + ex;
+
+  const uint32_t h = mmt_hash(key, row0 + (uint32_t)b, pos);
+  const double u = ((double)(h >> 8) + 0.5) * (1.0 / 16777216.0);
+  const double target = u * S;
+
+  // the owner of the token: the first thread whose inclusive prefix reaches the target (greedy: that holds a
+  // maximum); should rounding leave none, the last thread with any weight
+  const bool hit = greedy ? has_max : (tot > 0.0 && base + tot >= target);
+  const unsigned long long hm = __ballot(hit), nm = __ballot(tot > 0.0);
+  if (lane == 0) {
+    sh.i[par][wave] = hm ? wave * 64 + (__ffsll((long long)hm) - 1) : SAMPLE_THREADS;
+    sh.j[par][wave] = nm ? wave * 64 + (63 - __clzll((long long)nm)) : -1;
+  }
+  __syncthreads();
+  int first = SAMPLE_THREADS, last = -1;
+#pragma unroll
+  for (int w = 0; w < SAMPLE_WAVES; ++w) {
+    first = sh.i[par][w] < first ? sh.i[par][w] : first;
+    last = sh.j[par][w] > last ? sh.j[par][w] : last;
+  }
+  const int owner = first < SAMPLE_THREADS ? first : last;
+  if (tid != owner) return;
+
+  int t = -1, lastpos = i0;
+  double p = base;
+  for (int i = i0; i < i1; ++i) {
+    const float z = zat(i);
+    if (greedy) {
+      if (z == m) { t = i; break; }
+      continue;
+    }
+    const float e = okey(z) >= K ? weight(z, m) : 0.f;
+    p += (double)e;
+    if (e > 0.f) {
+      lastpos = i;
+      if (p >= target) { t = i; break; }
+    }
+  }
+  if (t < 0) t = lastpos;
+  *tok_out = t;
+  if (tok_compact) tok_compact[b] = t;
+  if (logprob) {
+    // step 7: log(e_tok / S) = (z_tok - m) - log S
+    const float zt = zat(t);
+    const float d = zt == m ? 0.f : zt - m;
+    logprob[(int64_t)b * lp_stride] = (float)((double)d - log(S));
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int mmt_sample(void* stream, int32_t batch, int32_t V, const float* logits, int64_t row_stride, float temperature,
+               int32_t top_k, float top_p, uint64_t seed, uint32_t row0, uint32_t pos, int64_t* tok,
+               int64_t tok_stride, int64_t* tok_compact, float* logprob, int64_t lp_stride) {
+  if (batch < 0 || V < 1 || row_stride < V || !(temperature >= 0.0f) || top_k < 0 || top_p != top_p)
+    return MMT_ERR_INVALID;
+  if (batch > 0 && (!logits || !tok)) return MMT_ERR_INVALID;
+  if (V > SAMPLE_MAX_V) return MMT_ERR_UNSUPPORTED;
+  if (batch == 0) return MMT_OK;
+  const int greedy = temperature == 0.0f ? 1 : 0;
+  const float inv_t = greedy ? 1.0f : 1.0f / temperature;
+  const uint32_t key = mmt_hash((uint32_t)seed, (uint32_t)(seed >> 32), SAMPLE_SALT);
+  hipStream_t s = (hipStream_t)stream;
+  if (V <= SAMPLE_ONCHIP)
+    hipLaunchKernelGGL(sample_kernel<true>, dim3((unsigned)batch), dim3(SAMPLE_THREADS), 0, s, V, logits, row_stride,
+                       inv_t, greedy, top_k, top_p, key, row0, pos, tok, tok_stride, tok_compact, logprob, lp_stride);
+  else
+    hipLaunchKernelGGL(sample_kernel<false>, dim3((unsigned)batch), dim3(SAMPLE_THREADS), 0, s, V, logits, row_stride,
+                       inv_t, greedy, top_k, top_p, key, row0, pos, tok, tok_stride, tok_compact, logprob, lp_stride);
+  return hipGetLastError() == hipSuccess ? MMT_OK : MMT_ERR_HIP;
+}
+
+}  // extern "C"

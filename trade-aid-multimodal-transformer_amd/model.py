@@ -489,7 +489,8 @@ class MultimodalTransformer(nn.Module):
         return logits, [losses[i] for i in range(M)]
 
     @torch.no_grad()
-    def generate(self, idx_list, max_new_tokens=1, modality_to_generate=0, use_cache=True, sample_fn=None):
+    def generate(self, idx_list, max_new_tokens=1, modality_to_generate=0, use_cache=True, sample_fn=None, *,
+                 temperature=None, top_k=None, top_p=None, seed=None, return_logprobs=False, logits_hook=None):
         """model.py:404-446: per new token, the logits of the last position of the (block_size
         cropped) context, a sample from the softmax of the target modality's last logits
         (torch.multinomial, as the reference; `sample_fn(probs) -> [B, 1]` overrides it), appended;
@@ -503,7 +504,20 @@ class MultimodalTransformer(nn.Module):
         re-run of the prompt's GEMMs. Once the sequence outgrows the block every position shifts
         and it falls back to the reference's full re-forward. use_cache=False (or training mode
         with dropout, where the reference's forward samples dropout, or the fp8 precision, whose
-        forward GEMMs the bf16 decode would not reproduce) always re-runs the forward."""
+        forward GEMMs the bf16 decode would not reproduce) always re-runs the forward.
+
+        Any of the keywords temperature / top_k / top_p / seed / return_logprobs / logits_hook selects the
+        device path (`_generate_device`; the rule of mmt_sample in include/mmt.h): sampling
+        on the device with draws keyed by (seed, row, position), no torch generator consumed, and with
+        return_logprobs=True the return value (sequences, logprobs fp32 [B, max_new_tokens]). Without them
+        the body below runs as before."""
+        if not (temperature is None and top_k is None and top_p is None and seed is None and not return_logprobs
+                and logits_hook is None):
+            if sample_fn is not None:
+                raise ValueError("generate: sample_fn cannot be combined with temperature / top_k / top_p / seed / "
+                                 "return_logprobs / logits_hook (the device path samples on the GPU)")
+            return self._generate_device(idx_list, max_new_tokens, modality_to_generate, use_cache, temperature, top_k,
+                                         top_p, seed, return_logprobs, logits_hook)
         seqs = [idx.clone() for idx in idx_list]
         T = self.block_size
         g = modality_to_generate
@@ -533,6 +547,103 @@ class MultimodalTransformer(nn.Module):
                 elif seqs[i].shape[1] > n:
                     seqs[i] = seqs[i][:, :n]
         return seqs
+
+    @torch.no_grad()
+    def _generate_device(self, idx_list, max_new_tokens, g, use_cache, temperature, top_k, top_p, seed,
+                         return_logprobs, logits_hook):
+        """generate with the sampling on the device (mmt_sample, include/mmt.h). The sequences live in
+        preallocated [B, n0 + max_new_tokens] buffers, the other modalities' pad with their last token is
+        written once before the loop (what the reference's pad / crop rule amounts to for prompts of one
+        length), the sampler writes column n of the target modality's buffer and the compact [B] token buffer
+        the next decode step reads, and the logits buffers and pointer arrays of the decode steps are made
+        once. Per token the host issues mmt_decode_step and mmt_sample, nothing else: no torch op, no sync.
+        Past block_size, with use_cache=False, in training mode with dropout and at fp8 a step is the
+        re-forward over the cropped context (the cache rule of the default path) and mmt_sample on the last
+        position of its logits, read in place. The draw of row b at sequence position n is keyed by
+        (seed, b, n): the same seed and the same logits give the same tokens whatever the cache mode and
+        whatever else is in the batch. seed=None takes one from the device generator (never torch's CPU
+        generator). `logits_hook(n, logits_BV)` sees the [B, V] view the sampler is about to read (the decode
+        steps reuse one buffer: clone it to keep it). Prompts of unequal lengths run the reference's loop with
+        the same sampler."""
+        import mmt_sample as MS
+        t, k, p = MS.check_settings(temperature, top_k, top_p)
+        flat = self.flat_params
+        dev = flat.device
+        M, T, N = self.num_modalities, self.block_size, int(max_new_tokens)
+        if len(idx_list) != M:
+            raise ValueError(f"expected {M} index tensors, got {len(idx_list)}")
+        if not 0 <= g < M:
+            raise ValueError(f"modality_to_generate must be 0..{M - 1}, got {g}")
+        if dev.type != "cuda":
+            raise RuntimeError("MultimodalTransformer (libmmt_hip) runs only on a ROCm GPU: call .to('cuda') "
+                               "(there is no CPU path)")
+        seed = MS.device_seed(dev) if seed is None else int(seed) & MS.MASK64
+        V = self.vocab_sizes[g]
+        B = idx_list[0].shape[0]
+        prompts = [s.to(device=dev, dtype=torch.long) for s in idx_list]
+        lp = torch.empty(B, max(N, 0), dtype=torch.float32, device=dev) if return_logprobs else None
+        L = ML.lib()
+        if len({int(s.shape[1]) for s in prompts}) != 1 or any(s.dim() != 2 for s in prompts):
+            # unequal prompt lengths: the reference's loop (re-forward, pad / crop per step) around the sampler
+            seqs = [s.clone() for s in prompts]
+            for j in range(N):
+                n = seqs[g].shape[1]
+                logits, _ = self([s[:, -T:] for s in seqs])
+                last = logits[g][:, -1, :]
+                if logits_hook is not None:
+                    logits_hook(n, last)
+                nxt, l = MS.sample(last, temperature=t, top_k=k, top_p=p, seed=seed, pos=n, return_logprobs=True)
+                if lp is not None:
+                    lp[:, j] = l
+                seqs[g] = torch.cat((seqs[g], nxt[:, None]), dim=1)
+                for i in range(M):
+                    if i != g and seqs[i].shape[1] < n + 1:
+                        seqs[i] = torch.cat((seqs[i], seqs[i][:, -1:]), dim=1)
+                    elif i != g and seqs[i].shape[1] > n + 1:
+                        seqs[i] = seqs[i][:, :n + 1]
+            seqs = [s.to(idx_list[i].dtype) for i, s in enumerate(seqs)]
+            return (seqs, lp) if return_logprobs else seqs
+        n0 = int(prompts[0].shape[1])
+        if n0 < 1:
+            raise ValueError("generate: the prompt must hold at least one token")
+        cap = n0 + N
+        bufs = []
+        for i, s in enumerate(prompts):
+            buf = torch.zeros(B, cap, dtype=torch.long, device=dev)
+            buf[:, :n0] = s
+            if i != g and N > 0:
+                buf[:, n0:] = s[:, -1:]
+            bufs.append(buf)
+        compact = torch.zeros(B, dtype=torch.long, device=dev)
+        cache = use_cache and not (self.training and self.dropout_p > 0.0) and self.precision == "bf16"
+        cached_pos = None  # the last position whose keys / values the workspace holds
+        dec = None  # (token pointers, logits pointers, logits buffers, workspace pointer) of the decode steps
+        tok_base, lp_base = bufs[g].data_ptr(), (lp.data_ptr() if lp is not None else 0)
+        with torch.cuda.device(dev):
+            stream = ML.stream_ptr(dev)
+            for j in range(N):
+                n = n0 + j
+                if cache and cached_pos is not None and n - 1 == cached_pos + 1 and n <= T:
+                    if dec is None:
+                        dec_idx = [compact if i == g else prompts[i][:, -1].contiguous() for i in range(M)]
+                        dec_logits = [torch.empty(B, Vi, dtype=torch.float32, device=dev) for Vi in self.vocab_sizes]
+                        dec = (ML.ptr_array(dec_idx), ML.ptr_array(dec_logits), dec_logits, ML.ptr(self._ws), dec_idx,
+                               ML.ptr(flat))
+                    rc = L.mmt_decode_step(self._ctx, stream, B, n - 1, dec[0], dec[5], dec[1], dec[3])
+                    ML.check(rc, self._ctx, "mmt_decode_step")
+                    self._gen += 1
+                    cached_pos = n - 1
+                    last = dec[2][g]
+                else:
+                    logits, _ = self([buf[:, max(0, n - T):n] for buf in bufs])
+                    last = logits[g][:, -1, :]
+                    cached_pos = n - 1 if (cache and n <= T) else None
+                if logits_hook is not None:
+                    logits_hook(n, last)
+                MS.launch(L, stream, B, V, last.data_ptr(), int(last.stride(0)) if B > 1 else V, t, k, p, seed, 0, n,
+                          tok_base + 8 * n, cap, compact.data_ptr(), lp_base + 4 * j if lp_base else 0, N)
+        seqs = [buf.to(idx_list[i].dtype) for i, buf in enumerate(bufs)]
+        return (seqs, lp) if return_logprobs else seqs
 
     @torch.no_grad()
     def _decode_step(self, tokens, pos):
