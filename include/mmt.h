@@ -473,6 +473,19 @@ int mmt_op_attention_bwd_ws(void* stream, int32_t B, int32_t T, int32_t H, int32
                             const float* const* lse, const void* dout, int32_t dout_ld, float* const* dvec, void* dq,
                             int32_t dq_ld, void* const* dk, void* const* dv, int32_t dkv_ld, int32_t dkv_hstride,
                             float* dq32, int32_t dq32_ld);
+/* KV-cache decode attention, the kernel under mmt_decode_step: ONE query position t (0 <= t < T) per sequence
+ * against the cached keys / values of positions 0..t, one softmax per KV stream (scale = hs^-0.5), the
+ * per-stream outputs summed. q and o are compact [B, *] bf16 (row b, head h at column h*hs, row strides q_ld /
+ * o_ld); the cache of stream j is k[j] / v[j], bf16 [B*T, kv_ld]: position s of sequence b is row b*T + s, head
+ * h at column h*kv_hstride (self-attention: the forward's [B*T, 3C] Q/K/V rows with k = +0, v = +2C, kv_hstride
+ * = hs; cross-attention: per-stream [B*T, 2C] rows with v = k + hs, kv_hstride = 2 hs). Rows s > t are never
+ * read; only columns [h*hs, (h+1)*hs) of o are written. Arithmetic is fp32 on the bf16 values, o is rounded
+ * once. Before any launch: MMT_ERR_INVALID for a null pointer, B or H < 1, nstreams outside 1..8, t outside
+ * 0..T-1, or q_ld / kv_ld / kv_hstride not a multiple of 8 (16-byte loads; the pointers must be 16-B aligned
+ * too); MMT_ERR_UNSUPPORTED for hs not in {8, 16, 24, 32, 48, 64}. */
+int mmt_op_attention_decode(void* stream, int32_t B, int32_t t, int32_t T, int32_t H, int32_t hs, int32_t nstreams,
+                            const void* q, int32_t q_ld, const void* const* k, const void* const* v,
+                            int32_t kv_ld, int32_t kv_hstride, void* o, int32_t o_ld);
 /* hs-32 causal self-attention (T <= 256) with Q / K / V made on chip: in place of q / k / v the kernels take
  * the stage-1 rows h1 (bf16 [B*T][ld_h1], ld_h1 % 8 == 0, 16-B aligned; column block blk = kind * H + head of
  * 16 columns, kinds K, Q, V; pad columns and rows past the batch are never read) and w2 (fp32 [3 H][32][16],

@@ -184,6 +184,8 @@ _SIGS = {
                                         ctypes.POINTER(c_vp), c_i32, c_i32, c_vp, c_i32, ctypes.POINTER(c_vp),
                                         ctypes.POINTER(c_vp), c_vp, c_i32, ctypes.POINTER(c_vp), c_vp, c_i32,
                                         ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_i32, c_i32, c_vp, c_i32]),
+    "mmt_op_attention_decode": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32,
+                                        ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_i32, c_i32, c_vp, c_i32]),
     "mmt_op_attention_fwd_h1": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp]),
     "mmt_op_attention_bwd_h1": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32,
                                         c_vp, c_vp, c_vp]),
