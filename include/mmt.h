@@ -99,6 +99,31 @@ int mmt_forward(mmt_ctx* ctx, void* stream, int32_t batch, const int64_t* const*
 int mmt_decode_step(mmt_ctx* ctx, void* stream, int32_t batch, int32_t pos, const int64_t* const* idx,
                     const float* params, float* const* logits, void* workspace);
 
+/* Sample fan-out (generate with num_samples = S): S continuations of each of `batch` prompts share ONE prefill
+ * and the prompt's keys / values. The decode step runs over batch*samples compact rows, row r = b*samples + s
+ * being sample s of prompt b, in a caller-owned fan buffer (the library still never allocates):
+ *   mmt_fanout_bytes        its size: the compact [batch*samples, *] scratch of one step plus the tail caches, per
+ *                           (layer, modality) the self-attention tail bf16 [batch*samples, max_new, 3C] and per
+ *                           (layer, cross modality, KV stream) the cross tail [batch*samples, max_new, 2C], row
+ *                           r*max_new + (pos - n0), columns as the forward's Q/K/V and cross K/V rows. -1 for
+ *                           batch, samples or max_new < 1, max_new >= block_size, or batch*samples rows beyond
+ *                           the launchers' 32-bit row * column range.
+ *   mmt_decode_fanout_step  the forward of position `pos` of every row: idx[i] int64 [batch*samples], logits[i]
+ *                           fp32 [batch*samples, V_i]. Keys / values of positions < n0 of row r are the workspace
+ *                           cache rows of sequence r / samples (what the last mmt_forward at `batch`, and any
+ *                           mmt_decode_step since, left there); positions n0..pos come from the fan buffer, which
+ *                           this step extends by position pos. The workspace is only read: after any number of
+ *                           fan-out steps mmt_decode_step at n0 gives the bits it gave before them.
+ * A run starts with pos == n0 (tail row 0) and continues with pos one greater per call, pos < n0 + max_new <=
+ * block_size; the engine keeps (n0, samples, next pos). MMT_ERR_STATE for a call out of order, without a prefill,
+ * after a prefill that sampled dropout and at precision fp8; MMT_ERR_INVALID for a null pointer, samples / n0 /
+ * max_new < 1, n0 + max_new > block_size, pos outside n0..n0+max_new-1, and after a training forward that kept
+ * Q/K/V on chip (as mmt_decode_step). Every refusal returns before any launch. A new mmt_forward ends the run. */
+int64_t mmt_fanout_bytes(mmt_ctx* ctx, int32_t batch, int32_t samples, int32_t max_new);
+int mmt_decode_fanout_step(mmt_ctx* ctx, void* stream, int32_t batch, int32_t samples, int32_t n0, int32_t max_new,
+                           int32_t pos, const int64_t* const* idx, const float* params, float* const* logits,
+                           const void* workspace, void* fan);
+
 /* Device-side sampling of generate (reference model.py:425-427: softmax of the last logits, torch.multinomial,
  * nothing else): one token per row from fp32 logits with temperature, top-k and top-p, a draw keyed by
  * (seed, row, position), and the log-probability of the token, in ONE launch for all rows (one 256-thread
@@ -486,6 +511,21 @@ int mmt_op_attention_bwd_ws(void* stream, int32_t B, int32_t T, int32_t H, int32
 int mmt_op_attention_decode(void* stream, int32_t B, int32_t t, int32_t T, int32_t H, int32_t hs, int32_t nstreams,
                             const void* q, int32_t q_ld, const void* const* k, const void* const* v,
                             int32_t kv_ld, int32_t kv_hstride, void* o, int32_t o_ld);
+/* Sample fan-out decode attention, the kernel under mmt_decode_fanout_step: q and o are compact [B*samples, *],
+ * row r = b*samples + s. Keys / values of positions 0..n0-1 of row r are the cache rows b*T + p of k[j] / v[j] (as
+ * above), positions n0..t its own tail rows r*tail_rows + (p - n0) of tail_k[j] / tail_v[j], bf16
+ * [B*samples*tail_rows, tail_ld], head h at column h*kv_hstride. One softmax per stream over the t + 1 keys, the
+ * outputs summed. A workgroup serves 16 samples of one (prompt, head): a prefix row is fetched once for the 16.
+ * Cache rows >= n0, tail rows > t - n0 and rows of samples >= `samples` are never read or written; fp32 scores and
+ * probabilities (flash-style running maximum over 64-key tiles), o rounded once; bit-identical run to run, and
+ * a sample's output does not depend on the other samples of the launch. Before any launch: the checks of
+ * mmt_op_attention_decode, and MMT_ERR_INVALID for samples < 1, n0 outside 1..t, tail_rows <= t - n0, a null
+ * tail pointer or tail_ld not a multiple of 8. */
+int mmt_op_attention_decode_fanout(void* stream, int32_t B, int32_t samples, int32_t n0, int32_t t, int32_t T,
+                                   int32_t H, int32_t hs, int32_t nstreams, const void* q, int32_t q_ld,
+                                   const void* const* k, const void* const* v, int32_t kv_ld, int32_t kv_hstride,
+                                   const void* const* tail_k, const void* const* tail_v, int32_t tail_ld,
+                                   int32_t tail_rows, void* o, int32_t o_ld);
 /* hs-32 causal self-attention (T <= 256) with Q / K / V made on chip: in place of q / k / v the kernels take
  * the stage-1 rows h1 (bf16 [B*T][ld_h1], ld_h1 % 8 == 0, 16-B aligned; column block blk = kind * H + head of
  * 16 columns, kinds K, Q, V; pad columns and rows past the batch are never read) and w2 (fp32 [3 H][32][16],

@@ -11,6 +11,14 @@ one generate with one synchronisation at its end; tokens per second counts B * n
 --tree DIR takes the package (and its built library) of another checkout of this repository, e.g. the parent
 commit, whose generate has the default path only (--paths default). --sampler adds the time of mmt_sample on its
 own per vocabulary size and setting. One JSON line per run.
+
+    python tools/generate_bench.py --samples S --batch B [--paths fanout,tiled] [--attn]
+
+--samples S measures S continuations per prompt instead: `fanout` is generate(prompts, num_samples=S) and `tiled`
+the same call over the prompts repeated S times by the caller (what a checkout without the keyword can do: with
+--tree, --paths tiled). Per round it records paths per second (B * S / wall time), tokens per second and the peak
+of torch.cuda.max_memory_allocated over the call; a path that runs out of memory is reported as such. --attn adds
+the fan-out attention kernel alone against attn_decode_kernel at B * S rows (this tree only).
 """
 import argparse
 import json
@@ -34,7 +42,11 @@ def main():
     ap.add_argument("--tree", default=REPO)
     ap.add_argument("--label", default="")
     ap.add_argument("--sampler", action="store_true", help="also time mmt_sample alone (this tree only)")
+    ap.add_argument("--samples", type=int, default=0, help="continuations per prompt (0: the single-path benchmark)")
+    ap.add_argument("--attn", action="store_true", help="with --samples: the two decode attention kernels alone")
     a = ap.parse_args()
+    if a.samples and a.paths == "default,device":
+        a.paths = "fanout,tiled"
     sys.path.insert(0, os.path.join(os.path.abspath(a.tree), "trade-aid-multimodal-transformer_amd"))
     import torch
     import config_utils
@@ -60,6 +72,8 @@ def main():
                                                    top_k=50, top_p=0.9, seed=11),
     }
     paths = [p for p in a.paths.split(",") if p]
+    if a.samples:
+        return fanout_bench(a, torch, dev, model, prompt, paths)
     out = {p: [] for p in paths}
     for p in paths:
         for _ in range(a.warmup):
@@ -80,6 +94,96 @@ def main():
     if a.sampler:
         res["sampler_us"] = sampler_alone(torch, dev, a.batch, a.rounds)
     print(json.dumps(res), flush=True)
+
+
+def fanout_bench(a, torch, dev, model, prompt, paths):
+    """--samples: the paths alternate, one sync per call, per round paths/s, tokens/s and the call's peak memory."""
+    S, B = a.samples, a.batch
+    tiled = [p.repeat_interleave(S, 0) for p in prompt]
+    kw = dict(max_new_tokens=a.new, modality_to_generate=0, temperature=1.0, seed=11)
+    calls = {"fanout": lambda: model.generate(prompt, num_samples=S, **kw),
+             "tiled": lambda: model.generate(tiled, **kw)}
+    rec = {p: {"paths_per_s": [], "tokens_per_s": [], "peak_bytes": []} for p in paths}
+
+    def one(p, timed):
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats(dev)
+        t0 = time.perf_counter()
+        try:
+            seqs = calls[p]()
+        except torch.OutOfMemoryError as e:
+            rec[p]["error"] = "out of memory: " + str(e).splitlines()[0][:160]
+            return False
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        assert tuple(seqs[0].shape) == (B * S, a.prompt + a.new)
+        if timed:
+            rec[p]["paths_per_s"].append(round(B * S / dt, 1))
+            rec[p]["tokens_per_s"].append(round(B * S * a.new / dt, 1))
+            rec[p]["peak_bytes"].append(int(torch.cuda.max_memory_allocated(dev)))
+        return True
+
+    live = [p for p in paths if all(one(p, False) for _ in range(a.warmup))]
+    for _ in range(a.rounds):
+        live = [p for p in live if one(p, True)]
+    res = {"tool": "generate_bench", "label": a.label, "device": torch.cuda.get_device_name(0), "batch": B,
+           "samples": S, "prompt": a.prompt, "new_tokens": a.new, "paths": rec}
+    if "fanout" in paths:
+        res["fanout_path"] = getattr(model, "last_generate_path", None) if "fanout" in live else None
+    if a.attn:
+        res["attn_us"] = attention_alone(torch, dev, B, S, a.prompt, a.prompt + a.new, a.rounds)
+    print(json.dumps(res), flush=True)
+
+
+def attention_alone(torch, dev, B, S, n0, T, rounds, reps=50):
+    """us per launch (HIP events around `reps` back-to-back launches, best of `rounds`) of the self-attention decode
+    of one modality at C1's heads: the fan-out kernel over B prompts x S samples with a shared prefix of n0 keys,
+    and attn_decode_kernel over B * S rows with a cache row each, at the middle and the last position."""
+    import ctypes
+
+    import mmt_lib as ML
+    L, st = ML.lib(), ML.stream_ptr(dev)
+    H, hs = C1["n_head"], C1["n_embd"] // C1["n_head"]
+    C, R, cap = H * hs, B * S, T - n0
+    bf = torch.bfloat16
+    q = torch.randn(R, 3 * C, device=dev).to(bf)
+    o = torch.empty(R, C, device=dev, dtype=bf)
+    cache = torch.randn(B * T, 3 * C, device=dev).to(bf)
+    tail = torch.randn(R * cap, 3 * C, device=dev).to(bf)
+    one = lambda x: (ctypes.c_void_p * 1)(x.data_ptr())  # noqa: E731
+    out = {}
+    try:
+        big = torch.randn(R * T, 3 * C, device=dev).to(bf)
+    except torch.OutOfMemoryError:
+        big = None
+    for t in (n0 + cap // 2 - 1, T - 1):
+        def fan():
+            return L.mmt_op_attention_decode_fanout(st, B, S, n0, t, T, H, hs, 1, ML.ptr(q[:, C:]), 3 * C, one(cache),
+                                                    one(cache[:, 2 * C:]), 3 * C, hs, one(tail), one(tail[:, 2 * C:]),
+                                                    3 * C, cap, ML.ptr(o), C)
+
+        def plain():
+            return L.mmt_op_attention_decode(st, R, t, T, H, hs, 1, ML.ptr(q[:, C:]), 3 * C, one(big),
+                                             one(big[:, 2 * C:]), 3 * C, hs, ML.ptr(o), C)
+
+        for name, fn in (("fanout", fan), ("decode", plain)):
+            if name == "decode" and big is None:
+                out[f"decode_t{t}"] = "out of memory"
+                continue
+            best = None
+            for _ in range(rounds):
+                assert fn() == 0
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                e0.record()
+                for _k in range(reps):
+                    fn()
+                e1.record()
+                torch.cuda.synchronize()
+                us = e0.elapsed_time(e1) / reps * 1e3
+                best = us if best is None else min(best, us)
+            out[f"{name}_t{t}"] = round(best, 2)
+    return out
 
 
 def sampler_alone(torch, dev, batch, rounds, reps=200):

@@ -109,6 +109,19 @@ struct Plan {
   std::vector<size_t> dec_x;  // [L*M][3]: fp32 residual stream x1, x2, x3 of the new rows
 };
 
+// Sample fan-out (mmt_decode_fanout_step): byte offsets in the caller's fan buffer. The compact scratch of
+// B*S rows (what Plan::dec / dec_x are for B rows) and the tail caches: per (layer, modality) the self-attention
+// tail [B*S, max_new, 3C], per (layer, cross modality, KV stream) the cross tail [B*S, max_new, 2C], bf16, row
+// r*max_new + (pos - n0), columns as the forward's rows
+struct FanPlan {
+  int B = -1, S = -1, max_new = -1;
+  size_t total = 0;
+  Plan::Dec dec[MAXM];
+  std::vector<size_t> dec_x;
+  std::vector<size_t> sa_tail;  // [L*M]
+  std::vector<size_t> ca_tail;  // [L*M][MAXM]
+};
+
 }  // namespace
 
 // the FFN's ReLU' as bits written by ffn0 (16x fewer bytes than the bf16 hidden the ffn2 data
@@ -194,6 +207,9 @@ struct mmt_ctx {
   int last_B = -1;
   bool fwd_ready = false;
   bool cache_ready = false;  // a forward filled the workspace's Q/K/V (decode may follow)
+  // sample fan-out: the buffer plan and the run in progress (n0, samples, next position; fan_next < 0: none)
+  FanPlan fan;
+  int fan_n0 = -1, fan_S = -1, fan_next = -1;
   bool last_training = false;
   uint64_t step_counter = 0;
   // dropout: seed of the next training forward (mmt_set_dropout_seed) and of the last one
@@ -458,6 +474,49 @@ size_t flag_offset(const mmt_ctx* c) { return (size_t)rup(c->pack_elems * 2, 256
 // -------------------------------------------------------------------------------------------
 // workspace plan for batch B (continued)
 // -------------------------------------------------------------------------------------------
+// the compact [rows, *] scratch of one decode step, every modality (rows = B, or B*S in a fan buffer)
+template <class Alloc>
+void plan_dec_rows(mmt_ctx* c, Alloc& A, size_t B, Plan::Dec* dec, std::vector<size_t>& dec_x) {
+  const int C = c->C, M = c->M, H = c->H;
+  const size_t f4 = 4, b2 = 2;
+  const int ldh1 = r8(3 * H * c->hh), ldp = r8(C / 2);
+  dec_x.resize((size_t)c->L * M * 3);
+  for (int i = 0; i < M; ++i) {
+    Plan::Dec& d = dec[i];
+    d.x0 = A(B * C * f4); d.a16 = A(B * C * b2); d.mean = A(B * f4); d.rstd = A(B * f4);
+    d.h1 = A(B * ldh1 * b2); d.qkv = A(B * 3 * C * b2); d.o16 = A(B * C * b2); d.p1 = A(B * ldp * b2);
+    d.f = A(B * 4 * C * b2); d.x2h = A(B * C * b2); d.d16 = A(B * C * b2); d.qc = A(B * C * b2);
+    d.oc = A(B * C * b2); d.pc = A(B * ldp * b2); d.lnf16 = A(B * C * b2); d.hh = A(B * c->ldvh[i] * b2);
+    for (int j = 0; j < M - 1; ++j) d.kv[j] = A(B * 2 * C * b2);
+  }
+  for (auto& o : dec_x) o = A(B * C * f4);
+}
+
+// the fan buffer of mmt_decode_fanout_step (include/mmt.h); false when the sizes leave the launchers' int range
+bool make_fan_plan(mmt_ctx* c, FanPlan& f, int B, int S, int max_new) {
+  f = FanPlan();
+  if (B < 1 || S < 1 || max_new < 1 || max_new >= c->T) return false;
+  const int64_t rows = (int64_t)B * S;
+  int64_t wide = 4 * (int64_t)c->C;
+  for (int i = 0; i < c->M; ++i) wide = std::max<int64_t>(wide, c->ldv[i]);
+  if (rows * wide >= ((int64_t)1 << 31)) return false;  // the GEMM and element kernels index rows * ld in int
+  f.B = B; f.S = S; f.max_new = max_new;
+  size_t cur = 0;
+  auto A = [&](size_t bytes) { const size_t o = cur; cur += (size_t)rup((int64_t)bytes, 256); return o; };
+  plan_dec_rows(c, A, (size_t)rows, f.dec, f.dec_x);
+  const int M = c->M;
+  f.sa_tail.assign((size_t)c->L * M, 0);
+  f.ca_tail.assign((size_t)c->L * M * MAXM, 0);
+  for (int l = 0; l < c->L; ++l)
+    for (int i = 0; i < M; ++i) {
+      f.sa_tail[(size_t)l * M + i] = A((size_t)rows * max_new * 3 * c->C * 2);
+      if (c->lm[(size_t)l * M + i].cross)
+        for (int j = 0; j < M - 1; ++j) f.ca_tail[((size_t)l * M + i) * MAXM + j] = A((size_t)rows * max_new * 2 * c->C * 2);
+    }
+  f.total = cur;
+  return true;
+}
+
 void make_plan(mmt_ctx* c, int B) {
   Plan& p = c->plan;
   p = Plan();
@@ -555,16 +614,7 @@ void make_plan(mmt_ctx* c, int B) {
     p.det = A((size_t)df * f4);
   }
   // decode scratch (tiny: B rows)
-  p.dec_x.resize((size_t)c->L * M * 3);
-  for (int i = 0; i < M; ++i) {
-    Plan::Dec& d = p.dec[i];
-    d.x0 = A(B * C * f4); d.a16 = A(B * C * b2); d.mean = A(B * f4); d.rstd = A(B * f4);
-    d.h1 = A(B * ldh1 * b2); d.qkv = A(B * 3 * C * b2); d.o16 = A(B * C * b2); d.p1 = A(B * ldp * b2);
-    d.f = A(B * 4 * C * b2); d.x2h = A(B * C * b2); d.d16 = A(B * C * b2); d.qc = A(B * C * b2);
-    d.oc = A(B * C * b2); d.pc = A(B * ldp * b2); d.lnf16 = A(B * C * b2); d.hh = A(B * c->ldvh[i] * b2);
-    for (int j = 0; j < M - 1; ++j) d.kv[j] = A(B * 2 * C * b2);
-  }
-  for (auto& o : p.dec_x) o = A(B * C * f4);
+  plan_dec_rows(c, A, (size_t)B, p.dec, p.dec_x);
   p.total = cur;
 }
 
@@ -1418,10 +1468,23 @@ int run_forward(mmt_ctx* c, Runner& r, const int64_t* const* idx, const int64_t*
 // its saved Q/K/V and cross-K/V buffers (row b*T + s); this step appends row t to them and runs
 // the decode attention over 0..t. Eval semantics (no dropout). The packed bf16 weights are the
 // ones the prefill forward made.
+//
+// Where the compact rows live is the caller's (DecWhere): the workspace plan with B rows (mmt_decode_step), or a
+// fan buffer with B*S rows, row b*S + s being sample s of prompt b (mmt_decode_fanout_step). The fan-out step
+// leaves the workspace alone: keys / values of positions < n0 are read from the cache rows of sequence b,
+// position t is appended to the fan buffer's tails (row r*max_new + t - n0) and the attention is the fan-out
+// kernel. Everything else is the same launches over `rows` rows.
 // -------------------------------------------------------------------------------------------
-int run_decode(mmt_ctx* c, Runner& r, int t, const int64_t* const* idx, float* const* logits) {
+struct DecWhere {
+  char* base; const Plan::Dec* dec; const size_t* dec_x; int rows;
+  const FanPlan* fan = nullptr; int S = 1, n0 = 0;
+  template <class T>
+  T* at(size_t off) const { return reinterpret_cast<T*>(base + off); }
+};
+
+int run_decode(mmt_ctx* c, Runner& r, const DecWhere& w, int t, const int64_t* const* idx, float* const* logits) {
   const int M = c->M, C = c->C, H = c->H, hs = c->hs, B = r.B, T = c->T;
-  const int R = B;  // compact rows
+  const int R = w.rows;  // compact rows
   const int ldh1 = r8(3 * H * c->hh), ldp = r8(C / 2);
   const float scale = 1.0f / std::sqrt((float)hs);
   Plan& p = c->plan;
@@ -1432,76 +1495,98 @@ int run_decode(mmt_ctx* c, Runner& r, int t, const int64_t* const* idx, float* c
     r.ok(hipMemcpy2DAsync(cache + (size_t)t * ld, (size_t)T * ld * 2, rows, (size_t)ld * 2, (size_t)ld * 2, B,
                           hipMemcpyDeviceToDevice, r.s), what);
   };
+  const int tail_rows = w.fan ? w.fan->max_new : 0;
+  auto tail_append = [&](bf16_t* tail, int ld, const bf16_t* rows, const char* what) {
+    // compact row r -> tail row r*max_new + (t - n0)
+    r.ok(hipMemcpy2DAsync(tail + (size_t)(t - w.n0) * ld, (size_t)tail_rows * ld * 2, rows, (size_t)ld * 2,
+                          (size_t)ld * 2, R, hipMemcpyDeviceToDevice, r.s), what);
+  };
   {
     EmbBatch eb{};
     eb.count = M;
     for (int i = 0; i < M; ++i) {
       eb.p[i].idx = idx[i]; eb.p[i].tok = r.P(c->post[i].tok); eb.p[i].pos = r.P(c->pos_off) + (int64_t)t * C;
-      eb.p[i].x = r.W<float>(p.dec[i].x0); eb.p[i].V = c->V[i];
+      eb.p[i].x = w.at<float>(w.dec[i].x0); eb.p[i].V = c->V[i];
     }
-    r.ok(mmt_launch_embed_fwd(eb, B, 1, C, r.s), "dec_embed");
+    r.ok(mmt_launch_embed_fwd(eb, R, 1, C, r.s), "dec_embed");
   }
   std::vector<const float*> xin(M);
-  for (int i = 0; i < M; ++i) xin[i] = r.W<float>(p.dec[i].x0);
+  for (int i = 0; i < M; ++i) xin[i] = w.at<float>(w.dec[i].x0);
   for (int l = 0; l < c->L && r.rc == MMT_OK; ++l) {
     const LM* x = &c->lm[(size_t)l * M];
     const ActLM* a = &p.act[(size_t)l * M];
-    auto X = [&](int i, int k) { return r.W<float>(p.dec_x[((size_t)l * M + i) * 3 + k]); };
+    auto X = [&](int i, int k) { return w.at<float>(w.dec_x[((size_t)l * M + i) * 3 + k]); };
     LnBatch lb{}; lb.count = M;
     for (int i = 0; i < M; ++i) {
-      const Plan::Dec& d = p.dec[i];
+      const Plan::Dec& d = w.dec[i];
       lb.p[i].x = xin[i]; lb.p[i].gamma = r.P(x[i].ln1w); lb.p[i].beta = r.P(x[i].ln1b);
-      lb.p[i].y = r.W<bf16_t>(d.a16); lb.p[i].mean = r.W<float>(d.mean); lb.p[i].rstd = r.W<float>(d.rstd);
+      lb.p[i].y = w.at<bf16_t>(d.a16); lb.p[i].mean = w.at<float>(d.mean); lb.p[i].rstd = w.at<float>(d.rstd);
     }
     r.ok(mmt_launch_ln_fwd(lb, R, C, r.s), "dec_ln1");
     GemmBatch g{}; g.count = M;
     for (int i = 0; i < M; ++i) {
-      g.p[i] = gp_fwd(r.W<bf16_t>(p.dec[i].a16), C, wpk, x[i].W1, R);
-      g.p[i].bias = r.P(x[i].b1); g.p[i].o16 = r.W<bf16_t>(p.dec[i].h1); g.p[i].ldo16 = ldh1;
+      g.p[i] = gp_fwd(w.at<bf16_t>(w.dec[i].a16), C, wpk, x[i].W1, R);
+      g.p[i].bias = r.P(x[i].b1); g.p[i].o16 = w.at<bf16_t>(w.dec[i].h1); g.p[i].ldo16 = ldh1;
     }
     r.gemm(g, true, true, EPI_BIAS_TANH_BF16, 1, "dec_qkv1");
     Qkv2Batch qb{}; qb.count = M;
     for (int i = 0; i < M; ++i) {
-      qb.p[i].h1 = r.W<bf16_t>(p.dec[i].h1); qb.p[i].w2 = r.P(x[i].w2); qb.p[i].out = r.W<bf16_t>(p.dec[i].qkv);
+      qb.p[i].h1 = w.at<bf16_t>(w.dec[i].h1); qb.p[i].w2 = r.P(x[i].w2); qb.p[i].out = w.at<bf16_t>(w.dec[i].qkv);
+      // fan-out: stage 2 writes row t - n0 of the self-attention tail itself (leading dimension max_new * 3C; the
+      // kernel forms (int64) row * ld and writes the 3C columns only), so no append copy and no compact K|Q|V row
+      if (w.fan) qb.p[i].out = w.at<bf16_t>(w.fan->sa_tail[(size_t)l * M + i]) + (size_t)(t - w.n0) * 3 * C;
     }
-    r.ok(mmt_launch_qkv2_fwd(qb, R, 3 * H, hs, ldh1, 3 * C, r.s), "dec_qkv2");
-    DecodeAttnBatch ab{}; ab.count = M;
-    for (int i = 0; i < M; ++i) {
+    r.ok(mmt_launch_qkv2_fwd(qb, R, 3 * H, hs, ldh1, w.fan ? tail_rows * 3 * C : 3 * C, r.s), "dec_qkv2");
+    if (w.fan) {
+      FanoutAttnBatch fb{}; fb.count = M;
+      for (int i = 0; i < M; ++i) {
+        const bf16_t* cache = r.W<bf16_t>(a[i].qkv);
+        bf16_t* tail = w.at<bf16_t>(w.fan->sa_tail[(size_t)l * M + i]);
+        FanoutAttnProblem& q = fb.p[i];
+        q.q = tail + (size_t)(t - w.n0) * 3 * C + C; q.q_ld = tail_rows * 3 * C;  // the query: the tail row just written
+        q.k[0] = cache; q.v[0] = cache + 2 * C; q.kv_ld = 3 * C; q.kv_hstride = hs;
+        q.tk[0] = tail; q.tv[0] = tail + 2 * C; q.tail_ld = 3 * C;
+        q.o = w.at<bf16_t>(w.dec[i].o16); q.o_ld = C; q.nstreams = 1;
+      }
+      r.ok(mmt_launch_attn_decode_fanout(fb, B, w.S, w.n0, t, T, H, hs, tail_rows, scale, r.s), "fan_attn");
+    }
+    DecodeAttnBatch ab{}; ab.count = w.fan ? 0 : M;
+    for (int i = 0; i < ab.count; ++i) {
       bf16_t* cache = r.W<bf16_t>(a[i].qkv);
-      scatter_rows(cache, 3 * C, r.W<bf16_t>(p.dec[i].qkv), "dec_kv_append");
+      scatter_rows(cache, 3 * C, w.at<bf16_t>(w.dec[i].qkv), "dec_kv_append");
       DecodeAttnProblem& q = ab.p[i];
-      q.q = r.W<bf16_t>(p.dec[i].qkv) + C; q.q_ld = 3 * C;
+      q.q = w.at<bf16_t>(w.dec[i].qkv) + C; q.q_ld = 3 * C;
       q.k[0] = cache; q.v[0] = cache + 2 * C; q.kv_ld = 3 * C; q.kv_hstride = hs;
-      q.o = r.W<bf16_t>(p.dec[i].o16); q.o_ld = C; q.nstreams = 1;
+      q.o = w.at<bf16_t>(w.dec[i].o16); q.o_ld = C; q.nstreams = 1;
     }
     r.ok(mmt_launch_attn_decode(ab, B, t, T, H, hs, scale, r.s), "dec_attn");
     for (int i = 0; i < M; ++i) {
-      g.p[i] = gp_fwd(r.W<bf16_t>(p.dec[i].o16), C, wpk, x[i].P0, R);
-      g.p[i].bias = r.P(x[i].bp0); g.p[i].o16 = r.W<bf16_t>(p.dec[i].p1); g.p[i].ldo16 = ldp;
+      g.p[i] = gp_fwd(w.at<bf16_t>(w.dec[i].o16), C, wpk, x[i].P0, R);
+      g.p[i].bias = r.P(x[i].bp0); g.p[i].o16 = w.at<bf16_t>(w.dec[i].p1); g.p[i].ldo16 = ldp;
     }
     r.gemm(g, true, true, EPI_BIAS_TANH_BF16, 1, "dec_proj0");
     for (int i = 0; i < M; ++i) {
-      g.p[i] = gp_fwd(r.W<bf16_t>(p.dec[i].p1), ldp, wpk, x[i].P2, R);
+      g.p[i] = gp_fwd(w.at<bf16_t>(w.dec[i].p1), ldp, wpk, x[i].P2, R);
       g.p[i].bias = r.P(x[i].bp2); g.p[i].resid = xin[i]; g.p[i].ldres = C;
       g.p[i].o32 = X(i, 0); g.p[i].ldc = C;
     }
     r.gemm(g, true, true, EPI_BIAS_RESID_F32, 1, "dec_proj2");
     for (int i = 0; i < M; ++i) {
-      const Plan::Dec& d = p.dec[i];
+      const Plan::Dec& d = w.dec[i];
       lb.p[i].x = X(i, 0); lb.p[i].gamma = r.P(x[i].ln2w); lb.p[i].beta = r.P(x[i].ln2b);
-      lb.p[i].y = r.W<bf16_t>(d.a16); lb.p[i].mean = r.W<float>(d.mean); lb.p[i].rstd = r.W<float>(d.rstd);
+      lb.p[i].y = w.at<bf16_t>(d.a16); lb.p[i].mean = w.at<float>(d.mean); lb.p[i].rstd = w.at<float>(d.rstd);
     }
     r.ok(mmt_launch_ln_fwd(lb, R, C, r.s), "dec_ln2");
     for (int i = 0; i < M; ++i) {
-      g.p[i] = gp_fwd(r.W<bf16_t>(p.dec[i].a16), C, wpk, x[i].F0, R);
-      g.p[i].bias = r.P(x[i].bf0); g.p[i].o16 = r.W<bf16_t>(p.dec[i].f); g.p[i].ldo16 = 4 * C;
+      g.p[i] = gp_fwd(w.at<bf16_t>(w.dec[i].a16), C, wpk, x[i].F0, R);
+      g.p[i].bias = r.P(x[i].bf0); g.p[i].o16 = w.at<bf16_t>(w.dec[i].f); g.p[i].ldo16 = 4 * C;
     }
     r.gemm(g, true, true, EPI_BIAS_RELU_BF16, 1, "dec_ffn0");
     for (int i = 0; i < M; ++i) {
-      g.p[i] = gp_fwd(r.W<bf16_t>(p.dec[i].f), 4 * C, wpk, x[i].F2, R);
+      g.p[i] = gp_fwd(w.at<bf16_t>(w.dec[i].f), 4 * C, wpk, x[i].F2, R);
       g.p[i].bias = r.P(x[i].bf2); g.p[i].resid = X(i, 0); g.p[i].ldres = C;
       g.p[i].o32 = X(i, 1); g.p[i].ldc = C;
-      if (c->any_cross) { g.p[i].o16 = r.W<bf16_t>(p.dec[i].x2h); g.p[i].ldo16 = C; }
+      if (c->any_cross) { g.p[i].o16 = w.at<bf16_t>(w.dec[i].x2h); g.p[i].ldo16 = C; }
     }
     r.gemm(g, true, true, EPI_BIAS_RESID_F32, 1, "dec_ffn2");
     std::vector<const float*> xout(M);
@@ -1513,11 +1598,11 @@ int run_decode(mmt_ctx* c, Runner& r, int t, const int64_t* const* idx, float* c
       GemmBatch gq{}; gq.count = (int)cx.size();
       for (size_t u = 0; u < cx.size(); ++u) {
         const int i = cx[u];
-        const Plan::Dec& d = p.dec[i];
+        const Plan::Dec& d = w.dec[i];
         lc.p[u].x = X(i, 1); lc.p[u].gamma = r.P(x[i].lncw); lc.p[u].beta = r.P(x[i].lncb);
-        lc.p[u].y = r.W<bf16_t>(d.d16); lc.p[u].mean = r.W<float>(d.mean); lc.p[u].rstd = r.W<float>(d.rstd);
-        gq.p[u] = gp_fwd(r.W<bf16_t>(d.d16), C, wpk, x[i].Wq, R);
-        gq.p[u].o16 = r.W<bf16_t>(d.qc); gq.p[u].ldo16 = C;
+        lc.p[u].y = w.at<bf16_t>(d.d16); lc.p[u].mean = w.at<float>(d.mean); lc.p[u].rstd = w.at<float>(d.rstd);
+        gq.p[u] = gp_fwd(w.at<bf16_t>(d.d16), C, wpk, x[i].Wq, R);
+        gq.p[u].o16 = w.at<bf16_t>(d.qc); gq.p[u].ldo16 = C;
       }
       r.ok(mmt_launch_ln_fwd(lc, R, C, r.s), "dec_lnc");
       r.gemm(gq, true, true, EPI_STORE_BF16, 1, "dec_ca_q");
@@ -1526,33 +1611,50 @@ int run_decode(mmt_ctx* c, Runner& r, int t, const int64_t* const* idx, float* c
         int jj = 0;
         for (int j = 0; j < M; ++j) {
           if (j == i) continue;
-          gk.p[gk.count] = gp_fwd(r.W<bf16_t>(p.dec[j].x2h), C, wpk, x[i].Wkv[jj], R);
-          gk.p[gk.count].o16 = r.W<bf16_t>(p.dec[i].kv[jj]); gk.p[gk.count].ldo16 = 2 * C;
+          gk.p[gk.count] = gp_fwd(w.at<bf16_t>(w.dec[j].x2h), C, wpk, x[i].Wkv[jj], R);
+          gk.p[gk.count].o16 = w.at<bf16_t>(w.dec[i].kv[jj]); gk.p[gk.count].ldo16 = 2 * C;
           ++gk.count; ++jj;
           if (gk.count == MMT_MAX_GROUP) { r.gemm(gk, true, true, EPI_STORE_BF16, 1, "dec_ca_kv"); gk.count = 0; }
         }
       }
       if (gk.count) r.gemm(gk, true, true, EPI_STORE_BF16, 1, "dec_ca_kv");
-      DecodeAttnBatch cb{}; cb.count = (int)cx.size();
-      for (size_t u = 0; u < cx.size(); ++u) {
+      if (w.fan) {
+        FanoutAttnBatch fb{}; fb.count = (int)cx.size();
+        for (size_t u = 0; u < cx.size(); ++u) {
+          const int i = cx[u];
+          FanoutAttnProblem& q = fb.p[u];
+          q.q = w.at<bf16_t>(w.dec[i].qc); q.q_ld = C;
+          for (int j = 0; j < M - 1; ++j) {
+            const bf16_t* kv = r.W<bf16_t>(a[i].kv[j]);
+            bf16_t* tail = w.at<bf16_t>(w.fan->ca_tail[((size_t)l * M + i) * MAXM + j]);
+            tail_append(tail, 2 * C, w.at<bf16_t>(w.dec[i].kv[j]), "fan_cakv_append");
+            q.k[j] = kv; q.v[j] = kv + hs; q.tk[j] = tail; q.tv[j] = tail + hs;
+          }
+          q.kv_ld = 2 * C; q.kv_hstride = 2 * hs; q.tail_ld = 2 * C;
+          q.o = w.at<bf16_t>(w.dec[i].oc); q.o_ld = C; q.nstreams = M - 1;
+        }
+        r.ok(mmt_launch_attn_decode_fanout(fb, B, w.S, w.n0, t, T, H, hs, tail_rows, scale, r.s), "fan_ca_attn");
+      }
+      DecodeAttnBatch cb{}; cb.count = w.fan ? 0 : (int)cx.size();
+      for (size_t u = 0; u < (size_t)cb.count; ++u) {
         const int i = cx[u];
         DecodeAttnProblem& q = cb.p[u];
-        q.q = r.W<bf16_t>(p.dec[i].qc); q.q_ld = C;
+        q.q = w.at<bf16_t>(w.dec[i].qc); q.q_ld = C;
         for (int j = 0; j < M - 1; ++j) {
           bf16_t* kv = r.W<bf16_t>(a[i].kv[j]);
-          scatter_rows(kv, 2 * C, r.W<bf16_t>(p.dec[i].kv[j]), "dec_cakv_append");
+          scatter_rows(kv, 2 * C, w.at<bf16_t>(w.dec[i].kv[j]), "dec_cakv_append");
           q.k[j] = kv; q.v[j] = kv + hs;
         }
-        q.kv_ld = 2 * C; q.kv_hstride = 2 * hs; q.o = r.W<bf16_t>(p.dec[i].oc); q.o_ld = C; q.nstreams = M - 1;
+        q.kv_ld = 2 * C; q.kv_hstride = 2 * hs; q.o = w.at<bf16_t>(w.dec[i].oc); q.o_ld = C; q.nstreams = M - 1;
       }
       r.ok(mmt_launch_attn_decode(cb, B, t, T, H, hs, scale, r.s), "dec_ca_attn");
       GemmBatch g0{}; g0.count = (int)cx.size();
       GemmBatch g2{}; g2.count = (int)cx.size();
       for (size_t u = 0; u < cx.size(); ++u) {
         const int i = cx[u];
-        g0.p[u] = gp_fwd(r.W<bf16_t>(p.dec[i].oc), C, wpk, x[i].C0, R);
-        g0.p[u].bias = r.P(x[i].bc0); g0.p[u].o16 = r.W<bf16_t>(p.dec[i].pc); g0.p[u].ldo16 = ldp;
-        g2.p[u] = gp_fwd(r.W<bf16_t>(p.dec[i].pc), ldp, wpk, x[i].C2, R);
+        g0.p[u] = gp_fwd(w.at<bf16_t>(w.dec[i].oc), C, wpk, x[i].C0, R);
+        g0.p[u].bias = r.P(x[i].bc0); g0.p[u].o16 = w.at<bf16_t>(w.dec[i].pc); g0.p[u].ldo16 = ldp;
+        g2.p[u] = gp_fwd(w.at<bf16_t>(w.dec[i].pc), ldp, wpk, x[i].C2, R);
         g2.p[u].bias = r.P(x[i].bc2); g2.p[u].resid = X(i, 1); g2.p[u].ldres = C;
         g2.p[u].o32 = X(i, 2); g2.p[u].ldc = C;
         xout[i] = X(i, 2);
@@ -1567,12 +1669,12 @@ int run_decode(mmt_ctx* c, Runner& r, int t, const int64_t* const* idx, float* c
   GemmBatch h0{}; h0.count = M;
   GemmBatch h2{}; h2.count = M;
   for (int i = 0; i < M; ++i) {
-    const Plan::Dec& d = p.dec[i];
+    const Plan::Dec& d = w.dec[i];
     lf.p[i].x = xin[i]; lf.p[i].gamma = r.P(c->post[i].lnw); lf.p[i].beta = r.P(c->post[i].lnb);
-    lf.p[i].y = r.W<bf16_t>(d.lnf16); lf.p[i].mean = r.W<float>(d.mean); lf.p[i].rstd = r.W<float>(d.rstd);
-    h0.p[i] = gp_fwd(r.W<bf16_t>(d.lnf16), C, wpk, c->post[i].H0, R);
-    h0.p[i].bias = r.P(c->post[i].b0); h0.p[i].o16 = r.W<bf16_t>(d.hh); h0.p[i].ldo16 = c->ldvh[i];
-    h2.p[i] = gp_fwd(r.W<bf16_t>(d.hh), c->ldvh[i], wpk, c->post[i].H2, R);
+    lf.p[i].y = w.at<bf16_t>(d.lnf16); lf.p[i].mean = w.at<float>(d.mean); lf.p[i].rstd = w.at<float>(d.rstd);
+    h0.p[i] = gp_fwd(w.at<bf16_t>(d.lnf16), C, wpk, c->post[i].H0, R);
+    h0.p[i].bias = r.P(c->post[i].b0); h0.p[i].o16 = w.at<bf16_t>(d.hh); h0.p[i].ldo16 = c->ldvh[i];
+    h2.p[i] = gp_fwd(w.at<bf16_t>(d.hh), c->ldvh[i], wpk, c->post[i].H2, R);
     h2.p[i].bias = r.P(c->post[i].b2); h2.p[i].o32 = logits[i]; h2.p[i].ldc = c->V[i];
   }
   r.ok(mmt_launch_ln_fwd(lf, R, C, r.s), "dec_lnf");
@@ -2116,6 +2218,7 @@ int64_t mmt_workspace_bytes(mmt_ctx* c, int32_t batch) {
   c->last_B = batch;
   c->fwd_ready = false;
   c->cache_ready = false;
+  c->fan_next = -1;
   return (int64_t)c->plan.total;
 }
 
@@ -2144,6 +2247,7 @@ int mmt_forward(mmt_ctx* c, void* stream, int32_t batch, const int64_t* const* i
   c->fwd_drop = r.drop;
   c->fwd_seed = r.seed;
   c->fwd_ready = false;
+  c->fan_next = -1;  // a new prefill ends a fan-out run
   for (int i = 0; i < c->M; ++i) c->last_idx[i] = idx[i];
   rc = run_forward(c, r, idx, tgt, logits, losses);
   if (rc == MMT_OK && tgt) c->fwd_ready = true;
@@ -2170,7 +2274,54 @@ int mmt_decode_step(mmt_ctx* c, void* stream, int32_t batch, int32_t pos, const 
                                   "would not reproduce: re-run mmt_forward per token");
   if (pos < 1 || pos >= c->T) return fail(c, MMT_ERR_INVALID, "mmt_decode_step: position outside 1..block_size-1");
   Runner r{c, (hipStream_t)stream, workspace, params, nullptr, batch, batch};
-  return run_decode(c, r, pos, idx, logits);
+  const DecWhere w{static_cast<char*>(workspace), c->plan.dec, c->plan.dec_x.data(), batch};
+  return run_decode(c, r, w, pos, idx, logits);
+}
+
+int64_t mmt_fanout_bytes(mmt_ctx* c, int32_t batch, int32_t samples, int32_t max_new) {
+  if (!c) return -1;
+  FanPlan f;
+  if (!make_fan_plan(c, f, batch, samples, max_new)) return -1;
+  return (int64_t)f.total;
+}
+
+int mmt_decode_fanout_step(mmt_ctx* c, void* stream, int32_t batch, int32_t samples, int32_t n0, int32_t max_new,
+                           int32_t pos, const int64_t* const* idx, const float* params, float* const* logits,
+                           const void* workspace, void* fan) {
+  if (!c) return MMT_ERR_INVALID;
+  const char* me = "mmt_decode_fanout_step";
+  if (!idx || !params || !logits || !workspace || !fan) return fail(c, MMT_ERR_INVALID, std::string(me) + ": null argument");
+  if (c->plan.B != batch || !c->cache_ready)
+    return fail(c, MMT_ERR_STATE, std::string(me) + ": run mmt_forward (prefill) on this batch and workspace first");
+  if (c->onchip == 3)
+    return fail(c, MMT_ERR_INVALID, std::string(me) + ": the last forward (training != 0) kept the self-attention Q/K/V "
+                                    "on chip, so the workspace holds no K/V cache: run the prefill with training = 0");
+  if (c->fwd_drop)
+    return fail(c, MMT_ERR_STATE, std::string(me) + ": the prefill forward sampled dropout (training mode); decode has "
+                                  "eval semantics: run the prefill with training = 0");
+  if (c->fp8)
+    return fail(c, MMT_ERR_STATE, std::string(me) + ": precision fp8 prefills with MX-fp8 GEMMs the bf16 decode would "
+                                  "not reproduce");
+  if (samples < 1 || n0 < 1 || max_new < 1 || (int64_t)n0 + max_new > c->T)
+    return fail(c, MMT_ERR_INVALID, std::string(me) + ": need samples >= 1, n0 >= 1, max_new >= 1, n0 + max_new <= block_size");
+  if (pos < n0 || pos >= n0 + max_new) return fail(c, MMT_ERR_INVALID, std::string(me) + ": position outside n0..n0+max_new-1");
+  const bool same = c->fan.B == batch && c->fan.S == samples && c->fan.max_new == max_new;
+  if (pos != n0 && (!same || c->fan_next != pos || c->fan_n0 != n0 || c->fan_S != samples))
+    return fail(c, MMT_ERR_STATE, std::string(me) + ": a run starts at pos == n0 and continues one position at a time "
+                                  "with the same batch, samples, n0 and max_new");
+  if (!same) {  // a run with another buffer shape starts
+    FanPlan f;
+    if (!make_fan_plan(c, f, batch, samples, max_new))
+      return fail(c, MMT_ERR_INVALID, std::string(me) + ": batch * samples rows exceed the launchers' range");
+    c->fan = std::move(f);
+  }
+  c->fan_next = -1;
+  Runner r{c, (hipStream_t)stream, const_cast<void*>(workspace), params, nullptr, batch, batch * samples};
+  DecWhere w{static_cast<char*>(fan), c->fan.dec, c->fan.dec_x.data(), batch * samples};
+  w.fan = &c->fan; w.S = samples; w.n0 = n0;
+  const int rc = run_decode(c, r, w, pos, idx, logits);
+  if (rc == MMT_OK) { c->fan_n0 = n0; c->fan_S = samples; c->fan_next = pos + 1; }
+  return rc;
 }
 
 int32_t mmt_backward_stage_count(const mmt_ctx* c) { return c ? c->L + 2 : 0; }

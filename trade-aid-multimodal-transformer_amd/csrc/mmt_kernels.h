@@ -315,6 +315,24 @@ struct DecodeAttnBatch { DecodeAttnProblem p[MMT_MAX_GROUP]; int count; };
 hipError_t mmt_launch_attn_decode(const DecodeAttnBatch& b, int B, int t, int T, int H, int hs, float scale,
                                   hipStream_t s);
 
+// Sample fan-out decode attention (generate with num_samples, mmt_decode_fanout.hip): compact row r = b*S + s is
+// sample s of prompt b; keys / values of positions < n0 are the cache rows b*T + p (read once per group of
+// MMT_FANOUT_G samples), positions n0..t the tail rows r*tail_rows + (p - n0) of tk / tv (head stride kv_hstride)
+#define MMT_FANOUT_G 16
+struct FanoutAttnProblem {
+  const bf16_t* q; int q_ld;                 // [B*S, *] compact
+  const bf16_t* k[MMT_MAX_STREAMS];
+  const bf16_t* v[MMT_MAX_STREAMS];          // cache [B*T, kv_ld]
+  const bf16_t* tk[MMT_MAX_STREAMS];
+  const bf16_t* tv[MMT_MAX_STREAMS];         // tails [B*S*tail_rows, tail_ld]
+  int kv_ld, kv_hstride, tail_ld;
+  bf16_t* o; int o_ld;                       // [B*S, *] compact
+  int nstreams;
+};
+struct FanoutAttnBatch { FanoutAttnProblem p[MMT_MAX_GROUP]; int count; };
+hipError_t mmt_launch_attn_decode_fanout(const FanoutAttnBatch& b, int B, int S, int n0, int t, int T, int H, int hs,
+                                         int tail_rows, float scale, hipStream_t s);
+
 // ------------------------------------------------------------------------------------------
 // Per-head Q/K/V stage 2: block-diagonal [hs/2 -> hs] maps (model.py:39,44,49), nblk = 3*H.
 //   out[r, blk*hs + o] = sum_i W2[blk][o][i] * h1[r, blk*hs/2 + i]

@@ -241,6 +241,34 @@ int mmt_op_attention_decode(void* stream, int32_t B, int32_t t, int32_t T, int32
   return st(mmt_launch_attn_decode(b, B, t, T, H, hs, scale, (hipStream_t)stream));
 }
 
+// sample fan-out decode attention (mmt_decode_fanout.hip), the launcher mmt_decode_fanout_step calls; the same
+// checks as above, before any launch, plus the fan-out's own
+int mmt_op_attention_decode_fanout(void* stream, int32_t B, int32_t samples, int32_t n0, int32_t t, int32_t T,
+                                   int32_t H, int32_t hs, int32_t nstreams, const void* q, int32_t q_ld,
+                                   const void* const* k, const void* const* v, int32_t kv_ld, int32_t kv_hstride,
+                                   const void* const* tail_k, const void* const* tail_v, int32_t tail_ld,
+                                   int32_t tail_rows, void* o, int32_t o_ld) {
+  if (!q || !k || !v || !tail_k || !tail_v || !o || B < 1 || H < 1 || samples < 1) return MMT_ERR_INVALID;
+  if (nstreams < 1 || nstreams > MMT_MAX_STREAMS || t < 0 || t >= T) return MMT_ERR_INVALID;
+  if (n0 < 1 || n0 > t || tail_rows < 1 || t - n0 >= tail_rows) return MMT_ERR_INVALID;
+  if (hs != 8 && hs != 16 && hs != 24 && hs != 32 && hs != 48 && hs != 64) return MMT_ERR_UNSUPPORTED;
+  if ((q_ld & 7) || (kv_ld & 7) || (kv_hstride & 7) || (tail_ld & 7)) return MMT_ERR_INVALID;  // 16-byte loads
+  for (int j = 0; j < nstreams; ++j)
+    if (!k[j] || !v[j] || !tail_k[j] || !tail_v[j]) return MMT_ERR_INVALID;
+  FanoutAttnBatch b{};
+  b.count = 1;
+  FanoutAttnProblem& p = b.p[0];
+  p.q = (const bf16_t*)q; p.q_ld = q_ld; p.kv_ld = kv_ld; p.kv_hstride = kv_hstride; p.tail_ld = tail_ld;
+  p.nstreams = nstreams;
+  for (int j = 0; j < nstreams; ++j) {
+    p.k[j] = (const bf16_t*)k[j]; p.v[j] = (const bf16_t*)v[j];
+    p.tk[j] = (const bf16_t*)tail_k[j]; p.tv[j] = (const bf16_t*)tail_v[j];
+  }
+  p.o = (bf16_t*)o; p.o_ld = o_ld;
+  const float scale = 1.0f / __builtin_sqrtf((float)hs);
+  return st(mmt_launch_attn_decode_fanout(b, B, samples, n0, t, T, H, hs, tail_rows, scale, (hipStream_t)stream));
+}
+
 // hs-32 self-attention with Q / K / V made on chip from the stage-1 rows (AttnProblem::oc_*)
 int mmt_op_attention_fwd_h1(void* stream, int32_t B, int32_t T, int32_t H, const void* h1, int32_t ld_h1, const float* w2,
                             void* o, int32_t o_ld, float* lse) {

@@ -37,6 +37,19 @@ from config_utils import (_get_block_size, _get_deterministic, _get_dropout, _ge
                           _get_precision)
 
 
+def check_num_samples(num_samples):
+    """generate's num_samples: an integer >= 1 (a bool is none)."""
+    if isinstance(num_samples, bool) or not isinstance(num_samples, int) or num_samples < 1:
+        raise ValueError(f"generate: num_samples must be an integer >= 1 or None, got {num_samples!r}")
+    return num_samples
+
+
+def tile_prompts(idx_list, num_samples):
+    """The row order of generate(num_samples=S): row b*S + s of every returned tensor is sample s of prompt b,
+    i.e. each prompt repeated S times in place."""
+    return [p.repeat_interleave(num_samples, 0) for p in idx_list]
+
+
 class _MmtStep(torch.autograd.Function):
     """One forward through the C-ABI; its backward is mmt_backward into a fresh flat grad (or, with
     set_grad_accumulation on, in place into flat_params.grad: then no gradient is returned for `flat`)."""
@@ -123,6 +136,8 @@ class MultimodalTransformer(nn.Module):
         self._ws = None
         self._ws_batch = -1
         self._ws_bytes = {}
+        self._fan = None  # the fan buffer of _decode_fanout_step
+        self.last_generate_path = None  # generate(num_samples=...): "fanout" or "tiled", whichever ran last
         self._gen = 0
         self._last = None
         self._grad_sync = None  # mmt_dist.GradSync when data parallel
@@ -490,7 +505,8 @@ class MultimodalTransformer(nn.Module):
 
     @torch.no_grad()
     def generate(self, idx_list, max_new_tokens=1, modality_to_generate=0, use_cache=True, sample_fn=None, *,
-                 temperature=None, top_k=None, top_p=None, seed=None, return_logprobs=False, logits_hook=None):
+                 temperature=None, top_k=None, top_p=None, seed=None, return_logprobs=False, logits_hook=None,
+                 num_samples=None):
         """model.py:404-446: per new token, the logits of the last position of the (block_size
         cropped) context, a sample from the softmax of the target modality's last logits
         (torch.multinomial, as the reference; `sample_fn(probs) -> [B, 1]` overrides it), appended;
@@ -510,12 +526,25 @@ class MultimodalTransformer(nn.Module):
         device path (`_generate_device`; the rule of mmt_sample in include/mmt.h): sampling
         on the device with draws keyed by (seed, row, position), no torch generator consumed, and with
         return_logprobs=True the return value (sequences, logprobs fp32 [B, max_new_tokens]). Without them
-        the body below runs as before."""
+        the body below runs as before.
+
+        num_samples=S (an integer >= 1; it selects the device path too) returns S continuations of every prompt:
+        what generate([p.repeat_interleave(S, 0) for p in prompts], ...) returns, row b*S + s being sample s of
+        prompt b with its draw at position n keyed by (seed, b*S + s, n), but from ONE prefill over the B prompts
+        and decode steps over B*S rows that share each prompt's keys / values (`_generate_fanout`,
+        mmt_decode_fanout_step). That engine runs with use_cache, in eval mode or without dropout, at bf16, for
+        prompts of one length n0 >= 1 with n0 + max_new_tokens <= block_size; otherwise the prompts are tiled and
+        the device path runs as without the keyword. `last_generate_path` says which ran: "fanout" or "tiled"."""
+        if num_samples is not None:
+            num_samples = check_num_samples(num_samples)
         if not (temperature is None and top_k is None and top_p is None and seed is None and not return_logprobs
-                and logits_hook is None):
+                and logits_hook is None and num_samples is None):
             if sample_fn is not None:
                 raise ValueError("generate: sample_fn cannot be combined with temperature / top_k / top_p / seed / "
-                                 "return_logprobs / logits_hook (the device path samples on the GPU)")
+                                 "return_logprobs / logits_hook / num_samples (the device path samples on the GPU)")
+            if num_samples is not None:
+                return self._generate_samples(idx_list, max_new_tokens, modality_to_generate, use_cache, temperature,
+                                              top_k, top_p, seed, return_logprobs, logits_hook, num_samples)
             return self._generate_device(idx_list, max_new_tokens, modality_to_generate, use_cache, temperature, top_k,
                                          top_p, seed, return_logprobs, logits_hook)
         seqs = [idx.clone() for idx in idx_list]
@@ -646,6 +675,82 @@ class MultimodalTransformer(nn.Module):
         return (seqs, lp) if return_logprobs else seqs
 
     @torch.no_grad()
+    def _generate_samples(self, idx_list, max_new_tokens, g, use_cache, temperature, top_k, top_p, seed,
+                          return_logprobs, logits_hook, S):
+        """generate(num_samples=S): the fan-out engine where it applies (the conditions in generate's docstring),
+        else the device path over the tiled prompts, which is the definition of the result."""
+        N, T = int(max_new_tokens), self.block_size
+        shapes = [tuple(s.shape) for s in idx_list]
+        fan = (use_cache and not (self.training and self.dropout_p > 0.0) and self.precision == "bf16"
+               and len(idx_list) == self.num_modalities and 0 <= g < self.num_modalities
+               and all(len(sh) == 2 for sh in shapes) and len(set(shapes)) == 1 and shapes[0][1] >= 1
+               and shapes[0][1] + N <= T and N >= 1 and self.flat_params.device.type == "cuda")
+        if not fan:
+            self.last_generate_path = "tiled"
+            return self._generate_device(tile_prompts(idx_list, S), max_new_tokens, g, use_cache, temperature, top_k,
+                                         top_p, seed, return_logprobs, logits_hook)
+        self.last_generate_path = "fanout"
+        return self._generate_fanout(idx_list, N, g, temperature, top_k, top_p, seed, return_logprobs, logits_hook, S)
+
+    @torch.no_grad()
+    def _generate_fanout(self, idx_list, N, g, temperature, top_k, top_p, seed, return_logprobs, logits_hook, S):
+        """S samples per prompt from one prefill (mmt_decode_fanout_step, include/mmt.h). The prefill runs over the
+        B prompts; its last-position logits, one row per prompt, are expanded to [B*S, V] once and sampled in one
+        mmt_sample launch (row r = b*S + s, position n0). From then on a token costs one fan-out decode step over
+        B*S rows, which reads the prompts' keys / values from the prefill's workspace and keeps the samples' own in
+        the fan buffer, and one mmt_sample launch: no torch op, no sync. Buffers as in `_generate_device`, with
+        B*S rows."""
+        import mmt_sample as MS
+        t, k, p = MS.check_settings(temperature, top_k, top_p)
+        flat = self.flat_params
+        dev = flat.device
+        M = self.num_modalities
+        seed = MS.device_seed(dev) if seed is None else int(seed) & MS.MASK64
+        V = self.vocab_sizes[g]
+        prompts = [s.to(device=dev, dtype=torch.long).contiguous() for s in idx_list]
+        B, n0 = prompts[0].shape
+        R, cap = B * S, n0 + N
+        L = ML.lib()
+        nbytes = L.mmt_fanout_bytes(self._ctx, B, S, N)
+        if nbytes < 0:
+            raise ValueError(f"generate: {B} prompts x {S} samples are more rows than the decode launches address")
+        bufs = []
+        for i, s in enumerate(tile_prompts(prompts, S)):
+            buf = torch.zeros(R, cap, dtype=torch.long, device=dev)
+            buf[:, :n0] = s
+            if i != g:
+                buf[:, n0:] = s[:, -1:]
+            bufs.append(buf)
+        lp = torch.empty(R, N, dtype=torch.float32, device=dev) if return_logprobs else None
+        compact = torch.zeros(R, dtype=torch.long, device=dev)
+        tok_base, lp_base = bufs[g].data_ptr(), (lp.data_ptr() if lp is not None else 0)
+        logits, _ = self(prompts)  # the prefill: leaves every prompt position's keys / values in the workspace
+        rows = torch.arange(B, device=dev).repeat_interleave(S)
+        first = logits[g][:, -1, :].index_select(0, rows)  # [B*S, V]: each sample's copy of its prompt's row
+        fan = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        dec_idx = [compact if i == g else bufs[i][:, n0 - 1].contiguous() for i in range(M)]
+        dec_logits = [torch.empty(R, Vi, dtype=torch.float32, device=dev) for Vi in self.vocab_sizes]
+        p_idx, p_logits, p_flat, p_ws, p_fan = (ML.ptr_array(dec_idx), ML.ptr_array(dec_logits), ML.ptr(flat),
+                                                ML.ptr(self._ws), ML.ptr(fan))
+        with torch.cuda.device(dev):
+            stream = ML.stream_ptr(dev)
+            for j in range(N):
+                n = n0 + j
+                if j == 0:
+                    last = first
+                else:
+                    rc = L.mmt_decode_fanout_step(self._ctx, stream, B, S, n0, N, n - 1, p_idx, p_flat, p_logits, p_ws,
+                                                  p_fan)
+                    ML.check(rc, self._ctx, "mmt_decode_fanout_step")
+                    last = dec_logits[g]
+                if logits_hook is not None:
+                    logits_hook(n, last)
+                MS.launch(L, stream, R, V, last.data_ptr(), V, t, k, p, seed, 0, n, tok_base + 8 * n, cap,
+                          compact.data_ptr(), lp_base + 4 * j if lp_base else 0, N)
+        seqs = [buf.to(idx_list[i].dtype) for i, buf in enumerate(bufs)]
+        return (seqs, lp) if return_logprobs else seqs
+
+    @torch.no_grad()
     def _decode_step(self, tokens, pos):
         """Logits [B, V_i] of every modality at position `pos` (1 <= pos < block_size), given the
         tokens [B] of that position; the workspace must hold positions < pos (a forward over them,
@@ -663,6 +768,34 @@ class MultimodalTransformer(nn.Module):
                                    ML.ptr_array(logits), ML.ptr(self._ws))
         ML.check(rc, self._ctx, "mmt_decode_step")
         self._gen += 1
+        self._keep_decode = idx  # alive until the step's kernels have read them
+        return logits
+
+    @torch.no_grad()
+    def _decode_fanout_step(self, tokens, pos, samples, n0, max_new):
+        """Logits [B*S, V_i] of every modality at position `pos` of the B*S sample rows (row b*S + s), given their
+        tokens [B*S]; the workspace must hold a prefill of the B prompts (positions < n0), and the steps run
+        n0, n0 + 1, ... in order (include/mmt.h mmt_decode_fanout_step). The fan buffer is kept on the model from
+        the step at n0 on."""
+        flat = self.flat_params
+        dev = flat.device
+        R = tokens[0].shape[0]
+        B = R // samples
+        if self._ws is None or self._ws_batch != B or B * samples != R:
+            raise RuntimeError("_decode_fanout_step: no prefill forward at this batch size")
+        L = ML.lib()
+        nbytes = L.mmt_fanout_bytes(self._ctx, B, samples, max_new)
+        if nbytes < 0:
+            raise ValueError("_decode_fanout_step: batch, samples or max_new out of range")
+        if pos == n0 or self._fan is None or self._fan.numel() != nbytes or self._fan.device != dev:
+            self._fan = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        idx = [t.to(device=dev, dtype=torch.long).contiguous() for t in tokens]
+        logits = [torch.empty(R, V, dtype=torch.float32, device=dev) for V in self.vocab_sizes]
+        with torch.cuda.device(dev):
+            rc = L.mmt_decode_fanout_step(self._ctx, ML.stream_ptr(dev), B, samples, n0, max_new, int(pos),
+                                          ML.ptr_array(idx), ML.ptr(flat), ML.ptr_array(logits), ML.ptr(self._ws),
+                                          ML.ptr(self._fan))
+        ML.check(rc, self._ctx, "mmt_decode_fanout_step")
         self._keep_decode = idx  # alive until the step's kernels have read them
         return logits
 
