@@ -20,6 +20,7 @@
  *                                    with a KV cache instead of the reference's full re-forward
  *   mmt_sample                    <- the sampling line of generate (model.py:425-427: softmax + multinomial),
  *                                    extended by temperature, top-k, top-p, seeded draws and log-probabilities
+ *   mmt_sample_multi              <- the same line for several modalities of one step (a joint rollout), one launch
  *   mmt_eval_direction            <- the per-sample loop of calculate_evaluation_metrics
  *                                    (training_utils.py:259-304)
  *   mmt_op_*                      primitive kernels, exported for kernel-level parity tests.
@@ -162,6 +163,31 @@ int mmt_sample(void* stream, int32_t batch, int32_t V, const float* logits, int6
                int32_t top_k, float top_p, uint64_t seed, uint32_t row0, uint32_t pos, int64_t* tok,
                int64_t tok_stride, int64_t* tok_compact /* nullable */, float* logprob /* nullable */,
                int64_t lp_stride);
+
+/* Several heads of one step in ONE launch (a joint rollout of generate samples every generated modality per token;
+ * at C1 a decode token is launch-bound, so G launches of mmt_sample are G - 1 too many): `count` independent
+ * problems over the same `batch` rows, `row0` and `pos`, grid (rows, problems). Every other argument of mmt_sample
+ * is a HOST array of `count` entries, read during the call (as the pointer arrays of mmt_forward): V, logits,
+ * row_stride, temperature, top_k, top_p, seed, tok, tok_stride, tok_compact, logprob, lp_stride. The arrays
+ * tok_compact and logprob may be NULL (no problem has that output), and so may any of their entries; lp_stride is
+ * read only where logprob is given.
+ * The contract: problem p gives bit for bit what mmt_sample gives when called alone with problem p's arguments
+ * (tokens, compact tokens, log-probabilities): both kernels are one device function, and a row's result depends
+ * on nothing else in the launch. In a joint rollout problem p carries its modality's own seed (the keying rule:
+ * INTEGRATION.md, mmt_sample.modality_seed), so draws of different modalities are independent.
+ * Launches: when every V is at most 8192 (the LDS rows) and count <= 8, one. Problems with V > 8192 run the
+ * re-read variant in a SECOND launch of the same shape (no runtime branch in the kernel: the LDS rows keep their
+ * code and the re-read rows do not reserve 32 KiB of LDS); more than 8 problems of either kind go in chunks of 8.
+ * All problems are validated before any launch, each by mmt_sample's own rules, the first failing problem giving
+ * the status (MMT_ERR_INVALID, or MMT_ERR_UNSUPPORTED for V > 2^20): then nothing is written. Also
+ * MMT_ERR_INVALID: count < 0, batch < 0, with count > 0 a null V / logits / row_stride / temperature / top_k /
+ * top_p / seed / tok / tok_stride array, or logprob without lp_stride. count == 0 or batch == 0 launches nothing
+ * (batch == 0 after the validation, as mmt_sample). No knobs, no atomics, the summation trees of mmt_sample. */
+int mmt_sample_multi(void* stream, int32_t count, int32_t batch, const int32_t* V, const float* const* logits,
+                     const int64_t* row_stride, const float* temperature, const int32_t* top_k, const float* top_p,
+                     const uint64_t* seed, uint32_t row0, uint32_t pos, int64_t* const* tok,
+                     const int64_t* tok_stride, int64_t* const* tok_compact /* nullable, entries nullable */,
+                     float* const* logprob /* nullable, entries nullable */, const int64_t* lp_stride);
 
 /* failure detection (the reference's guard is the NaN check on eval losses,
  * main.py:606): byte offset in the workspace of two int32 bitmasks (the same for every batch size;

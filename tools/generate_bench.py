@@ -14,6 +14,10 @@ own per vocabulary size and setting. One JSON line per run.
 
     python tools/generate_bench.py --samples S --batch B [--paths fanout,tiled] [--attn]
 
+Joint rollouts (every modality sampled per step from its own head, one mmt_sample_multi per token): --paths
+joint,joint_topk_topp beside device,device_topk_topp; with --samples, --paths fanout_joint beside fanout.
+--sampler-multi adds the time of one mmt_sample_multi launch over the four heads against four mmt_sample launches.
+
 --samples S measures S continuations per prompt instead: `fanout` is generate(prompts, num_samples=S) and `tiled`
 the same call over the prompts repeated S times by the caller (what a checkout without the keyword can do: with
 --tree, --paths tiled). Per round it records paths per second (B * S / wall time), tokens per second and the peak
@@ -42,6 +46,8 @@ def main():
     ap.add_argument("--tree", default=REPO)
     ap.add_argument("--label", default="")
     ap.add_argument("--sampler", action="store_true", help="also time mmt_sample alone (this tree only)")
+    ap.add_argument("--sampler-multi", action="store_true",
+                    help="also time mmt_sample_multi over the four heads against four mmt_sample launches")
     ap.add_argument("--samples", type=int, default=0, help="continuations per prompt (0: the single-path benchmark)")
     ap.add_argument("--attn", action="store_true", help="with --samples: the two decode attention kernels alone")
     a = ap.parse_args()
@@ -70,6 +76,11 @@ def main():
         "device": lambda: model.generate(prompt, max_new_tokens=a.new, modality_to_generate=0, temperature=1.0, seed=11),
         "device_topk_topp": lambda: model.generate(prompt, max_new_tokens=a.new, modality_to_generate=0, temperature=0.8,
                                                    top_k=50, top_p=0.9, seed=11),
+        # joint rollouts: every modality sampled per step from its own head (one mmt_sample_multi per token)
+        "joint": lambda: model.generate(prompt, max_new_tokens=a.new, modality_to_generate="all", temperature=1.0,
+                                        seed=11),
+        "joint_topk_topp": lambda: model.generate(prompt, max_new_tokens=a.new, modality_to_generate="all",
+                                                  temperature=0.8, top_k=50, top_p=0.9, seed=11),
     }
     paths = [p for p in a.paths.split(",") if p]
     if a.samples:
@@ -93,6 +104,8 @@ def main():
            "tokens_per_s": out, "best_tokens_per_s": {p: max(v) for p, v in out.items()}}
     if a.sampler:
         res["sampler_us"] = sampler_alone(torch, dev, a.batch, a.rounds)
+    if a.sampler_multi:
+        res["sampler_multi_us"] = sampler_multi_alone(torch, dev, a.rounds)
     print(json.dumps(res), flush=True)
 
 
@@ -102,7 +115,8 @@ def fanout_bench(a, torch, dev, model, prompt, paths):
     tiled = [p.repeat_interleave(S, 0) for p in prompt]
     kw = dict(max_new_tokens=a.new, modality_to_generate=0, temperature=1.0, seed=11)
     calls = {"fanout": lambda: model.generate(prompt, num_samples=S, **kw),
-             "tiled": lambda: model.generate(tiled, **kw)}
+             "tiled": lambda: model.generate(tiled, **kw),
+             "fanout_joint": lambda: model.generate(prompt, num_samples=S, **dict(kw, modality_to_generate="all"))}
     rec = {p: {"paths_per_s": [], "tokens_per_s": [], "peak_bytes": []} for p in paths}
 
     def one(p, timed):
@@ -217,6 +231,54 @@ def sampler_alone(torch, dev, batch, rounds, reps=200):
                 us = e0.elapsed_time(e1) / reps * 1e3
                 best = us if best is None else min(best, us)
             out[f"V{V}_{name}"] = round(best, 2)
+    return out
+
+
+def sampler_multi_alone(torch, dev, rounds, reps=200):
+    """us per step of sampling all four C1 heads (V 900 / 13 / 144 / 5) over the same rows: one mmt_sample_multi
+    launch against four back-to-back mmt_sample launches, at 64 and 4096 rows, plain and with top_k=50, top_p=0.9
+    (HIP events around `reps` steps over rotating N(0, 3^2) logits, best of `rounds`; the two alternate)."""
+    import mmt_lib as ML
+    import mmt_sample
+    L, st = ML.lib(), ML.stream_ptr(dev)
+    Vs = C1["V"]
+    out = {}
+    for rows in (64, 4096):
+        toks = [torch.zeros(rows, dtype=torch.int64, device=dev) for _ in Vs]
+        lps = [torch.zeros(rows, dtype=torch.float32, device=dev) for _ in Vs]
+        bufs = [[torch.randn(rows, V, device=dev) * 3.0 for V in Vs] for _ in range(8)]
+        for name, (t, k_, p) in (("plain", (1.0, 0, 1.0)), ("top_k50_top_p0.9", (0.8, 50, 0.9))):
+            ml = mmt_sample.MultiLaunch(Vs, [(t, k_, p)] * 4, [mmt_sample.modality_seed(3, i) for i in range(4)],
+                                        [1] * 4, [1] * 4)
+            for i in range(4):
+                ml.tok[i], ml.logprob[i] = toks[i].data_ptr(), lps[i].data_ptr()
+
+            def multi(k):
+                for i in range(4):
+                    ml.logits[i] = bufs[k % 8][i].data_ptr()
+                ml.run(L, st, rows, 0, k)
+
+            def four(k):
+                for i, V in enumerate(Vs):
+                    mmt_sample.launch(L, st, rows, V, bufs[k % 8][i].data_ptr(), V, t, k_, p, int(ml.seed[i]), 0, k,
+                                      toks[i].data_ptr(), 1, 0, lps[i].data_ptr(), 1)
+
+            best = {"multi": None, "four_launches": None}
+            for _ in range(rounds):
+                for which, fn in (("multi", multi), ("four_launches", four)):
+                    for k in range(8):
+                        fn(k)
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    torch.cuda.synchronize()
+                    e0.record()
+                    for k in range(reps):
+                        fn(k)
+                    e1.record()
+                    torch.cuda.synchronize()
+                    us = e0.elapsed_time(e1) / reps * 1e3
+                    best[which] = us if best[which] is None else min(best[which], us)
+            for which, us in best.items():
+                out[f"rows{rows}_{name}_{which}"] = round(us, 2)
     return out
 
 

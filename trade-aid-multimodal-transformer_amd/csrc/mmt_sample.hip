@@ -1,5 +1,6 @@
 // Device-side sampling of generate (mmt.h: mmt_sample): temperature, top-k, top-p, a counter-hash uniform draw,
-// the token and its log-probability, one 256-thread workgroup per row, one launch for all rows.
+// the token and its log-probability, one 256-thread workgroup per row, one launch for all rows; mmt_sample_multi:
+// the same for several problems (the heads of one joint-rollout step) over the same rows, grid (rows, problems).
 //
 // No float atomics and no data-dependent summation order: every sum below runs over a fixed assignment of
 // elements to threads and a fixed tree (per-thread serial sum, xor-butterfly or shift scan inside a wave, the
@@ -84,13 +85,14 @@ __device__ __forceinline__ unsigned long long block_count3(unsigned long long v,
 // weight of an element relative to the row maximum m: 1 at the maximum (also when m is +inf), exp(z - m) below
 __device__ __forceinline__ float weight(float z, float m) { return z == m ? 1.0f : expf(z - m); }
 
+// One row: row b = blockIdx.x of one problem, the whole rule of mmt.h. Both kernels below are this body and
+// nothing else, so a problem of mmt_sample_multi gives the bits mmt_sample gives with the same arguments.
 template <bool ONCHIP>
-__global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(
-    int V, const float* __restrict__ logits, int64_t row_stride, float inv_t, int greedy, int top_k, float top_p,
-    uint32_t key, uint32_t row0, uint32_t pos, int64_t* __restrict__ tok, int64_t tok_stride,
-    int64_t* __restrict__ tok_compact, float* __restrict__ logprob, int64_t lp_stride) {
-  __shared__ float zs[ONCHIP ? SAMPLE_ONCHIP : 1];
-  __shared__ SampleShared sh;
+__device__ __forceinline__ void sample_row(
+    float* __restrict__ zs, SampleShared& sh, int V, const float* __restrict__ logits, int64_t row_stride,
+    float inv_t, int greedy, int top_k, float top_p, uint32_t key, uint32_t row0, uint32_t pos,
+    int64_t* __restrict__ tok, int64_t tok_stride, int64_t* __restrict__ tok_compact, float* __restrict__ logprob,
+    int64_t lp_stride) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int b = blockIdx.x;
   const float* row = logits + (int64_t)b * row_stride;
@@ -250,6 +252,54 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(
   }
 }
 
+template <bool ONCHIP>
+__global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(
+    int V, const float* __restrict__ logits, int64_t row_stride, float inv_t, int greedy, int top_k, float top_p,
+    uint32_t key, uint32_t row0, uint32_t pos, int64_t* __restrict__ tok, int64_t tok_stride,
+    int64_t* __restrict__ tok_compact, float* __restrict__ logprob, int64_t lp_stride) {
+  __shared__ float zs[ONCHIP ? SAMPLE_ONCHIP : 1];
+  __shared__ SampleShared sh;
+  sample_row<ONCHIP>(zs, sh, V, logits, row_stride, inv_t, greedy, top_k, top_p, key, row0, pos, tok, tok_stride,
+                     tok_compact, logprob, lp_stride);
+}
+
+// mmt_sample_multi: grid (rows, problems), workgroup (b, p) is row b of problem p. The problems travel by value
+// in the kernel arguments (8 x 80 bytes); a workgroup reads its own through wave-uniform loads.
+struct SampleProblem {
+  const float* logits;
+  int64_t row_stride;
+  int64_t* tok;
+  int64_t tok_stride;
+  int64_t* tok_compact;
+  float* logprob;
+  int64_t lp_stride;
+  float inv_t, top_p;
+  int V, greedy, top_k;
+  uint32_t key;
+};
+struct SampleBatch { SampleProblem p[MMT_MAX_GROUP]; };
+
+template <bool ONCHIP>
+__global__ __launch_bounds__(SAMPLE_THREADS) void sample_multi_kernel(SampleBatch batch, uint32_t row0, uint32_t pos) {
+  __shared__ float zs[ONCHIP ? SAMPLE_ONCHIP : 1];
+  __shared__ SampleShared sh;
+  const SampleProblem& q = batch.p[blockIdx.y];
+  sample_row<ONCHIP>(zs, sh, q.V, q.logits, q.row_stride, q.inv_t, q.greedy, q.top_k, q.top_p, q.key, row0, pos, q.tok,
+                     q.tok_stride, q.tok_compact, q.logprob, q.lp_stride);
+}
+
+// mmt_sample's refusals for one problem; MMT_OK when it may launch
+int sample_check(int32_t batch, int32_t V, const float* logits, int64_t row_stride, float temperature, int32_t top_k,
+                 float top_p, const int64_t* tok) {
+  if (batch < 0 || V < 1 || row_stride < V || !(temperature >= 0.0f) || top_k < 0 || top_p != top_p)
+    return MMT_ERR_INVALID;
+  if (batch > 0 && (!logits || !tok)) return MMT_ERR_INVALID;
+  if (V > SAMPLE_MAX_V) return MMT_ERR_UNSUPPORTED;
+  return MMT_OK;
+}
+
+uint32_t sample_key(uint64_t seed) { return mmt_hash((uint32_t)seed, (uint32_t)(seed >> 32), SAMPLE_SALT); }
+
 }  // namespace
 
 extern "C" {
@@ -257,14 +307,12 @@ extern "C" {
 int mmt_sample(void* stream, int32_t batch, int32_t V, const float* logits, int64_t row_stride, float temperature,
                int32_t top_k, float top_p, uint64_t seed, uint32_t row0, uint32_t pos, int64_t* tok,
                int64_t tok_stride, int64_t* tok_compact, float* logprob, int64_t lp_stride) {
-  if (batch < 0 || V < 1 || row_stride < V || !(temperature >= 0.0f) || top_k < 0 || top_p != top_p)
-    return MMT_ERR_INVALID;
-  if (batch > 0 && (!logits || !tok)) return MMT_ERR_INVALID;
-  if (V > SAMPLE_MAX_V) return MMT_ERR_UNSUPPORTED;
+  const int rc = sample_check(batch, V, logits, row_stride, temperature, top_k, top_p, tok);
+  if (rc != MMT_OK) return rc;
   if (batch == 0) return MMT_OK;
   const int greedy = temperature == 0.0f ? 1 : 0;
   const float inv_t = greedy ? 1.0f : 1.0f / temperature;
-  const uint32_t key = mmt_hash((uint32_t)seed, (uint32_t)(seed >> 32), SAMPLE_SALT);
+  const uint32_t key = sample_key(seed);
   hipStream_t s = (hipStream_t)stream;
   if (V <= SAMPLE_ONCHIP)
     hipLaunchKernelGGL(sample_kernel<true>, dim3((unsigned)batch), dim3(SAMPLE_THREADS), 0, s, V, logits, row_stride,
@@ -273,6 +321,59 @@ int mmt_sample(void* stream, int32_t batch, int32_t V, const float* logits, int6
     hipLaunchKernelGGL(sample_kernel<false>, dim3((unsigned)batch), dim3(SAMPLE_THREADS), 0, s, V, logits, row_stride,
                        inv_t, greedy, top_k, top_p, key, row0, pos, tok, tok_stride, tok_compact, logprob, lp_stride);
   return hipGetLastError() == hipSuccess ? MMT_OK : MMT_ERR_HIP;
+}
+
+int mmt_sample_multi(void* stream, int32_t count, int32_t batch, const int32_t* V, const float* const* logits,
+                     const int64_t* row_stride, const float* temperature, const int32_t* top_k, const float* top_p,
+                     const uint64_t* seed, uint32_t row0, uint32_t pos, int64_t* const* tok, const int64_t* tok_stride,
+                     int64_t* const* tok_compact, float* const* logprob, const int64_t* lp_stride) {
+  if (count < 0 || batch < 0) return MMT_ERR_INVALID;
+  if (count == 0) return MMT_OK;
+  if (!V || !logits || !row_stride || !temperature || !top_k || !top_p || !seed || !tok || !tok_stride ||
+      (logprob && !lp_stride))
+    return MMT_ERR_INVALID;
+  for (int p = 0; p < count; ++p) {  // every problem before any launch
+    const int rc = sample_check(batch, V[p], logits[p], row_stride[p], temperature[p], top_k[p], top_p[p], tok[p]);
+    if (rc != MMT_OK) return rc;
+  }
+  if (batch == 0) return MMT_OK;
+  hipStream_t s = (hipStream_t)stream;
+  // the rows that fit LDS first, then the re-read ones (a second launch, only when there are any), each in
+  // chunks of MMT_MAX_GROUP problems in the caller's order
+  for (int large = 0; large < 2; ++large) {
+    SampleBatch sb;
+    int n = 0;
+    for (int p = 0; p <= count; ++p) {
+      if (p < count && (V[p] > SAMPLE_ONCHIP) == (large != 0)) {
+        const int greedy = temperature[p] == 0.0f ? 1 : 0;
+        SampleProblem& q = sb.p[n++];
+        q.logits = logits[p];
+        q.row_stride = row_stride[p];
+        q.tok = tok[p];
+        q.tok_stride = tok_stride[p];
+        q.tok_compact = tok_compact ? tok_compact[p] : nullptr;
+        q.logprob = logprob ? logprob[p] : nullptr;
+        q.lp_stride = logprob ? lp_stride[p] : 0;
+        q.inv_t = greedy ? 1.0f : 1.0f / temperature[p];
+        q.top_p = top_p[p];
+        q.V = V[p];
+        q.greedy = greedy;
+        q.top_k = top_k[p];
+        q.key = sample_key(seed[p]);
+      }
+      if (n == MMT_MAX_GROUP || (p == count && n > 0)) {
+        for (int k = n; k < MMT_MAX_GROUP; ++k) sb.p[k] = sb.p[0];  // never read: grid.y == n
+        const dim3 grid((unsigned)batch, (unsigned)n);
+        if (large)
+          hipLaunchKernelGGL(sample_multi_kernel<false>, grid, dim3(SAMPLE_THREADS), 0, s, sb, row0, pos);
+        else
+          hipLaunchKernelGGL(sample_multi_kernel<true>, grid, dim3(SAMPLE_THREADS), 0, s, sb, row0, pos);
+        if (hipGetLastError() != hipSuccess) return MMT_ERR_HIP;
+        n = 0;
+      }
+    }
+  }
+  return MMT_OK;
 }
 
 }  // extern "C"

@@ -6,7 +6,14 @@
 
 `model.generate(..., temperature=..., top_k=..., top_p=..., seed=...)` runs on `launch` below; `sample` is the
 same entry for users with their own decode loop. The rule is stated in include/mmt.h and INTEGRATION.md.
+
+Several heads of one step in one launch (mmt_sample_multi), as the joint rollouts of generate use it:
+
+    toks = mmt_sample.sample_multi([logits_0, logits_2], temperature=[0.8, 1.0], top_k=50,
+                                   seeds=[mmt_sample.modality_seed(1234, i) for i in (0, 2)], pos=n)
 """
+import ctypes
+
 import torch
 
 import mmt_lib as ML
@@ -72,3 +79,88 @@ def sample(logits, *, temperature=1.0, top_k=0, top_p=1.0, seed, pos, row0=0, re
         launch(ML.lib(), ML.stream_ptr(dev), B, V, logits.data_ptr(), max(int(logits.stride(0)), V) if B > 1 else V,
                t, k, p, int(seed), int(row0), int(pos), tok.data_ptr(), 1, 0, lp.data_ptr() if lp is not None else 0, 1)
     return (tok, lp) if return_logprobs else tok
+
+
+def modality_seed(seed, i):
+    """The keying rule of joint rollouts (generate with a list of modalities or "all"): the draw of modality i, row r,
+    position n is mmt_sample's draw with this seed, whatever other modalities are generated. One splitmix64 step on
+    seed + (i + 1) * 0x9E3779B97F4A7C15, all arithmetic modulo 2^64."""
+    x = (int(seed) + (int(i) + 1) * 0x9E3779B97F4A7C15) & MASK64
+    x ^= x >> 30
+    x = (x * 0xBF58476D1CE4E5B9) & MASK64
+    x ^= x >> 27
+    x = (x * 0x94D049BB133111EB) & MASK64
+    return x ^ (x >> 31)
+
+
+class MultiLaunch:
+    """The host arrays of one mmt_sample_multi call over P problems (include/mmt.h), made once and updated in place
+    between launches: a decode loop changes `logits[p]` / `row_stride[p]` / `tok[p]` / `logprob[p]` (raw addresses,
+    0 = absent) and calls `run`. settings: P triples from check_settings; seeds: P ints."""
+
+    def __init__(self, V, settings, seeds, tok_stride, lp_stride):
+        P = self.P = len(V)
+        n = max(1, P)
+        self.V = (ctypes.c_int32 * n)(*[int(v) for v in V])
+        self.temperature = (ctypes.c_float * n)(*[s[0] for s in settings])
+        self.top_k = (ctypes.c_int32 * n)(*[s[1] for s in settings])
+        self.top_p = (ctypes.c_float * n)(*[s[2] for s in settings])
+        self.seed = (ctypes.c_uint64 * n)(*[int(s) & MASK64 for s in seeds])
+        self.logits = (ctypes.c_void_p * n)()
+        self.row_stride = (ctypes.c_int64 * n)(*[int(v) for v in V])
+        self.tok = (ctypes.c_void_p * n)()
+        self.tok_stride = (ctypes.c_int64 * n)(*[int(x) for x in tok_stride])
+        self.compact = (ctypes.c_void_p * n)()
+        self.logprob = (ctypes.c_void_p * n)()
+        self.lp_stride = (ctypes.c_int64 * n)(*[int(x) for x in lp_stride])
+
+    def run(self, L, stream, batch, row0, pos):
+        """One mmt_sample_multi. Raises MmtError on a non-zero status."""
+        rc = L.mmt_sample_multi(stream, self.P, batch, self.V, self.logits, self.row_stride, self.temperature,
+                                self.top_k, self.top_p, self.seed, row0, pos, self.tok, self.tok_stride, self.compact,
+                                self.logprob, self.lp_stride)
+        if rc != 0:
+            raise ML.MmtError(f"mmt_sample_multi failed (status {rc})")
+
+
+def _per_problem(value, P, name):
+    if isinstance(value, (list, tuple)):
+        if len(value) != P:
+            raise ValueError(f"sample_multi: {name} has {len(value)} entries for {P} problems")
+        return list(value)
+    return [value] * P
+
+
+def sample_multi(logits_list, *, temperature=1.0, top_k=0, top_p=1.0, seeds, pos, row0=0, return_logprobs=False):
+    """`sample` for P problems over the same rows in one launch (mmt_sample_multi): logits_list holds P fp32 [B, V_p]
+    tensors on one GPU (rows may be strided, as for `sample`); temperature / top_k / top_p are scalars or sequences
+    of P; seeds is a sequence of P 64-bit seeds (for the modalities of a joint rollout: modality_seed(seed, i)), or
+    one int for all. Returns a list of P int64 [B] tensors, with return_logprobs also a list of P fp32 [B]. Problem p
+    gives exactly what sample(logits_list[p], ..., seed=seeds[p]) gives."""
+    P = len(logits_list)
+    ts, ks, ps = (_per_problem(temperature, P, "temperature"), _per_problem(top_k, P, "top_k"),
+                  _per_problem(top_p, P, "top_p"))
+    seeds = [int(s) for s in _per_problem(seeds, P, "seeds")]
+    settings = [check_settings(t, k, p) for t, k, p in zip(ts, ks, ps)]
+    if P == 0:
+        return ([], []) if return_logprobs else []
+    B, dev = logits_list[0].shape[0], logits_list[0].device
+    for lg in logits_list:
+        if lg.dim() != 2 or lg.dtype != torch.float32 or lg.device.type != "cuda" or lg.device != dev:
+            raise ValueError("sample_multi: every logits must be an fp32 [B, V] tensor on the same GPU")
+        if lg.shape[0] != B:
+            raise ValueError("sample_multi: the problems must share the number of rows")
+        V = lg.shape[1]
+        if V < 1 or (V > 1 and lg.stride(1) != 1) or (B > 1 and lg.stride(0) < V):
+            raise ValueError("sample_multi: the elements of a row must be contiguous and rows must not overlap")
+    toks = [torch.empty(B, dtype=torch.int64, device=dev) for _ in range(P)]
+    lps = [torch.empty(B, dtype=torch.float32, device=dev) for _ in range(P)] if return_logprobs else None
+    ml = MultiLaunch([lg.shape[1] for lg in logits_list], settings, seeds, [1] * P, [1] * P)
+    for p, lg in enumerate(logits_list):
+        ml.logits[p] = lg.data_ptr()
+        ml.row_stride[p] = max(int(lg.stride(0)), lg.shape[1]) if B > 1 else lg.shape[1]
+        ml.tok[p] = toks[p].data_ptr()
+        ml.logprob[p] = lps[p].data_ptr() if lps is not None else None
+    with torch.cuda.device(dev):
+        ml.run(ML.lib(), ML.stream_ptr(dev), B, int(row0), int(pos))
+    return (toks, lps) if return_logprobs else toks

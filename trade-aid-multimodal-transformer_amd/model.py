@@ -50,6 +50,93 @@ def tile_prompts(idx_list, num_samples):
     return [p.repeat_interleave(num_samples, 0) for p in idx_list]
 
 
+GENERATED, GIVEN, HELD = "generated", "given", "held"
+
+
+class JointPlan:
+    """What plan_joint returns for the list form of generate: `roles[i]` in (GENERATED, GIVEN, HELD), `generated`
+    the generated modalities in ascending order, `given` {modality: the caller's int64 tensor}, and the checked
+    shape: B prompts of n0 tokens, N new tokens."""
+
+    def __init__(self, roles, generated, given, B, n0, N):
+        self.roles, self.generated, self.given, self.B, self.n0, self.N = roles, generated, given, B, n0, N
+
+
+def plan_joint(modality_to_generate, given, vocab_sizes, prompt_shapes, max_new_tokens, num_samples=None):
+    """generate's `modality_to_generate` and `given` as per-modality roles, every refusal of the list form that
+    needs no device in one place. An int (the int form: one modality sampled, generate as it always ran) returns
+    None, and refuses `given`. A sequence of distinct ints, even of one, or "all" is the list form (a joint
+    rollout): those modalities are GENERATED, the keys of `given` are GIVEN (tokens supplied by the caller,
+    int64 [B, N] or [B * num_samples, N] with N = max_new_tokens), every other modality is HELD at its last prompt
+    token. ValueError for: a modality named twice, out of range or not an int; an empty list; a modality both
+    generated and given; a given tensor of another dtype or shape, or with a token outside 0..V_i - 1; a wrong
+    number of prompts; prompts that are not [B, n0 >= 1] of one shape (the reference's pad / crop rule is defined
+    around one generated modality)."""
+    M = len(vocab_sizes)
+    g = modality_to_generate
+    if isinstance(g, int) and not isinstance(g, bool):
+        if given is not None:
+            raise ValueError("generate: given= needs the list form of modality_to_generate (a sequence or \"all\")")
+        return None
+    if isinstance(g, str):
+        if g != "all":
+            raise ValueError(f"generate: modality_to_generate must be an int, a sequence of ints or \"all\", got {g!r}")
+        gen = list(range(M))
+    else:
+        try:
+            gen = list(g)
+        except TypeError:
+            raise ValueError(f"generate: modality_to_generate must be an int, a sequence of ints or \"all\", "
+                             f"got {g!r}") from None
+    for i in gen:
+        if isinstance(i, bool) or not isinstance(i, int) or not 0 <= i < M:
+            raise ValueError(f"generate: modality_to_generate names {i!r}; modalities are the ints 0..{M - 1}")
+    if len(set(gen)) != len(gen):
+        raise ValueError(f"generate: modality_to_generate names a modality twice: {gen}")
+    if not gen:
+        raise ValueError("generate: modality_to_generate is empty")
+    N = int(max_new_tokens)
+    if N < 0:
+        raise ValueError(f"generate: max_new_tokens must be >= 0, got {max_new_tokens!r}")
+    shapes = [tuple(int(x) for x in s) for s in prompt_shapes]
+    if len(shapes) != M:
+        raise ValueError(f"expected {M} index tensors, got {len(shapes)}")
+    if any(len(s) != 2 for s in shapes) or len(set(shapes)) != 1:
+        raise ValueError(f"generate: a joint rollout needs [B, n0] prompts of one shape, got {shapes}")
+    B, n0 = shapes[0]
+    if n0 < 1:
+        raise ValueError("generate: the prompt must hold at least one token")
+    given = {} if given is None else given
+    if not isinstance(given, dict):
+        raise ValueError("generate: given must be a dict {modality: int64 [B, N] tokens}")
+    rows = (B,) if num_samples is None else (B, B * num_samples)
+    for i, t in given.items():
+        if isinstance(i, bool) or not isinstance(i, int) or not 0 <= i < M:
+            raise ValueError(f"generate: given names {i!r}; modalities are the ints 0..{M - 1}")
+        if i in gen:
+            raise ValueError(f"generate: modality {i} is both generated and given")
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.long:
+            raise ValueError(f"generate: given[{i}] must be an int64 tensor")
+        if t.dim() != 2 or t.shape[1] != N or t.shape[0] not in rows:
+            raise ValueError(f"generate: given[{i}] must be [{' or '.join(str(r) for r in rows)}, {N}], "
+                             f"got {tuple(t.shape)}")
+        if t.numel() and (int(t.min()) < 0 or int(t.max()) >= vocab_sizes[i]):
+            raise ValueError(f"generate: given[{i}] holds tokens outside 0..{vocab_sizes[i] - 1}")
+    roles = [GENERATED if i in gen else GIVEN if i in given else HELD for i in range(M)]
+    return JointPlan(roles, sorted(gen), dict(given), B, n0, N)
+
+
+def joint_setting(value, generated, name):
+    """A sampling setting of the list form per generated modality: a scalar (or None) for all, or a dict
+    {modality: value} whose keys are generated modalities (the others take the default)."""
+    if not isinstance(value, dict):
+        return {i: value for i in generated}
+    for i in value:
+        if i not in generated:
+            raise ValueError(f"generate: {name} names modality {i!r}, which is not generated")
+    return {i: value.get(i) for i in generated}
+
+
 class _MmtStep(torch.autograd.Function):
     """One forward through the C-ABI; its backward is mmt_backward into a fresh flat grad (or, with
     set_grad_accumulation on, in place into flat_params.grad: then no gradient is returned for `flat`)."""
@@ -506,7 +593,7 @@ class MultimodalTransformer(nn.Module):
     @torch.no_grad()
     def generate(self, idx_list, max_new_tokens=1, modality_to_generate=0, use_cache=True, sample_fn=None, *,
                  temperature=None, top_k=None, top_p=None, seed=None, return_logprobs=False, logits_hook=None,
-                 num_samples=None):
+                 num_samples=None, given=None):
         """model.py:404-446: per new token, the logits of the last position of the (block_size
         cropped) context, a sample from the softmax of the target modality's last logits
         (torch.multinomial, as the reference; `sample_fn(probs) -> [B, 1]` overrides it), appended;
@@ -534,9 +621,28 @@ class MultimodalTransformer(nn.Module):
         and decode steps over B*S rows that share each prompt's keys / values (`_generate_fanout`,
         mmt_decode_fanout_step). That engine runs with use_cache, in eval mode or without dropout, at bf16, for
         prompts of one length n0 >= 1 with n0 + max_new_tokens <= block_size; otherwise the prompts are tiled and
-        the device path runs as without the keyword. `last_generate_path` says which ran: "fanout" or "tiled"."""
+        the device path runs as without the keyword. `last_generate_path` says which ran: "fanout" or "tiled".
+
+        Joint rollouts: modality_to_generate as a sequence of distinct ints (even of one) or "all" samples each of
+        those modalities per step from its own head and feeds them back together (`_generate_joint`, always the
+        device path: one decode step and one mmt_sample_multi per token). The draw of modality i, row r, position n
+        is mmt_sample's with the seed mmt_sample.modality_seed(seed, i), whatever else is generated. given={i:
+        int64 [B, N] or [B * S, N]} makes modality i follow the caller's tokens (a scenario, or a series known in
+        advance; [B, N] is shared by a prompt's samples); every other modality is held at its last prompt token. In
+        this form temperature / top_k / top_p are scalars or {modality: value} dicts, logits_hook(n, logits_list)
+        sees the [rows, V_i] views of all modalities, return_logprobs gives (sequences, {i: fp32 [rows, N]}),
+        sample_fn and prompts of unequal lengths are refused (plan_joint lists every refusal), and num_samples runs
+        the fan-out engine under the conditions above. An int runs exactly as it always did."""
         if num_samples is not None:
             num_samples = check_num_samples(num_samples)
+        plan = plan_joint(modality_to_generate, given, self.vocab_sizes, [tuple(s.shape) for s in idx_list],
+                          max_new_tokens, num_samples)
+        if plan is not None:
+            if sample_fn is not None:
+                raise ValueError("generate: sample_fn cannot be combined with a joint rollout (a list of modalities "
+                                 "or \"all\"): it samples on the GPU")
+            return self._generate_joint(idx_list, plan, use_cache, temperature, top_k, top_p, seed, return_logprobs,
+                                        logits_hook, num_samples)
         if not (temperature is None and top_k is None and top_p is None and seed is None and not return_logprobs
                 and logits_hook is None and num_samples is None):
             if sample_fn is not None:
@@ -749,6 +855,122 @@ class MultimodalTransformer(nn.Module):
                           compact.data_ptr(), lp_base + 4 * j if lp_base else 0, N)
         seqs = [buf.to(idx_list[i].dtype) for i, buf in enumerate(bufs)]
         return (seqs, lp) if return_logprobs else seqs
+
+    @torch.no_grad()
+    def _generate_joint(self, idx_list, plan, use_cache, temperature, top_k, top_p, seed, return_logprobs,
+                        logits_hook, S):
+        """The list form of generate (a joint rollout): every GENERATED modality is sampled per step from its own
+        head, all of them in one mmt_sample_multi launch, modality i with the seed modality_seed(seed, i); GIVEN
+        modalities follow the caller's tokens; HELD ones stay at their last prompt token. Sequence buffers as in
+        `_generate_device`, given columns and held pads written once before the loop, one compact [rows] buffer per
+        generated modality. The decode step's idx[i] points at that compact buffer, at the held token, or at row j
+        of a [N, rows] transposed copy of the given tokens: the engine reads the pointer array on the host per
+        call, so the host moves a pointer and no kernel copies a token. Per token the host issues one decode step
+        (with num_samples under the fan-out conditions of `_generate_samples`: one fan-out step over B*S rows) and
+        one mmt_sample_multi: no torch op, no sync. Past block_size, with use_cache=False, in training mode with
+        dropout and at fp8 a step is the re-forward over the cropped buffers, and each problem reads its
+        modality's last-position logits in place."""
+        import mmt_sample as MS
+        flat = self.flat_params
+        dev = flat.device
+        M, T, N, n0, gen = self.num_modalities, self.block_size, plan.N, plan.n0, plan.generated
+        ts, ks, ps = (joint_setting(temperature, gen, "temperature"), joint_setting(top_k, gen, "top_k"),
+                      joint_setting(top_p, gen, "top_p"))
+        settings = [MS.check_settings(ts[i], ks[i], ps[i]) for i in gen]
+        if dev.type != "cuda":
+            raise RuntimeError("MultimodalTransformer (libmmt_hip) runs only on a ROCm GPU: call .to('cuda') "
+                               "(there is no CPU path)")
+        seed = MS.device_seed(dev) if seed is None else int(seed) & MS.MASK64
+        L = ML.lib()
+        cache = use_cache and not (self.training and self.dropout_p > 0.0) and self.precision == "bf16"
+        fan = S is not None and cache and n0 + N <= T and N >= 1
+        nbytes = L.mmt_fanout_bytes(self._ctx, plan.B, S, N) if fan else 0
+        if nbytes < 0:
+            raise ValueError(f"generate: {plan.B} prompts x {S} samples are more rows than the decode launches address")
+        if S is not None:
+            self.last_generate_path = "fanout" if fan else "tiled"
+        prompts = [s.to(device=dev, dtype=torch.long).contiguous() for s in idx_list]
+        rows = prompts if S is None else tile_prompts(prompts, S)
+        R, cap = rows[0].shape[0], n0 + N
+        bufs, steps = [], {}
+        for i, s in enumerate(rows):
+            buf = torch.zeros(R, cap, dtype=torch.long, device=dev)
+            buf[:, :n0] = s
+            if plan.roles[i] == GIVEN and N > 0:
+                g = plan.given[i].to(dev)
+                buf[:, n0:] = g if g.shape[0] == R else g.repeat_interleave(S, 0)
+                steps[i] = buf[:, n0:].t().contiguous()  # [N, R]: row j is what a decode step of new position j reads
+            elif plan.roles[i] == HELD and N > 0:
+                buf[:, n0:] = s[:, -1:]
+            bufs.append(buf)
+        compact = {i: torch.zeros(R, dtype=torch.long, device=dev) for i in gen}
+        held = {i: rows[i][:, -1].contiguous() for i in range(M) if plan.roles[i] == HELD}
+        lps = {i: torch.empty(R, N, dtype=torch.float32, device=dev) for i in gen} if return_logprobs else None
+        ml = MS.MultiLaunch([self.vocab_sizes[i] for i in gen], settings, [MS.modality_seed(seed, i) for i in gen],
+                            [cap] * len(gen), [N] * len(gen))
+        for p, i in enumerate(gen):
+            ml.compact[p] = compact[i].data_ptr()
+        dec_logits = p_idx = p_logits = None
+        p_flat = ML.ptr(flat)
+
+        def decode_args(j):
+            """The pointer arrays of the decode step that reads the tokens of new position j (made at first use)."""
+            nonlocal dec_logits, p_idx, p_logits
+            if p_idx is None:
+                dec_logits = [torch.empty(R, Vi, dtype=torch.float32, device=dev) for Vi in self.vocab_sizes]
+                p_idx = ML.ptr_array([compact[i] if i in compact else held.get(i) for i in range(M)])
+                p_logits = ML.ptr_array(dec_logits)
+            for i, st in steps.items():
+                p_idx[i] = st.data_ptr() + 8 * R * j
+
+        def sample(n, j, views):
+            if logits_hook is not None:
+                logits_hook(n, views)
+            for p, i in enumerate(gen):
+                ml.logits[p] = views[i].data_ptr()
+                ml.row_stride[p] = int(views[i].stride(0)) if R > 1 else self.vocab_sizes[i]
+                ml.tok[p] = bufs[i].data_ptr() + 8 * n
+                ml.logprob[p] = lps[i].data_ptr() + 4 * j if lps is not None else None
+            ml.run(L, stream, R, 0, n)
+
+        with torch.cuda.device(dev):
+            stream = ML.stream_ptr(dev)
+            if fan:
+                logits, _ = self(prompts)  # the prefill: leaves every prompt position's keys / values in the workspace
+                sel = torch.arange(plan.B, device=dev).repeat_interleave(S)
+                first = [lg[:, -1, :].index_select(0, sel) for lg in logits]  # each sample's copy of its prompt's row
+                fanbuf = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+                p_ws, p_fan = ML.ptr(self._ws), ML.ptr(fanbuf)
+                for j in range(N):
+                    n = n0 + j
+                    if j == 0:
+                        views = first
+                    else:
+                        decode_args(j - 1)
+                        rc = L.mmt_decode_fanout_step(self._ctx, stream, plan.B, S, n0, N, n - 1, p_idx, p_flat,
+                                                      p_logits, p_ws, p_fan)
+                        ML.check(rc, self._ctx, "mmt_decode_fanout_step")
+                        views = dec_logits
+                    sample(n, j, views)
+            else:
+                cached_pos = None  # the last position whose keys / values the workspace holds
+                for j in range(N):
+                    n = n0 + j
+                    if cache and cached_pos is not None and n - 1 == cached_pos + 1 and n <= T:
+                        decode_args(j - 1)
+                        rc = L.mmt_decode_step(self._ctx, stream, R, n - 1, p_idx, p_flat, p_logits,
+                                               ML.ptr(self._ws))
+                        ML.check(rc, self._ctx, "mmt_decode_step")
+                        self._gen += 1
+                        cached_pos = n - 1
+                        views = dec_logits
+                    else:
+                        logits, _ = self([buf[:, max(0, n - T):n] for buf in bufs])
+                        views = [lg[:, -1, :] for lg in logits]
+                        cached_pos = n - 1 if (cache and n <= T) else None
+                    sample(n, j, views)
+        seqs = [buf.to(idx_list[i].dtype) for i, buf in enumerate(bufs)]
+        return (seqs, lps) if return_logprobs else seqs
 
     @torch.no_grad()
     def _decode_step(self, tokens, pos):
