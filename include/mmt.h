@@ -189,6 +189,75 @@ int mmt_sample_multi(void* stream, int32_t count, int32_t batch, const int32_t* 
                      const int64_t* tok_stride, int64_t* const* tok_compact /* nullable, entries nullable */,
                      float* const* logprob /* nullable, entries nullable */, const int64_t* lp_stride);
 
+/* Evidence of conditioned rollouts. generate(..., given={i: tokens}) forces modality i through the caller's series;
+ * the heads are conditionally independent given the history, so the probability of the forced token under its own
+ * head is the path's importance weight. The three entries below score the forced tokens, turn weighted paths into
+ * posterior paths (a particle filter over the S paths of a prompt) and move the fan-out tails to their ancestors.
+ *
+ * mmt_score_multi: `count` problems over the same `batch` rows, grid (rows, problems), the shape and the host
+ * arrays of mmt_sample_multi. Problem p reads row b of its fp32 logits at logits[p] + b * row_stride[p] (a
+ * [B, T, V] tensor is read in place) and the token tok[p][b * tok_stride[p]] (int64), and writes the fp32
+ * log-probability at logprob[p] + b * lp_stride[p].
+ * The rule: the score of token t is the log-probability mmt_sample reports when it draws t at temperature 1,
+ * top_k 0, top_p 1: steps 1, 3 and 7 above (z = logit, NaN as -inf; e_i = exp(z_i - m) in fp32, 1 at the maximum;
+ * S their fp64 sum over the sampler's tree; (z_t - m) - log S rounded to fp32 once), by the sampler's own device
+ * code, so the score is bit for bit what the sampler writes for the same row and token. A token whose logit is
+ * -inf or NaN scores -inf; a row with no finite logit scores NaN; a token outside 0..V-1 (which the Python layer
+ * refuses before any launch) is not read and scores NaN.
+ * MMT_ERR_INVALID before any launch, nothing written: count < 0, batch < 0, with count > 0 a null array, and per
+ * problem V < 1, row_stride < V or, with batch > 0, a null logits / tok / logprob; MMT_ERR_UNSUPPORTED for
+ * V > 2^20. All problems are checked before any launch. Launches as mmt_sample_multi: chunks of 8 problems, rows
+ * with V > 8192 in the re-read variant. mmt_sample and mmt_sample_multi keep their launch shapes and bits. */
+int mmt_score_multi(void* stream, int32_t count, int32_t batch, const int32_t* V, const float* const* logits,
+                    const int64_t* row_stride, const int64_t* const* tok, const int64_t* tok_stride,
+                    float* const* logprob, const int64_t* lp_stride);
+
+/* mmt_resample: one workgroup per prompt, no context. Row r = b * samples + s is path s of prompt b. Inputs:
+ * `count` <= 8 log-probability matrices (the given modalities', fp32, logprob[i] + r * lp_stride[i] + j; HOST
+ * arrays of pointers and strides), the column range [j0, j1), logw fp64 [batch * samples] (the log-weight carried
+ * since the last resampling; the caller zeroes it at the start), log_evidence fp64 [batch] (accumulated; zeroed by
+ * the caller), ess_threshold, seed, pos. Outputs: ancestors int32 [batch * samples] as GLOBAL row indices,
+ * resampled int32 [batch]. The rule, per prompt b, with S = samples:
+ *   1. a_s = logw[r] + sum over j = j0..j1-1, then over the given matrices in the caller's order (ascending
+ *      modality), of (double) lp_i[r, j]: a serial fp64 sum in that order; a NaN term (and a NaN logw or sum)
+ *      counts as -inf. mx = max a_s. If mx == -inf (no live path): logw[r] = a_s, ancestors are the identity,
+ *      resampled[b] = 0, nothing else is written.
+ *   2. d_s = (float)(a_s - mx); e_s = 1 where d_s == 0, else expf(d_s), fp32. W = sum e_s and Q = sum e_s^2 in fp64
+ *      over a fixed assignment and tree, the sampler's: thread t of 256 owns the c = ceil(S / 256) | 1 consecutive
+ *      elements from t c, serial sum, shift scan over the lanes, wave totals added left to right.
+ *      ESS = W^2 / Q.
+ *   3. if not ESS < ess_threshold * S (fp64): logw[r] = a_s, ancestors are the identity, resampled[b] = 0.
+ *   4. else systematic resampling: key = mmt_hash(lo32(seed), hi32(seed), 0x52534D50); h = mmt_hash(key, b, pos);
+ *      u = ((h >> 8) + 0.5) * 2^-24. Slot s takes the first row, in row order, with e > 0 whose inclusive prefix
+ *      sum of e (the tree's) reaches ((s + u) / S) * W; if rounding leaves none, the last row with e > 0.
+ *      ancestors[r] = b * S + that row, logw[r] = 0, log_evidence[b] += mx + log(W / S), resampled[b] = 1.
+ * Hence equal weights give the identity, and a dead path (e = 0) is never an ancestor. ess_threshold 0 never
+ * resamples: the call only folds the columns into logw. A NEGATIVE ess_threshold is the closing fold of a run: no
+ * resampling (steps 1 and 3), and log_evidence[b] += mx + log(W / S) (-inf when no path is live), so log_evidence
+ * ends as the estimate of log p(given series | history) and logw as the weights of the returned paths.
+ * No float atomics, nothing depends on the other prompts of the launch: bit-identical run to run, and a prompt alone
+ * gives the bits it gives in company. The S weights of a prompt stay in LDS: samples <= 4096 (the largest fan the
+ * README measures); above that MMT_ERR_UNSUPPORTED, nothing is re-read from memory.
+ * MMT_ERR_INVALID before any launch: batch < 0, samples < 1, count outside 0..8, j0 < 0, j1 < j0, a NaN threshold,
+ * lp_stride[i] < j1, batch * samples >= 2^31, a null pointer with batch > 0. batch == 0 launches nothing. */
+int mmt_resample(void* stream, int32_t batch, int32_t samples, int32_t count, const float* const* logprob,
+                 const int64_t* lp_stride, int32_t j0, int32_t j1, double* logw, double* log_evidence,
+                 double ess_threshold, uint64_t seed, uint32_t pos, int32_t* ancestors, int32_t* resampled);
+
+/* mmt_fanout_gather: the tails of a fan-out run follow their ancestors. For every tail of the run's fan buffer plan
+ * (per (layer, modality) the self-attention tail, per (layer, cross modality, KV stream) the cross tail) the first
+ * npos positions of row r of dst_fan become those of row ancestors[r] of src_fan: one gather kernel with 16-byte
+ * accesses over a segment table the engine takes from its own plan, up to 64 segments per launch. Whole positions
+ * are copied (the K, Q and V thirds of a self-attention row are contiguous); what no later step reads, the Q third
+ * and positions >= npos, is unspecified in dst. The compact per-step scratch at the front of the buffer is not
+ * copied, and the run state (next position, n0, samples) is left as it is: the next mmt_decode_fanout_step is
+ * simply handed dst_fan. An ancestor outside 0..batch*samples-1 is read as the row itself.
+ * Refusals, each before any launch: a null pointer, src_fan == dst_fan, buffers not 16-byte aligned
+ * (MMT_ERR_INVALID); batch / samples / n0 / max_new that are not the run in progress, or no run (MMT_ERR_STATE);
+ * npos != next position - n0 (MMT_ERR_INVALID). */
+int mmt_fanout_gather(mmt_ctx* ctx, void* stream, int32_t batch, int32_t samples, int32_t n0, int32_t max_new,
+                      int32_t npos, const int32_t* ancestors, const void* src_fan, void* dst_fan);
+
 /* failure detection (the reference's guard is the NaN check on eval losses,
  * main.py:606): byte offset in the workspace of two int32 bitmasks (the same for every batch size;
  * the query never touches the workspace plan of a pending backward or decode). The

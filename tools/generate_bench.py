@@ -23,6 +23,11 @@ the same call over the prompts repeated S times by the caller (what a checkout w
 --tree, --paths tiled). Per round it records paths per second (B * S / wall time), tokens per second and the peak
 of torch.cuda.max_memory_allocated over the call; a path that runs out of memory is reported as such. --attn adds
 the fan-out attention kernel alone against attn_decode_kernel at B * S rows (this tree only).
+
+Evidence of a given series (modalities 0..2 sampled, modality 3 given): --paths joint_given,joint_weights without
+--samples; with --samples, --paths fanout_given,fanout_weights,fanout_resample1,fanout_resample8,fanout_resample32
+(evidence="resample" with ess_threshold 0.5 at resample_every 1 / 8 / 32). --gather adds mmt_fanout_gather alone
+after half the new tokens: its bytes (read plus written) and us per call.
 """
 import argparse
 import json
@@ -50,6 +55,7 @@ def main():
                     help="also time mmt_sample_multi over the four heads against four mmt_sample launches")
     ap.add_argument("--samples", type=int, default=0, help="continuations per prompt (0: the single-path benchmark)")
     ap.add_argument("--attn", action="store_true", help="with --samples: the two decode attention kernels alone")
+    ap.add_argument("--gather", action="store_true", help="with --samples: mmt_fanout_gather alone (this tree only)")
     a = ap.parse_args()
     if a.samples and a.paths == "default,device":
         a.paths = "fanout,tiled"
@@ -82,6 +88,11 @@ def main():
         "joint_topk_topp": lambda: model.generate(prompt, max_new_tokens=a.new, modality_to_generate="all",
                                                   temperature=0.8, top_k=50, top_p=0.9, seed=11),
     }
+    # evidence of a given series: modalities 0..2 sampled, modality 3 follows the caller's tokens
+    scen = {3: torch.randint(0, C1["V"][3], (a.batch, a.new), generator=g)}
+    gkw = dict(max_new_tokens=a.new, modality_to_generate=[0, 1, 2], given=scen, temperature=1.0, seed=11)
+    calls["joint_given"] = lambda: model.generate(prompt, **gkw)
+    calls["joint_weights"] = lambda: model.generate(prompt, evidence="weights", **gkw)[0]
     paths = [p for p in a.paths.split(",") if p]
     if a.samples:
         return fanout_bench(a, torch, dev, model, prompt, paths)
@@ -117,6 +128,14 @@ def fanout_bench(a, torch, dev, model, prompt, paths):
     calls = {"fanout": lambda: model.generate(prompt, num_samples=S, **kw),
              "tiled": lambda: model.generate(tiled, **kw),
              "fanout_joint": lambda: model.generate(prompt, num_samples=S, **dict(kw, modality_to_generate="all"))}
+    g = torch.Generator().manual_seed(8)
+    scen = {3: torch.randint(0, C1["V"][3], (B, a.new), generator=g)}
+    gkw = dict(kw, modality_to_generate=[0, 1, 2], given=scen, num_samples=S)
+    calls["fanout_given"] = lambda: model.generate(prompt, **gkw)
+    calls["fanout_weights"] = lambda: model.generate(prompt, evidence="weights", **gkw)[0]
+    for every in (1, 8, 32):
+        calls[f"fanout_resample{every}"] = lambda every=every: model.generate(
+            prompt, evidence="resample", resample_every=every, ess_threshold=0.5, **gkw)[0]
     rec = {p: {"paths_per_s": [], "tokens_per_s": [], "peak_bytes": []} for p in paths}
 
     def one(p, timed):
@@ -146,7 +165,44 @@ def fanout_bench(a, torch, dev, model, prompt, paths):
         res["fanout_path"] = getattr(model, "last_generate_path", None) if "fanout" in live else None
     if a.attn:
         res["attn_us"] = attention_alone(torch, dev, B, S, a.prompt, a.prompt + a.new, a.rounds)
+    if a.gather:
+        res["gather"] = gather_alone(torch, dev, model, prompt, B, S, a.prompt, a.new, a.rounds)
     print(json.dumps(res), flush=True)
+
+
+def gather_alone(torch, dev, model, prompt, B, S, n0, N, rounds, reps=20):
+    """mmt_fanout_gather on its own after N // 2 fan-out steps (identity ancestors, a second fan buffer): the bytes it
+    moves (read plus written: whole K | Q | V and cross K | V rows of the positions written so far) and us per call
+    (HIP events around `reps` back-to-back calls, best of `rounds`)."""
+    import mmt_lib as ML
+    L, st = ML.lib(), ML.stream_ptr(dev)
+    R, npos = B * S, max(1, N // 2)
+    with torch.no_grad():
+        model(prompt)
+        for k in range(npos):
+            model._decode_fanout_step([torch.zeros(R, dtype=torch.long, device=dev) for _ in C1["V"]], n0 + k, S, n0, N)
+    src = model._fan
+    dst = torch.empty_like(src)
+    anc = torch.arange(R, dtype=torch.int32, device=dev)
+    C, M, ncross = C1["n_embd"], len(C1["V"]), sum(C1["cross"])
+    moved = 2 * R * npos * 2 * C1["n_layer"] * (M * 3 * C + ncross * (M - 1) * 2 * C)
+
+    def one():
+        return L.mmt_fanout_gather(model._ctx, st, B, S, n0, N, npos, ML.ptr(anc), ML.ptr(src), ML.ptr(dst))
+
+    best = None
+    for _ in range(rounds):
+        assert one() == 0
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        for _k in range(reps):
+            one()
+        e1.record()
+        torch.cuda.synchronize()
+        us = e0.elapsed_time(e1) / reps * 1e3
+        best = us if best is None else min(best, us)
+    return {"npos": npos, "bytes": moved, "us": round(best, 2), "GB_per_s": round(moved / best / 1e3, 1)}
 
 
 def attention_alone(torch, dev, B, S, n0, T, rounds, reps=50):

@@ -2324,6 +2324,52 @@ int mmt_decode_fanout_step(mmt_ctx* c, void* stream, int32_t batch, int32_t samp
   return rc;
 }
 
+int mmt_fanout_gather(mmt_ctx* c, void* stream, int32_t batch, int32_t samples, int32_t n0, int32_t max_new,
+                      int32_t npos, const int32_t* ancestors, const void* src_fan, void* dst_fan) {
+  if (!c) return MMT_ERR_INVALID;
+  const char* me = "mmt_fanout_gather";
+  if (!ancestors || !src_fan || !dst_fan) return fail(c, MMT_ERR_INVALID, std::string(me) + ": null argument");
+  if (src_fan == dst_fan) return fail(c, MMT_ERR_INVALID, std::string(me) + ": src_fan and dst_fan are one buffer");
+  if (c->fan_next < 0 || c->fan.B != batch || c->fan.S != samples || c->fan.max_new != max_new || c->fan_n0 != n0 ||
+      c->fan_S != samples)
+    return fail(c, MMT_ERR_STATE, std::string(me) + ": batch, samples, n0 and max_new must be those of the fan-out run "
+                                  "in progress");
+  if (npos != c->fan_next - n0)
+    return fail(c, MMT_ERR_INVALID, std::string(me) + ": npos must be the number of positions the run has written");
+  if ((((uintptr_t)src_fan | (uintptr_t)dst_fan) & 15) != 0)
+    return fail(c, MMT_ERR_INVALID, std::string(me) + ": fan buffers must be 16-byte aligned");
+  // the segment table is the plan's: every self-attention and cross tail, rows max_new * ld elements apart, the
+  // first npos positions of each (contiguous in a row); the compact per-step scratch in front is not copied
+  const FanPlan& f = c->fan;
+  const int M = c->M, C = c->C;
+  const int rows = batch * samples;
+  const char* src = static_cast<const char*>(src_fan);
+  char* dst = static_cast<char*>(dst_fan);
+  hipStream_t s = (hipStream_t)stream;
+  GatherBatch gb{};
+  auto flush = [&]() -> bool {
+    if (gb.count == 0) return true;
+    const hipError_t e = mmt_launch_row_gather(gb, ancestors, rows, s);
+    gb.count = 0;
+    return e == hipSuccess;
+  };
+  auto add = [&](size_t off, int ld) -> bool {
+    GatherSeg& q = gb.seg[gb.count++];
+    q.src = src + off; q.dst = dst + off;
+    q.row_bytes = (int64_t)max_new * ld * 2; q.bytes = (int64_t)npos * ld * 2;
+    return gb.count < MMT_GATHER_SEGS || flush();
+  };
+  bool ok = true;
+  for (int l = 0; l < c->L && ok; ++l)
+    for (int i = 0; i < M && ok; ++i) {
+      ok = add(f.sa_tail[(size_t)l * M + i], 3 * C);
+      if (c->lm[(size_t)l * M + i].cross)
+        for (int j = 0; j < M - 1 && ok; ++j) ok = add(f.ca_tail[((size_t)l * M + i) * MAXM + j], 2 * C);
+    }
+  ok = ok && flush();
+  return ok ? MMT_OK : fail(c, MMT_ERR_HIP, std::string(me) + ": launch failed");
+}
+
 int32_t mmt_backward_stage_count(const mmt_ctx* c) { return c ? c->L + 2 : 0; }
 
 int mmt_backward_stage_range(const mmt_ctx* c, int32_t stage, int64_t* begin, int64_t* end) {

@@ -333,6 +333,14 @@ struct FanoutAttnBatch { FanoutAttnProblem p[MMT_MAX_GROUP]; int count; };
 hipError_t mmt_launch_attn_decode_fanout(const FanoutAttnBatch& b, int B, int S, int n0, int t, int T, int H, int hs,
                                          int tail_rows, float scale, hipStream_t s);
 
+// Row gather of the fan-out tails (mmt_fanout_gather, mmt_evidence.hip): for every segment, the first `bytes`
+// bytes of dst row r become those of src row anc[r]; rows are row_bytes apart. Bases, row_bytes and bytes are
+// multiples of 16 (16-byte accesses). An ancestor outside 0..rows-1 is read as r itself.
+#define MMT_GATHER_SEGS 64
+struct GatherSeg { const char* src; char* dst; int64_t row_bytes, bytes; };
+struct GatherBatch { GatherSeg seg[MMT_GATHER_SEGS]; int count; };
+hipError_t mmt_launch_row_gather(const GatherBatch& b, const int32_t* anc, int rows, hipStream_t s);
+
 // ------------------------------------------------------------------------------------------
 // Per-head Q/K/V stage 2: block-diagonal [hs/2 -> hs] maps (model.py:39,44,49), nblk = 3*H.
 //   out[r, blk*hs + o] = sum_i W2[blk][o][i] * h1[r, blk*hs/2 + i]

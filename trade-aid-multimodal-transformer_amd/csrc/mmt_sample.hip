@@ -85,6 +85,72 @@ __device__ __forceinline__ unsigned long long block_count3(unsigned long long v,
 // weight of an element relative to the row maximum m: 1 at the maximum (also when m is +inf), exp(z - m) below
 __device__ __forceinline__ float weight(float z, float m) { return z == m ? 1.0f : expf(z - m); }
 
+// Steps 1, 3 and 7 of the rule, shared by the sampler and by the scoring kernel (mmt_score_multi), so a score is
+// bit for bit the log-probability the sampler writes for the same row and token.
+// step 1: z = logit * inv_t (one fp32 multiply), NaN as -inf
+__device__ __forceinline__ float scaled_logit(const float* __restrict__ row, int i, float inv_t) {
+  const float z = row[i] * inv_t;
+  return z != z ? -INFINITY : z;
+}
+// step 1 over the row: the scaled logits into LDS (ONCHIP) and their maximum; the barrier of the reduction also
+// publishes zs
+template <bool ONCHIP>
+__device__ __forceinline__ float row_max(float* __restrict__ zs, const float* __restrict__ row, int V, float inv_t,
+                                         SampleShared& sh, int& par) {
+  float m = -INFINITY;
+  for (int i = threadIdx.x; i < V; i += SAMPLE_THREADS) {
+    const float z = scaled_logit(row, i, inv_t);
+    if (ONCHIP) zs[i] = z;
+    m = fmaxf(m, z);
+  }
+  return block_max(m, sh, par);
+}
+// steps 3, 5: the weights of { key >= K } summed in vocabulary order. Thread t owns the contiguous chunk
+// [t c, t c + c), c odd so the LDS reads of a wave spread over the banks; serial sum per thread, shift scan over
+// the lanes, wave totals added left to right. Every thread ends with S, its own total and its exclusive prefix.
+struct RowSums {
+  int i0, i1;
+  double tot, base, S;
+  bool has_max;
+};
+template <class ZAT>
+__device__ __forceinline__ RowSums row_sums(ZAT zat, int V, float m, uint32_t K, SampleShared& sh, int& par) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  RowSums r;
+  const int c = ((V + SAMPLE_THREADS - 1) / SAMPLE_THREADS) | 1;
+  const int64_t i0l = (int64_t)tid * c;
+  r.i0 = i0l < V ? (int)i0l : V;
+  r.i1 = i0l + c < V ? (int)(i0l + c) : V;
+  r.tot = 0.0;
+  r.has_max = false;
+  for (int i = r.i0; i < r.i1; ++i) {
+    const float z = zat(i);
+    r.tot += okey(z) >= K ? (double)weight(z, m) : 0.0;
+    r.has_max = r.has_max || z == m;
+  }
+  double inc = r.tot;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const double n = __shfl_up(inc, o, 64);
+    if (lane >= o) inc += n;
+  }
+  double ex = __shfl_up(inc, 1, 64);
+  if (lane == 0) ex = 0.0;
+  if (lane == 63) sh.d[par][0][wave] = inc;
+  __syncthreads();
+  const double w0 = sh.d[par][0][0], w1 = sh.d[par][0][1], w2 = sh.d[par][0][2], w3 = sh.d[par][0][3];
+  par ^= 1;
+  r.S = ((w0 + w1) + w2) + w3;
+  const double wbase = wave == 0 ? 0.0 : wave == 1 ? w0 : wave == 2 ? (w0 + w1) : ((w0 + w1) + w2);
+  r.base = wbase + ex;
+  return r;
+}
+// step 7: log(e_tok / S) = (z_tok - m) - log S, rounded to fp32 once
+__device__ __forceinline__ float token_logprob(float zt, float m, double S) {
+  const float d = zt == m ? 0.f : zt - m;
+  return (float)((double)d - log(S));
+}
+
 // One row: row b = blockIdx.x of one problem, the whole rule of mmt.h. Both kernels below are this body and
 // nothing else, so a problem of mmt_sample_multi gives the bits mmt_sample gives with the same arguments.
 template <bool ONCHIP>
@@ -98,20 +164,8 @@ __device__ __forceinline__ void sample_row(
   const float* row = logits + (int64_t)b * row_stride;
   int par = 0;
 
-  // step 1: z = logit * inv_t (one fp32 multiply), NaN as -inf
-  auto scaled = [&](int i) -> float {
-    const float z = row[i] * inv_t;
-    return z != z ? -INFINITY : z;
-  };
-  auto zat = [&](int i) -> float { return ONCHIP ? zs[i] : scaled(i); };
-
-  float m = -INFINITY;
-  for (int i = tid; i < V; i += SAMPLE_THREADS) {
-    const float z = scaled(i);
-    if (ONCHIP) zs[i] = z;
-    m = fmaxf(m, z);
-  }
-  m = block_max(m, sh, par);  // its barrier also publishes zs
+  auto zat = [&](int i) -> float { return ONCHIP ? zs[i] : scaled_logit(row, i, inv_t); };
+  const float m = row_max<ONCHIP>(zs, row, V, inv_t, sh, par);
 
   int64_t* tok_out = tok + (int64_t)b * tok_stride;
   if (m == -INFINITY) {  // no finite logit: token 0, log-probability NaN (uniform branch: every thread holds m)
@@ -175,34 +229,11 @@ __device__ __forceinline__ void sample_row(
     }
   }
 
-  // steps 5, 6: prefix sums in vocabulary order. Thread t owns the contiguous chunk [t c, t c + c), c odd so the
-  // LDS reads of a wave spread over the banks; serial sum per thread, shift scan over the lanes, wave totals added
-  // left to right.
-  const int c = ((V + SAMPLE_THREADS - 1) / SAMPLE_THREADS) | 1;
-  const int64_t i0l = (int64_t)tid * c;
-  const int i0 = i0l < V ? (int)i0l : V, i1 = i0l + c < V ? (int)(i0l + c) : V;
-  double tot = 0.0;
-  bool has_max = false;
-  for (int i = i0; i < i1; ++i) {
-    const float z = zat(i);
-    tot += okey(z) >= K ? (double)weight(z, m) : 0.0;
-    has_max = has_max || z == m;
-  }
-  double inc = tot;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const double n = __shfl_up(inc, o, 64);
-    if (lane >= o) inc += n;
-  }
-  double ex = __shfl_up(inc, 1, 64);
-  if (lane == 0) ex = 0.0;
-  if (lane == 63) sh.d[par][0][wave] = inc;
-  __syncthreads();
-  const double w0 = sh.d[par][0][0], w1 = sh.d[par][0][1], w2 = sh.d[par][0][2], w3 = sh.d[par][0][3];
-  par ^= 1;
-  const double S = ((w0 + w1) + w2) + w3;
-  const double wbase = wave == 0 ? 0.0 : wave == 1 ? w0 : wave == 2 ? (w0 + w1) : ((w0 + w1) + w2);
-  const double base = wbase + ex;
+  // steps 5, 6: prefix sums in vocabulary order (row_sums)
+  const RowSums rs = row_sums(zat, V, m, K, sh, par);
+  const int i0 = rs.i0, i1 = rs.i1;
+  const double tot = rs.tot, base = rs.base, S = rs.S;
+  const bool has_max = rs.has_max;
 
   const uint32_t h = mmt_hash(key, row0 + (uint32_t)b, pos);
   const double u = ((double)(h >> 8) + 0.5) * (1.0 / 16777216.0);
@@ -245,10 +276,7 @@ __device__ __forceinline__ void sample_row(
   *tok_out = t;
   if (tok_compact) tok_compact[b] = t;
   if (logprob) {
-    // step 7: log(e_tok / S) = (z_tok - m) - log S
-    const float zt = zat(t);
-    const float d = zt == m ? 0.f : zt - m;
-    logprob[(int64_t)b * lp_stride] = (float)((double)d - log(S));
+    logprob[(int64_t)b * lp_stride] = token_logprob(zat(t), m, S);
   }
 }
 
@@ -286,6 +314,47 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_multi_kernel(SampleBatc
   const SampleProblem& q = batch.p[blockIdx.y];
   sample_row<ONCHIP>(zs, sh, q.V, q.logits, q.row_stride, q.inv_t, q.greedy, q.top_k, q.top_p, q.key, row0, pos, q.tok,
                      q.tok_stride, q.tok_compact, q.logprob, q.lp_stride);
+}
+
+// mmt_score_multi: the log-probability of a GIVEN token under the row's raw softmax, i.e. what sample_row writes
+// when it draws that token at temperature 1, top_k 0, top_p 1: row_max with inv_t = 1 (an exact multiply), row_sums
+// with K = 0, token_logprob. Workgroup (b, p) is row b of problem p; thread 0 writes.
+struct ScoreProblem {
+  const float* logits;
+  int64_t row_stride;
+  const int64_t* tok;
+  int64_t tok_stride;
+  float* logprob;
+  int64_t lp_stride;
+  int V;
+};
+struct ScoreBatch { ScoreProblem p[MMT_MAX_GROUP]; };
+
+template <bool ONCHIP>
+__global__ __launch_bounds__(SAMPLE_THREADS) void score_multi_kernel(ScoreBatch batch) {
+  __shared__ float zs[ONCHIP ? SAMPLE_ONCHIP : 1];
+  __shared__ SampleShared sh;
+  const ScoreProblem& q = batch.p[blockIdx.y];
+  const int b = blockIdx.x, V = q.V;
+  const float* row = q.logits + (int64_t)b * q.row_stride;
+  int par = 0;
+  auto zat = [&](int i) -> float { return ONCHIP ? zs[i] : scaled_logit(row, i, 1.0f); };
+  const float m = row_max<ONCHIP>(zs, row, V, 1.0f, sh, par);
+  float* out = q.logprob + (int64_t)b * q.lp_stride;
+  const float nan = __uint_as_float(0x7fc00000u);
+  if (m == -INFINITY) {  // no finite logit (uniform branch)
+    if (threadIdx.x == 0) *out = nan;
+    return;
+  }
+  const RowSums rs = row_sums(zat, V, m, 0u, sh, par);
+  if (threadIdx.x != 0) return;
+  const int64_t t = q.tok[(int64_t)b * q.tok_stride];
+  if (t < 0 || t >= V) {  // refused by the Python layer; never read outside the row
+    *out = nan;
+    return;
+  }
+  const float zt = zat((int)t);
+  *out = zt == -INFINITY ? -INFINITY : token_logprob(zt, m, rs.S);
 }
 
 // mmt_sample's refusals for one problem; MMT_OK when it may launch
@@ -368,6 +437,48 @@ int mmt_sample_multi(void* stream, int32_t count, int32_t batch, const int32_t* 
           hipLaunchKernelGGL(sample_multi_kernel<false>, grid, dim3(SAMPLE_THREADS), 0, s, sb, row0, pos);
         else
           hipLaunchKernelGGL(sample_multi_kernel<true>, grid, dim3(SAMPLE_THREADS), 0, s, sb, row0, pos);
+        if (hipGetLastError() != hipSuccess) return MMT_ERR_HIP;
+        n = 0;
+      }
+    }
+  }
+  return MMT_OK;
+}
+
+int mmt_score_multi(void* stream, int32_t count, int32_t batch, const int32_t* V, const float* const* logits,
+                    const int64_t* row_stride, const int64_t* const* tok, const int64_t* tok_stride,
+                    float* const* logprob, const int64_t* lp_stride) {
+  if (count < 0 || batch < 0) return MMT_ERR_INVALID;
+  if (count == 0) return MMT_OK;
+  if (!V || !logits || !row_stride || !tok || !tok_stride || !logprob || !lp_stride) return MMT_ERR_INVALID;
+  for (int p = 0; p < count; ++p) {  // every problem before any launch
+    if (V[p] < 1 || row_stride[p] < V[p]) return MMT_ERR_INVALID;
+    if (batch > 0 && (!logits[p] || !tok[p] || !logprob[p])) return MMT_ERR_INVALID;
+    if (V[p] > SAMPLE_MAX_V) return MMT_ERR_UNSUPPORTED;
+  }
+  if (batch == 0) return MMT_OK;
+  hipStream_t s = (hipStream_t)stream;
+  for (int large = 0; large < 2; ++large) {  // the launch shapes of mmt_sample_multi
+    ScoreBatch sb;
+    int n = 0;
+    for (int p = 0; p <= count; ++p) {
+      if (p < count && (V[p] > SAMPLE_ONCHIP) == (large != 0)) {
+        ScoreProblem& q = sb.p[n++];
+        q.logits = logits[p];
+        q.row_stride = row_stride[p];
+        q.tok = tok[p];
+        q.tok_stride = tok_stride[p];
+        q.logprob = logprob[p];
+        q.lp_stride = lp_stride[p];
+        q.V = V[p];
+      }
+      if (n == MMT_MAX_GROUP || (p == count && n > 0)) {
+        for (int k = n; k < MMT_MAX_GROUP; ++k) sb.p[k] = sb.p[0];  // never read: grid.y == n
+        const dim3 grid((unsigned)batch, (unsigned)n);
+        if (large)
+          hipLaunchKernelGGL(score_multi_kernel<false>, grid, dim3(SAMPLE_THREADS), 0, s, sb);
+        else
+          hipLaunchKernelGGL(score_multi_kernel<true>, grid, dim3(SAMPLE_THREADS), 0, s, sb);
         if (hipGetLastError() != hipSuccess) return MMT_ERR_HIP;
         n = 0;
       }

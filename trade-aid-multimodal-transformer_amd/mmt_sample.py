@@ -11,6 +11,13 @@ Several heads of one step in one launch (mmt_sample_multi), as the joint rollout
 
     toks = mmt_sample.sample_multi([logits_0, logits_2], temperature=[0.8, 1.0], top_k=50,
                                    seeds=[mmt_sample.modality_seed(1234, i) for i in (0, 2)], pos=n)
+
+Evidence of given tokens (generate's evidence=): the score of a token under a head (mmt_score_multi) and one
+particle-filter step over the S paths of each prompt (mmt_resample):
+
+    lps = mmt_sample.score_multi([logits_1], [tokens_1])
+    ancestors, resampled = mmt_sample.resample(lps_list, logw, log_evidence, samples=S, ess_threshold=0.5,
+                                               seed=1234, pos=n)
 """
 import ctypes
 
@@ -164,3 +171,128 @@ def sample_multi(logits_list, *, temperature=1.0, top_k=0, top_p=1.0, seeds, pos
     with torch.cuda.device(dev):
         ml.run(ML.lib(), ML.stream_ptr(dev), B, int(row0), int(pos))
     return (toks, lps) if return_logprobs else toks
+
+
+class ScoreLaunch:
+    """The host arrays of one mmt_score_multi call over P problems (include/mmt.h), made once and updated in place
+    between launches, as MultiLaunch: a decode loop changes `logits[p]` / `row_stride[p]` / `tok[p]` / `logprob[p]`
+    (raw addresses) and calls `run`."""
+
+    def __init__(self, V, tok_stride, lp_stride):
+        P = self.P = len(V)
+        n = max(1, P)
+        self.V = (ctypes.c_int32 * n)(*[int(v) for v in V])
+        self.logits = (ctypes.c_void_p * n)()
+        self.row_stride = (ctypes.c_int64 * n)(*[int(v) for v in V])
+        self.tok = (ctypes.c_void_p * n)()
+        self.tok_stride = (ctypes.c_int64 * n)(*[int(x) for x in tok_stride])
+        self.logprob = (ctypes.c_void_p * n)()
+        self.lp_stride = (ctypes.c_int64 * n)(*[int(x) for x in lp_stride])
+
+    def run(self, L, stream, batch):
+        """One mmt_score_multi. Raises MmtError on a non-zero status."""
+        rc = L.mmt_score_multi(stream, self.P, batch, self.V, self.logits, self.row_stride, self.tok, self.tok_stride,
+                               self.logprob, self.lp_stride)
+        if rc != 0:
+            raise ML.MmtError(f"mmt_score_multi failed (status {rc})")
+
+
+def score_multi(logits_list, tokens_list):
+    """The log-probability of given tokens, P problems over the same rows in one launch (mmt_score_multi):
+    logits_list holds P fp32 [B, V_p] tensors on one GPU (rows may be strided, as for `sample`), tokens_list P int64
+    [B] tensors (any stride). Returns a list of P fp32 [B]: for a token that `sample(logits, temperature=1.0)` drew,
+    bit for bit the log-probability it reported. ValueError for a token outside 0..V_p - 1 (this check reads the
+    tokens on the host; a loop that must not sync validates its tokens once and uses ScoreLaunch)."""
+    P = len(logits_list)
+    if len(tokens_list) != P:
+        raise ValueError(f"score_multi: {len(tokens_list)} token tensors for {P} problems")
+    if P == 0:
+        return []
+    B, dev = logits_list[0].shape[0], logits_list[0].device
+    for lg, tk in zip(logits_list, tokens_list):
+        if lg.dim() != 2 or lg.dtype != torch.float32 or lg.device.type != "cuda" or lg.device != dev:
+            raise ValueError("score_multi: every logits must be an fp32 [B, V] tensor on the same GPU")
+        if lg.shape[0] != B:
+            raise ValueError("score_multi: the problems must share the number of rows")
+        V = lg.shape[1]
+        if V < 1 or (V > 1 and lg.stride(1) != 1) or (B > 1 and lg.stride(0) < V):
+            raise ValueError("score_multi: the elements of a row must be contiguous and rows must not overlap")
+        if tk.dim() != 1 or tk.dtype != torch.int64 or tk.device != dev or tk.shape[0] != B:
+            raise ValueError("score_multi: every tokens must be an int64 [B] tensor on the logits' GPU")
+        if B and (int(tk.min()) < 0 or int(tk.max()) >= V):
+            raise ValueError(f"score_multi: tokens outside 0..{V - 1}")
+    lps = [torch.empty(B, dtype=torch.float32, device=dev) for _ in range(P)]
+    sl = ScoreLaunch([lg.shape[1] for lg in logits_list], [max(int(tk.stride(0)), 1) for tk in tokens_list], [1] * P)
+    for p, (lg, tk) in enumerate(zip(logits_list, tokens_list)):
+        sl.logits[p] = lg.data_ptr()
+        sl.row_stride[p] = max(int(lg.stride(0)), lg.shape[1]) if B > 1 else lg.shape[1]
+        sl.tok[p] = tk.data_ptr()
+        sl.logprob[p] = lps[p].data_ptr()
+    with torch.cuda.device(dev):
+        sl.run(ML.lib(), ML.stream_ptr(dev), B)
+    return lps
+
+
+RESAMPLE_MAX_SAMPLES = 4096  # csrc/mmt_evidence.hip RS_MAX_S: the S weights of a prompt stay in LDS
+
+
+class ResampleLaunch:
+    """The host arrays of mmt_resample over G log-probability matrices (raw addresses and row strides in elements),
+    made once; `run` is one launch over the columns [j0, j1)."""
+
+    def __init__(self, lp_ptrs, lp_strides):
+        G = self.G = len(lp_ptrs)
+        n = max(1, G)
+        self.lp = (ctypes.c_void_p * n)(*[int(x) for x in lp_ptrs])
+        self.stride = (ctypes.c_int64 * n)(*[int(x) for x in lp_strides])
+
+    def run(self, L, stream, batch, samples, j0, j1, logw_ptr, log_evidence_ptr, ess_threshold, seed, pos, anc_ptr,
+            resampled_ptr):
+        rc = L.mmt_resample(stream, batch, samples, self.G, self.lp, self.stride, j0, j1, logw_ptr, log_evidence_ptr,
+                            float(ess_threshold), int(seed) & MASK64, int(pos), anc_ptr, resampled_ptr)
+        if rc != 0:
+            raise ML.MmtError(f"mmt_resample failed (status {rc})")
+
+
+def resample(logprobs, logw, log_evidence, *, samples, ess_threshold, seed, pos, j0=0, j1=None):
+    """One particle-filter step over the S = samples paths of each prompt (mmt_resample, include/mmt.h): logprobs is
+    a list of up to 8 fp32 [B * S, N] tensors (the given modalities' log-probabilities, ascending modality; the
+    elements of a row contiguous), logw fp64 [B * S] and log_evidence fp64 [B] are updated IN PLACE, the columns
+    [j0, j1) (default: all) are folded in. Returns (ancestors int32 [B * S] as global row indices, resampled int32
+    [B]). ess_threshold 0 only accumulates; a negative one is the closing fold (log_evidence gains the estimate of
+    the carried weights, nothing is resampled). No sync."""
+    dev = logw.device
+    if logw.dtype != torch.float64 or logw.dim() != 1 or not logw.is_contiguous() or dev.type != "cuda":
+        raise ValueError("resample: logw must be a contiguous fp64 [B * S] tensor on the GPU")
+    R, S = logw.shape[0], int(samples)
+    if S < 1 or R % S:
+        raise ValueError(f"resample: {R} rows are no multiple of samples={samples}")
+    B = R // S
+    if (log_evidence.dtype != torch.float64 or log_evidence.shape != (B,) or not log_evidence.is_contiguous()
+            or log_evidence.device != dev):
+        raise ValueError(f"resample: log_evidence must be a contiguous fp64 [{B}] tensor on the GPU")
+    if len(logprobs) > 8:
+        raise ValueError("resample: at most 8 log-probability matrices")
+    N = None
+    for lp in logprobs:
+        if lp.dtype != torch.float32 or lp.dim() != 2 or lp.shape[0] != R or lp.device != dev or (
+                lp.shape[1] > 1 and lp.stride(1) != 1):
+            raise ValueError(f"resample: every logprobs must be an fp32 [{R}, N] tensor on the GPU, rows contiguous")
+        if N is not None and lp.shape[1] != N:
+            raise ValueError("resample: the logprobs must share N")
+        N = lp.shape[1]
+    N = 0 if N is None else N
+    j1 = N if j1 is None else int(j1)
+    if not 0 <= int(j0) <= j1 <= N:
+        raise ValueError(f"resample: columns [{j0}, {j1}) outside 0..{N}")
+    if ess_threshold != ess_threshold:
+        raise ValueError("resample: ess_threshold must not be NaN")
+    if S > RESAMPLE_MAX_SAMPLES:
+        raise ValueError(f"resample: samples={S} exceeds {RESAMPLE_MAX_SAMPLES}")
+    anc = torch.empty(R, dtype=torch.int32, device=dev)
+    res = torch.empty(B, dtype=torch.int32, device=dev)
+    rl = ResampleLaunch([lp.data_ptr() for lp in logprobs], [max(int(lp.stride(0)), N) for lp in logprobs])
+    with torch.cuda.device(dev):
+        rl.run(ML.lib(), ML.stream_ptr(dev), B, S, int(j0), j1, logw.data_ptr(), log_evidence.data_ptr(),
+               ess_threshold, seed, pos, anc.data_ptr(), res.data_ptr())
+    return anc, res

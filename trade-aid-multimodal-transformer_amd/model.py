@@ -56,13 +56,27 @@ GENERATED, GIVEN, HELD = "generated", "given", "held"
 class JointPlan:
     """What plan_joint returns for the list form of generate: `roles[i]` in (GENERATED, GIVEN, HELD), `generated`
     the generated modalities in ascending order, `given` {modality: the caller's int64 tensor}, and the checked
-    shape: B prompts of n0 tokens, N new tokens."""
+    shape: B prompts of n0 tokens, N new tokens. `evidence` is None, "weights" or "resample", with it
+    `resample_every`, `ess_threshold` and `points`, the new-token indices j after whose sampling the paths are
+    resampled (resample_points; empty unless evidence == "resample")."""
 
-    def __init__(self, roles, generated, given, B, n0, N):
+    def __init__(self, roles, generated, given, B, n0, N, evidence=None, resample_every=1, ess_threshold=0.5):
         self.roles, self.generated, self.given, self.B, self.n0, self.N = roles, generated, given, B, n0, N
+        self.evidence, self.resample_every, self.ess_threshold = evidence, resample_every, ess_threshold
+        self.points = resample_points(N, resample_every) if evidence == "resample" else []
 
 
-def plan_joint(modality_to_generate, given, vocab_sizes, prompt_shapes, max_new_tokens, num_samples=None):
+EVIDENCE_MODES = (None, "weights", "resample")
+
+
+def resample_points(N, resample_every):
+    """The fixed schedule of generate(evidence="resample"): the paths are resampled after the sampling of new token
+    j whenever (j + 1) % resample_every == 0 and j < N - 1 (after the last token nothing is left to steer)."""
+    return [j for j in range(N - 1) if (j + 1) % resample_every == 0]
+
+
+def plan_joint(modality_to_generate, given, vocab_sizes, prompt_shapes, max_new_tokens, num_samples=None,
+               evidence=None, resample_every=1, ess_threshold=0.5):
     """generate's `modality_to_generate` and `given` as per-modality roles, every refusal of the list form that
     needs no device in one place. An int (the int form: one modality sampled, generate as it always ran) returns
     None, and refuses `given`. A sequence of distinct ints, even of one, or "all" is the list form (a joint
@@ -71,9 +85,28 @@ def plan_joint(modality_to_generate, given, vocab_sizes, prompt_shapes, max_new_
     token. ValueError for: a modality named twice, out of range or not an int; an empty list; a modality both
     generated and given; a given tensor of another dtype or shape, or with a token outside 0..V_i - 1; a wrong
     number of prompts; prompts that are not [B, n0 >= 1] of one shape (the reference's pad / crop rule is defined
-    around one generated modality)."""
+    around one generated modality). `evidence` ("weights" or "resample": the importance weights of the given series,
+    generate's docstring) is refused without a given modality, with an unknown value, with resample_every < 1
+    or no integer, with a negative or NaN ess_threshold, and as "resample" without num_samples."""
     M = len(vocab_sizes)
     g = modality_to_generate
+    if evidence not in EVIDENCE_MODES:
+        raise ValueError(f"generate: evidence must be None, \"weights\" or \"resample\", got {evidence!r}")
+    if evidence is not None:
+        if not given:
+            raise ValueError("generate: evidence= needs a given modality (given={modality: tokens}): the weights are "
+                             "the probabilities of the given tokens")
+        if isinstance(resample_every, bool) or not isinstance(resample_every, int) or resample_every < 1:
+            raise ValueError(f"generate: resample_every must be an integer >= 1, got {resample_every!r}")
+        try:
+            thr_ok = float(ess_threshold) >= 0.0
+        except (TypeError, ValueError):
+            thr_ok = False
+        if not thr_ok:
+            raise ValueError(f"generate: ess_threshold must be a number >= 0, got {ess_threshold!r}")
+        if evidence == "resample" and num_samples is None:
+            raise ValueError("generate: evidence=\"resample\" resamples the num_samples paths of each prompt: pass "
+                             "num_samples")
     if isinstance(g, int) and not isinstance(g, bool):
         if given is not None:
             raise ValueError("generate: given= needs the list form of modality_to_generate (a sequence or \"all\")")
@@ -123,7 +156,8 @@ def plan_joint(modality_to_generate, given, vocab_sizes, prompt_shapes, max_new_
         if t.numel() and (int(t.min()) < 0 or int(t.max()) >= vocab_sizes[i]):
             raise ValueError(f"generate: given[{i}] holds tokens outside 0..{vocab_sizes[i] - 1}")
     roles = [GENERATED if i in gen else GIVEN if i in given else HELD for i in range(M)]
-    return JointPlan(roles, sorted(gen), dict(given), B, n0, N)
+    return JointPlan(roles, sorted(gen), dict(given), B, n0, N, evidence, resample_every,
+                     0.5 if evidence is None else float(ess_threshold))
 
 
 def joint_setting(value, generated, name):
@@ -593,7 +627,7 @@ class MultimodalTransformer(nn.Module):
     @torch.no_grad()
     def generate(self, idx_list, max_new_tokens=1, modality_to_generate=0, use_cache=True, sample_fn=None, *,
                  temperature=None, top_k=None, top_p=None, seed=None, return_logprobs=False, logits_hook=None,
-                 num_samples=None, given=None):
+                 num_samples=None, given=None, evidence=None, resample_every=1, ess_threshold=0.5):
         """model.py:404-446: per new token, the logits of the last position of the (block_size
         cropped) context, a sample from the softmax of the target modality's last logits
         (torch.multinomial, as the reference; `sample_fn(probs) -> [B, 1]` overrides it), appended;
@@ -632,11 +666,32 @@ class MultimodalTransformer(nn.Module):
         this form temperature / top_k / top_p are scalars or {modality: value} dicts, logits_hook(n, logits_list)
         sees the [rows, V_i] views of all modalities, return_logprobs gives (sequences, {i: fp32 [rows, N]}),
         sample_fn and prompts of unequal lengths are refused (plan_joint lists every refusal), and num_samples runs
-        the fan-out engine under the conditions above. An int runs exactly as it always did."""
+        the fan-out engine under the conditions above. An int runs exactly as it always did.
+
+        Evidence of a given series (list form with given=): a forced series makes the paths samples of "the model
+        with modality i overwritten", not of "the model given that modality i does this". The heads are
+        conditionally independent given the history, so the probability of the forced token under its own head is
+        the path's importance weight. evidence="weights" scores every given token on the device (one
+        mmt_score_multi launch per token over the views the sampler reads, on every path: cached, fan-out, tiled,
+        re-forward, fp8) and returns a last element `ev`, a dict: "given_logprobs" {i: fp32 [rows, N]},
+        "log_weights" fp64 [rows] (the sum over j, then over the given i ascending), "log_evidence" fp64 [B] (the log
+        of the mean weight of a prompt's paths, the estimate of log p(given series | prompt); B = rows without
+        num_samples), "ancestors" int32 [points, rows], "resampled" int32 [points, B] and "steps" (the j of every
+        resampling point; none here). Sequences and sampled log-probabilities are bit-identical to the call without
+        evidence. evidence="resample" also turns the weighted paths into posterior paths (a particle filter,
+        mmt_resample in include/mmt.h): after the sampling of new token j, whenever (j + 1) % resample_every == 0 and
+        j < N - 1, every prompt whose effective sample size fell below ess_threshold * S redraws its S paths from
+        their weights (systematic resampling; the others keep theirs), the sequences, log-probabilities and fan-out
+        tails follow their ancestors (mmt_fanout_gather), the weights restart at 1 and log_evidence keeps the
+        product. The host follows the fixed schedule and never reads the device's verdict; draws stay keyed by
+        (seed, current row, position), so copies of one ancestor diverge at the next step. It needs num_samples
+        (at most 4096) and the fan-out engine's conditions and raises ValueError otherwise (no fallback), and it
+        holds two fan buffers. Returned rows are the final paths: "given_logprobs" are those of each path's own
+        history, "log_weights" the weights since the last resampling point."""
         if num_samples is not None:
             num_samples = check_num_samples(num_samples)
         plan = plan_joint(modality_to_generate, given, self.vocab_sizes, [tuple(s.shape) for s in idx_list],
-                          max_new_tokens, num_samples)
+                          max_new_tokens, num_samples, evidence, resample_every, ess_threshold)
         if plan is not None:
             if sample_fn is not None:
                 raise ValueError("generate: sample_fn cannot be combined with a joint rollout (a list of modalities "
@@ -869,7 +924,10 @@ class MultimodalTransformer(nn.Module):
         (with num_samples under the fan-out conditions of `_generate_samples`: one fan-out step over B*S rows) and
         one mmt_sample_multi: no torch op, no sync. Past block_size, with use_cache=False, in training mode with
         dropout and at fp8 a step is the re-forward over the cropped buffers, and each problem reads its
-        modality's last-position logits in place."""
+        modality's last-position logits in place. With plan.evidence a step also issues one mmt_score_multi over
+        the given modalities' views and the given tokens of column n, which the sequence buffers hold; "resample"
+        adds, at the plan's points, mmt_resample, an index_select of every per-row buffer and mmt_fanout_gather
+        into the second fan buffer; a closing mmt_resample folds the remaining columns."""
         import mmt_sample as MS
         flat = self.flat_params
         dev = flat.device
@@ -887,6 +945,14 @@ class MultimodalTransformer(nn.Module):
         nbytes = L.mmt_fanout_bytes(self._ctx, plan.B, S, N) if fan else 0
         if nbytes < 0:
             raise ValueError(f"generate: {plan.B} prompts x {S} samples are more rows than the decode launches address")
+        if plan.evidence == "resample" and not (fan and S <= MS.RESAMPLE_MAX_SAMPLES):
+            raise ValueError(
+                "generate: evidence=\"resample\" runs on the fan-out engine only: it needs num_samples (at most "
+                f"{MS.RESAMPLE_MAX_SAMPLES}), use_cache, eval mode or no dropout, precision bf16, max_new_tokens >= 1 and "
+                "n0 + max_new_tokens <= block_size")
+        if plan.evidence is not None and S is not None and S > MS.RESAMPLE_MAX_SAMPLES:
+            raise ValueError(f"generate: evidence= folds the weights of at most {MS.RESAMPLE_MAX_SAMPLES} samples per "
+                             f"prompt, got num_samples={S}")
         if S is not None:
             self.last_generate_path = "fanout" if fan else "tiled"
         prompts = [s.to(device=dev, dtype=torch.long).contiguous() for s in idx_list]
@@ -912,6 +978,19 @@ class MultimodalTransformer(nn.Module):
             ml.compact[p] = compact[i].data_ptr()
         dec_logits = p_idx = p_logits = None
         p_flat = ML.ptr(flat)
+        # evidence: one scoring problem per given modality, over the views the sampler reads and the given token of
+        # column n, which the sequence buffers already hold; the fp64 weights per row and evidence per prompt
+        giv = sorted(plan.given) if plan.evidence is not None else []
+        if giv:
+            glp = {i: torch.zeros(R, N, dtype=torch.float32, device=dev) for i in giv}
+            sl = MS.ScoreLaunch([self.vocab_sizes[i] for i in giv], [cap] * len(giv), [N] * len(giv))
+            Bp, Sp = (plan.B, S) if S is not None else (R, 1)  # without num_samples every row is a prompt of one path
+            logw = torch.zeros(R, dtype=torch.float64, device=dev)
+            logev = torch.zeros(Bp, dtype=torch.float64, device=dev)
+            npts = len(plan.points)
+            anc = torch.empty(npts + 1, R, dtype=torch.int32, device=dev)  # the last row: the closing fold's identity
+            res = torch.empty(npts + 1, Bp, dtype=torch.int32, device=dev)
+            rl = MS.ResampleLaunch([glp[i].data_ptr() for i in giv], [N] * len(giv))
 
         def decode_args(j):
             """The pointer arrays of the decode step that reads the tokens of new position j (made at first use)."""
@@ -932,6 +1011,27 @@ class MultimodalTransformer(nn.Module):
                 ml.tok[p] = bufs[i].data_ptr() + 8 * n
                 ml.logprob[p] = lps[i].data_ptr() + 4 * j if lps is not None else None
             ml.run(L, stream, R, 0, n)
+            if giv:
+                for p, i in enumerate(giv):
+                    sl.logits[p] = views[i].data_ptr()
+                    sl.row_stride[p] = int(views[i].stride(0)) if R > 1 else self.vocab_sizes[i]
+                    sl.tok[p] = bufs[i].data_ptr() + 8 * n
+                    sl.logprob[p] = glp[i].data_ptr() + 4 * j
+                sl.run(L, stream, R)
+
+        def fold(j0, j1, threshold, pos, point):
+            """mmt_resample over the given log-probabilities of the new tokens j0..j1-1 into row `point` of the
+            ancestors / resampled records."""
+            rl.run(L, stream, Bp, Sp, j0, j1, logw.data_ptr(), logev.data_ptr(), threshold, seed, pos,
+                   anc.data_ptr() + 4 * R * point, res.data_ptr() + 4 * Bp * point)
+
+        def follow(a):
+            """Every per-row buffer follows its ancestor (in place: the launch arrays keep their addresses)."""
+            a = a.long()
+            for t in bufs + list(compact.values()) + list(glp.values()) + (list(lps.values()) if lps else []):
+                t.copy_(t.index_select(0, a))
+            for st in steps.values():
+                st.copy_(st.index_select(1, a))
 
         with torch.cuda.device(dev):
             stream = ML.stream_ptr(dev)
@@ -941,6 +1041,10 @@ class MultimodalTransformer(nn.Module):
                 first = [lg[:, -1, :].index_select(0, sel) for lg in logits]  # each sample's copy of its prompt's row
                 fanbuf = torch.empty(nbytes, dtype=torch.uint8, device=dev)
                 p_ws, p_fan = ML.ptr(self._ws), ML.ptr(fanbuf)
+                if plan.points:  # the second fan buffer: the tails are gathered from one into the other
+                    fanbuf2 = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+                    p_fan2 = ML.ptr(fanbuf2)
+                last_point, point = 0, 0
                 for j in range(N):
                     n = n0 + j
                     if j == 0:
@@ -952,6 +1056,19 @@ class MultimodalTransformer(nn.Module):
                         ML.check(rc, self._ctx, "mmt_decode_fanout_step")
                         views = dec_logits
                     sample(n, j, views)
+                    if point < len(plan.points) and plan.points[point] == j:
+                        # the fixed schedule: weights of the columns since the last point, ancestors (the identity for
+                        # a prompt that did not trigger), then every per-row buffer and the tails follow them
+                        fold(last_point, j + 1, plan.ess_threshold, n, point)
+                        follow(anc[point])
+                        if j >= 1:
+                            rc = L.mmt_fanout_gather(self._ctx, stream, plan.B, S, n0, N, j,
+                                                     anc.data_ptr() + 4 * R * point, p_fan, p_fan2)
+                            ML.check(rc, self._ctx, "mmt_fanout_gather")
+                            p_fan, p_fan2 = p_fan2, p_fan
+                        last_point, point = j + 1, point + 1
+                if giv:
+                    fold(last_point, N, -1.0, n0 + N - 1, len(plan.points))  # the closing fold: no resampling
             else:
                 cached_pos = None  # the last position whose keys / values the workspace holds
                 for j in range(N):
@@ -969,7 +1086,13 @@ class MultimodalTransformer(nn.Module):
                         views = [lg[:, -1, :] for lg in logits]
                         cached_pos = n - 1 if (cache and n <= T) else None
                     sample(n, j, views)
+                if giv:
+                    fold(0, N, -1.0, n0 + N - 1, 0)
         seqs = [buf.to(idx_list[i].dtype) for i, buf in enumerate(bufs)]
+        if giv:
+            ev = {"given_logprobs": glp, "log_weights": logw, "log_evidence": logev, "ancestors": anc[:npts],
+                  "resampled": res[:npts], "steps": list(plan.points)}
+            return (seqs, lps, ev) if return_logprobs else (seqs, ev)
         return (seqs, lps) if return_logprobs else seqs
 
     @torch.no_grad()
