@@ -593,6 +593,35 @@ int mmt_op_attention_bwd_ws(void* stream, int32_t B, int32_t T, int32_t H, int32
                             const float* const* lse, const void* dout, int32_t dout_ld, float* const* dvec, void* dq,
                             int32_t dq_ld, void* const* dk, void* const* dv, int32_t dkv_ld, int32_t dkv_hstride,
                             float* dq32, int32_t dq32_ld);
+/* Dropout of the normalised attention probabilities, as the engine's training forward runs it. The keep bits
+ * are made once per (key, shape) by mmt_op_attention_mask and read by the forward and the backward:
+ * element (query t, key s) of stream j, head slot bh = b*H + h is kept iff the 16-bit half (s & 1) of
+ * prob_hash(hash(hash(drop_key, j, stream salt), bh*T + t, row salt), s >> 1) is >= drop_thr (csrc/mmt_common.h;
+ * drop_thr = 0: no dropout, nothing read or written); kept probabilities are scaled by drop_scale.
+ * mmt_op_attention_mask fills the buffers of `count` (1..8) problems of one shape in one launch: nstreams,
+ * drop_key and drop_thr are host arrays of `count` entries, dmask a host array of count * 8 device pointers
+ * (problem g, stream j at dmask[g * 8 + j]; entries j >= nstreams[g] are not read), each to
+ * mmt_op_attention_mask_dwords(B, H, T) dwords: per 32 x 32 tile (bh, query tile qt, key tile kt <= qt), index
+ * bh * ntri + qt (qt + 1) / 2 + kt, a 32-dword key-major record, then after all of those the tiles' 32-dword
+ * lane-word records. MMT_ERR_INVALID before any launch for count outside 1..8, a null array, nstreams[g] outside
+ * 1..8 or a null buffer of a problem with drop_thr != 0. */
+int64_t mmt_op_attention_mask_dwords(int32_t B, int32_t H, int32_t T);
+int mmt_op_attention_mask(void* stream, int32_t count, int32_t B, int32_t T, int32_t H, const int32_t* nstreams,
+                          const uint32_t* drop_key, const uint32_t* drop_thr, uint32_t* const* dmask);
+/* mmt_op_attention_fwd / _bwd_ws with that dropout (dmask: host array of nstreams device pointers, filled by
+ * mmt_op_attention_mask for the same drop_key, drop_thr, B, T, H; not read when drop_thr == 0, then the calls
+ * are the ones above). MMT_ERR_INVALID for drop_thr != 0 with a null dmask. */
+int mmt_op_attention_fwd_drop(void* stream, int32_t B, int32_t T, int32_t H, int32_t hs, int32_t nstreams,
+                              const void* q, int32_t q_ld, const void* const* k, const void* const* v, int32_t kv_ld,
+                              int32_t kv_hstride, void* o, int32_t o_ld, void* const* oj, float* const* lse,
+                              uint32_t drop_key, uint32_t drop_thr, float drop_scale, uint32_t* const* dmask);
+int mmt_op_attention_bwd_drop(void* stream, int32_t B, int32_t T, int32_t H, int32_t hs, int32_t nstreams,
+                              const void* q, int32_t q_ld, const void* const* k, const void* const* v, int32_t kv_ld,
+                              int32_t kv_hstride, const void* o, int32_t o_ld, const void* const* oj,
+                              const float* const* lse, const void* dout, int32_t dout_ld, float* const* dvec, void* dq,
+                              int32_t dq_ld, void* const* dk, void* const* dv, int32_t dkv_ld, int32_t dkv_hstride,
+                              float* dq32, int32_t dq32_ld, uint32_t drop_key, uint32_t drop_thr, float drop_scale,
+                              uint32_t* const* dmask);
 /* KV-cache decode attention, the kernel under mmt_decode_step: ONE query position t (0 <= t < T) per sequence
  * against the cached keys / values of positions 0..t, one softmax per KV stream (scale = hs^-0.5), the
  * per-stream outputs summed. q and o are compact [B, *] bf16 (row b, head h at column h*hs, row strides q_ld /
@@ -633,6 +662,14 @@ int mmt_op_attention_fwd_h1(void* stream, int32_t B, int32_t T, int32_t H, const
 int mmt_op_attention_bwd_h1(void* stream, int32_t B, int32_t T, int32_t H, const void* h1, int32_t ld_h1,
                             const float* w2, const void* o, int32_t o_ld, const float* lse, const void* dout,
                             int32_t dout_ld, void* dh1, float* dw2, float* db1);
+/* the same two with dropout of the probabilities (one stream: dmask is the device buffer itself) */
+int mmt_op_attention_fwd_h1_drop(void* stream, int32_t B, int32_t T, int32_t H, const void* h1, int32_t ld_h1,
+                                 const float* w2, void* o, int32_t o_ld, float* lse, uint32_t drop_key,
+                                 uint32_t drop_thr, float drop_scale, uint32_t* dmask);
+int mmt_op_attention_bwd_h1_drop(void* stream, int32_t B, int32_t T, int32_t H, const void* h1, int32_t ld_h1,
+                                 const float* w2, const void* o, int32_t o_ld, const float* lse, const void* dout,
+                                 int32_t dout_ld, void* dh1, float* dw2, float* db1, uint32_t drop_key,
+                                 uint32_t drop_thr, float drop_scale, uint32_t* dmask);
 int mmt_op_qkv2_fwd(void* stream, int32_t R, int32_t nblk, int32_t hs, const void* h1, int32_t ld_h1,
                     const float* w2, void* out, int32_t ld_out);
 int mmt_op_qkv2_bwd(void* stream, int32_t R, int32_t nblk, int32_t hs, const void* h1, int32_t ld_h1,

@@ -257,14 +257,22 @@ class HashDropout:
         rows = (np.arange(B)[:, None, None] * T + np.arange(T)[None, :, None]).astype(np.int64)
         return self._mask(self.key(l, i, site), rows, np.arange(C)[None, None, :])
 
-    def probs(self, l, i, site, j, h, H, B, T):
-        """[B, T, T] probabilities of head h, stream j: row (b*H + h)*T + t, column s."""
-        kj = int(mask_hash(self.key(l, i, site), j, STREAM_SALT))
-        rows = ((np.arange(B)[:, None, None] * H + h) * T + np.arange(T)[None, :, None]).astype(np.int64)
-        cols = np.arange(T, dtype=np.int64)[None, None, :]
+    @staticmethod
+    def probs_raw(key, j, rows, cols, thr):
+        """bool keep bits of stream j under the raw drop key `key` (AttnProblem::drop_key): score rows `rows`
+        (bh*T + t) against key columns `cols`, broadcast together."""
+        kj = int(mask_hash(key, j, STREAM_SALT))
+        cols = np.asarray(cols, dtype=np.int64)
         hsh = prob_hash(mask_hash(kj, rows, PROB_ROW_SALT), cols >> 1)  # mmt_prob_row / mmt_prob_hash
         half = (hsh >> ((cols & 1).astype(_U32) * _U32(16))) & _U32(0xFFFF)
-        return torch.from_numpy((half >= _U32(self.thr)).astype(np.float32) * np.float32(self.scale))
+        return half >= _U32(thr)
+
+    def probs(self, l, i, site, j, h, H, B, T):
+        """[B, T, T] probabilities of head h, stream j: row (b*H + h)*T + t, column s."""
+        rows = ((np.arange(B)[:, None, None] * H + h) * T + np.arange(T)[None, :, None]).astype(np.int64)
+        cols = np.arange(T, dtype=np.int64)[None, None, :]
+        keep = self.probs_raw(self.key(l, i, site), j, rows, cols, self.thr)
+        return torch.from_numpy(keep.astype(np.float32) * np.float32(self.scale))
 
 
 def _drop(x, p, training, mask_fn=None):

@@ -45,7 +45,25 @@ def _inputs(B, T, H, pad):
     return _bf(h1), ld_h1, w2, _bf(do)
 
 
-def _materialised_forward(B, T, H, h1, ld_h1, w2):
+DROP_P = 0.1
+DROP_KEY = 0x0C5EED01
+
+
+def _dropout(B, T, H):
+    """(drop_key, drop_thr, drop_scale, keep-bit buffer) of p = DROP_P, the bits from mmt_op_attention_mask."""
+    import attn_drop_ref as DR
+    L = ML.lib()
+    thr, c = DR.thr_of(DROP_P), DR.scale_of(DROP_P)
+    dmask = torch.zeros(L.mmt_op_attention_mask_dwords(B, H, T), dtype=torch.int32, device=DEV)
+    mp = (ctypes.c_void_p * 8)(dmask.data_ptr())
+    assert L.mmt_op_attention_mask(_s(), 1, B, T, H, (ctypes.c_int32 * 1)(1), (ctypes.c_uint32 * 1)(DROP_KEY),
+                                   (ctypes.c_uint32 * 1)(thr), mp) == 0
+    torch.cuda.synchronize()
+    assert dmask.any()
+    return DROP_KEY, thr, c, dmask
+
+
+def _materialised_forward(B, T, H, h1, ld_h1, w2, drop=None):
     """mmt_op_qkv2_fwd + mmt_op_attention_fwd on clean copies of the rows: qkv, O, LSE."""
     L = ML.lib()
     R, C = B * T, H * 32
@@ -56,8 +74,11 @@ def _materialised_forward(B, T, H, h1, ld_h1, w2):
     lse = torch.zeros(B * H * T, device=DEV)
     kp = (ctypes.c_void_p * 1)(qkv.data_ptr())
     vp = (ctypes.c_void_p * 1)(qkv[:, 2 * C:].data_ptr())
-    assert L.mmt_op_attention_fwd(_s(), B, T, H, 32, 1, ML.ptr(qkv[:, C:]), 3 * C, kp, vp, 3 * C, 32, ML.ptr(o), C,
-                                  None, ML.ptr_array([lse])) == 0
+    args = (_s(), B, T, H, 32, 1, ML.ptr(qkv[:, C:]), 3 * C, kp, vp, 3 * C, 32, ML.ptr(o), C, None, ML.ptr_array([lse]))
+    if drop is None:
+        assert L.mmt_op_attention_fwd(*args) == 0
+    else:
+        assert L.mmt_op_attention_fwd_drop(*args, drop[0], drop[1], drop[2], (ctypes.c_void_p * 1)(drop[3].data_ptr())) == 0
     torch.cuda.synchronize()
     return clean, qkv, o, lse
 
@@ -70,7 +91,7 @@ SHAPES = [(2, 256, 8), (3, 37, 2), (1, 33, 2), (1, 2, 2), (2, 96, 1)]
 
 @pytest.mark.parametrize("pad", [0, 8])
 @pytest.mark.parametrize("B,T,H", SHAPES)
-def test_forward_from_h1_same_bits_as_materialised(B, T, H, pad):
+def test_forward_from_h1_same_bits_as_materialised(B, T, H, pad, drop=None):
     """O and LSE against mmt_op_qkv2_fwd + mmt_op_attention_fwd, bitwise. (The hs-32 stage-2 kernel behind
     mmt_op_qkv2_fwd feeds its MFMA in the K-slot order of the stage-1 GEMM's epilogue, as the on-chip kernels do: in
     the natural order its rows differed from the epilogue's by one bf16 ulp in 2 of 393216 entries at (2, 256, 8),
@@ -78,10 +99,14 @@ def test_forward_from_h1_same_bits_as_materialised(B, T, H, pad):
     L = ML.lib()
     R, C = B * T, H * 32
     h1, ld_h1, w2, _ = _inputs(B, T, H, pad)
-    _, _, o_ref, lse_ref = _materialised_forward(B, T, H, h1, ld_h1, w2)
+    _, _, o_ref, lse_ref = _materialised_forward(B, T, H, h1, ld_h1, w2, drop)
     o = torch.zeros(R + GUARD, C, dtype=torch.bfloat16, device=DEV)
     lse = torch.zeros(B * H * T, device=DEV)
-    assert L.mmt_op_attention_fwd_h1(_s(), B, T, H, ML.ptr(h1), ld_h1, ML.ptr(w2), ML.ptr(o), C, ML.ptr(lse)) == 0
+    args = (_s(), B, T, H, ML.ptr(h1), ld_h1, ML.ptr(w2), ML.ptr(o), C, ML.ptr(lse))
+    if drop is None:
+        assert L.mmt_op_attention_fwd_h1(*args) == 0
+    else:
+        assert L.mmt_op_attention_fwd_h1_drop(*args, drop[0], drop[1], drop[2], ML.ptr(drop[3])) == 0
     torch.cuda.synchronize()
     assert torch.isfinite(o.float()).all() and torch.isfinite(lse).all()
     assert o_ref.float().abs().max() > 0
@@ -127,11 +152,11 @@ def test_forward_from_h1_same_bits_as_gemm_epilogue_rows(B, T, H):
 
 @pytest.mark.parametrize("pad", [0, 8])
 @pytest.mark.parametrize("B,T,H", SHAPES)
-def test_backward_from_h1_matches_materialised(B, T, H, pad):
+def test_backward_from_h1_matches_materialised(B, T, H, pad, drop=None):
     L = ML.lib()
     R, C, nblk = B * T, H * 32, 3 * H
     h1, ld_h1, w2, do = _inputs(B, T, H, pad)
-    clean, qkv, o, lse = _materialised_forward(B, T, H, h1, ld_h1, w2)
+    clean, qkv, o, lse = _materialised_forward(B, T, H, h1, ld_h1, w2, drop)
     # reference: the one-pass backward (mmt_attn_set_ring bit 6) writes bf16 dQ / dK / dV, then the stage-2 backward
     old = L.mmt_attn_set_ring(15 | 64)
     try:
@@ -142,9 +167,14 @@ def test_backward_from_h1_matches_materialised(B, T, H, pad):
         dkp = (ctypes.c_void_p * 1)(dqkv.data_ptr())
         dvp = (ctypes.c_void_p * 1)(dqkv[:, 2 * C:].data_ptr())
         do_clean = do[:R].contiguous()
-        assert L.mmt_op_attention_bwd(_s(), B, T, H, 32, 1, ML.ptr(qkv[:, C:]), 3 * C, kp, vp, 3 * C, 32, ML.ptr(o), C,
-                                      None, ML.ptr_array([lse]), ML.ptr(do_clean), C, ML.ptr_array([dvec]),
-                                      ML.ptr(dqkv[:, C:]), 3 * C, dkp, dvp, 3 * C, 32) == 0
+        args = (_s(), B, T, H, 32, 1, ML.ptr(qkv[:, C:]), 3 * C, kp, vp, 3 * C, 32, ML.ptr(o), C, None,
+                ML.ptr_array([lse]), ML.ptr(do_clean), C, ML.ptr_array([dvec]), ML.ptr(dqkv[:, C:]), 3 * C, dkp, dvp,
+                3 * C, 32)
+        if drop is None:
+            assert L.mmt_op_attention_bwd(*args) == 0
+        else:
+            assert L.mmt_op_attention_bwd_drop(*args, None, 0, drop[0], drop[1], drop[2],
+                                               (ctypes.c_void_p * 1)(drop[3].data_ptr())) == 0
         dh1_ref = torch.zeros(R, ld_h1, dtype=torch.bfloat16, device=DEV)
         dw2_ref = torch.zeros_like(w2)
         assert L.mmt_op_qkv2_bwd(_s(), R, nblk, 32, ML.ptr(clean), ld_h1, ML.ptr(w2), ML.ptr(dqkv), 3 * C,
@@ -157,8 +187,12 @@ def test_backward_from_h1_matches_materialised(B, T, H, pad):
         dh1 = torch.zeros(R + GUARD, ld_h1, dtype=torch.bfloat16, device=DEV)
         dw2 = torch.zeros_like(w2)
         db1 = torch.zeros(nblk * 16, device=DEV)
-        assert L.mmt_op_attention_bwd_h1(_s(), B, T, H, ML.ptr(h1), ld_h1, ML.ptr(w2), ML.ptr(o_g), C, ML.ptr(lse_g),
-                                         ML.ptr(do), C, ML.ptr(dh1), ML.ptr(dw2), ML.ptr(db1)) == 0
+        args = (_s(), B, T, H, ML.ptr(h1), ld_h1, ML.ptr(w2), ML.ptr(o_g), C, ML.ptr(lse_g), ML.ptr(do), C, ML.ptr(dh1),
+                ML.ptr(dw2), ML.ptr(db1))
+        if drop is None:
+            assert L.mmt_op_attention_bwd_h1(*args) == 0
+        else:
+            assert L.mmt_op_attention_bwd_h1_drop(*args, drop[0], drop[1], drop[2], ML.ptr(drop[3])) == 0
         torch.cuda.synchronize()
     finally:
         L.mmt_attn_set_ring(old)
@@ -175,6 +209,29 @@ def test_backward_from_h1_matches_materialised(B, T, H, pad):
     cols = dh1[:R, : nblk * 16].float()
     slack = cols.abs().sum(0) * (2.0 ** -8 + 1e-5) + 1e-6
     assert ((db1 - cols.sum(0)).abs() <= slack).all(), ((db1 - cols.sum(0)).abs() / slack).max().item()
+
+
+# the smallest shape and T = 256, under dropout of the probabilities (p = 0.1): both paths read the same keep bits
+DROP_SHAPES = [(1, 2, 2), (2, 256, 8)]
+
+
+@pytest.mark.parametrize("B,T,H", DROP_SHAPES)
+def test_forward_from_h1_dropout_same_bits_as_materialised(B, T, H):
+    """mmt_op_attention_fwd_h1_drop against mmt_op_attention_fwd_drop on the materialised Q/K/V: O and LSE bitwise,
+    and the mask acts (O differs from the forward without dropout)."""
+    drop = _dropout(B, T, H)
+    test_forward_from_h1_same_bits_as_materialised(B, T, H, 8, drop)
+    h1, ld_h1, w2, _ = _inputs(B, T, H, 8)
+    _, _, o_drop, lse_drop = _materialised_forward(B, T, H, h1, ld_h1, w2, drop)
+    _, _, o_plain, lse_plain = _materialised_forward(B, T, H, h1, ld_h1, w2)
+    assert not torch.equal(o_drop, o_plain) and torch.equal(lse_drop, lse_plain)
+
+
+@pytest.mark.parametrize("B,T,H", DROP_SHAPES)
+def test_backward_from_h1_dropout_matches_materialised(B, T, H):
+    """mmt_op_attention_bwd_h1_drop against the materialised one-pass backward with the same keep bits, at
+    test_backward_from_h1_matches_materialised's bounds."""
+    test_backward_from_h1_matches_materialised(B, T, H, 8, _dropout(B, T, H))
 
 
 def test_unsupported_shapes_are_refused_not_run():

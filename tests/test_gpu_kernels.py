@@ -508,15 +508,19 @@ def test_mlp2_bwd_fused(M, C):
 
 
 # --------------------------------------------------------------------------------- attention
-def _attn_ref(q, ks, vs, scale):
+def _attn_ref(q, ks, vs, scale, masks=None):
     # q [B,H,T,hs], ks/vs list of [B,H,T,hs]; sum over streams of causal softmax attention
+    # masks (optional): per stream the scaled dropout mask [B,H,T,T] of the probabilities (keep / (1 - p))
     T = q.shape[2]
     mask = torch.tril(torch.ones(T, T, device=q.device)) == 0
     out = 0
-    for k, v in zip(ks, vs):
+    for j, (k, v) in enumerate(zip(ks, vs)):
         a = (q @ k.transpose(-1, -2)) * scale
         a = a.masked_fill(mask, float("-inf"))
-        out = out + torch.softmax(a, -1) @ v
+        pr = torch.softmax(a, -1)
+        if masks is not None:
+            pr = pr * masks[j]
+        out = out + pr @ v
     return out
 
 
@@ -525,7 +529,9 @@ def _attn_ref(q, ks, vs, scale):
                                          # longer than one LDS chunk (256 rows at hs <= 32, 128 above)
                                          (1, 300, 2, 32, 1), (1, 300, 2, 32, 3), (1, 520, 2, 64, 2),
                                          (1, 1024, 1, 64, 1), (1, 257, 1, 24, 1)])
-def test_attention_fwd_bwd(B, T, H, hs, ns, scratch=False):
+def test_attention_fwd_bwd(B, T, H, hs, ns, scratch=False, drop=0.0):
+    """drop > 0 (test_attention_fwd_bwd_dropout): the same comparison under dropout of the probabilities, the keep
+    bits from mmt_op_attention_mask, the reference with the scaled hash mask of tests/attn_drop_ref.py."""
     torch.manual_seed(B * 1000 + T * 10 + hs + ns)
     C = H * hs
     R = B * T
@@ -553,19 +559,50 @@ def test_attention_fwd_bwd(B, T, H, hs, ns, scratch=False):
     qf = heads(q).requires_grad_(True)
     kf = [heads(k).requires_grad_(True) for k in ks]
     vf = [heads(v).requires_grad_(True) for v in vs]
-    ref = _attn_ref(qf, kf, vf, scale)
+    L = ML.lib()
+    masks, drop_args = None, ()
+    if drop:
+        import attn_drop_ref as DR
+        key, thr, c = 0xD0D0 + T, DR.thr_of(drop), DR.scale_of(drop)
+        masks = [torch.from_numpy(DR.keep_matrix(key, j, B, H, T, thr)).to(DEV).float() * c for j in range(ns)]
+        nd = L.mmt_op_attention_mask_dwords(B, H, T)
+        dmask = [torch.zeros(nd, dtype=torch.int32, device=DEV) for _ in range(ns)]
+        mp = (ctypes.c_void_p * 8)(*[t.data_ptr() for t in dmask])
+        assert L.mmt_op_attention_mask(_s(), 1, B, T, H, (ctypes.c_int32 * 1)(ns), (ctypes.c_uint32 * 1)(key),
+                                       (ctypes.c_uint32 * 1)(thr), mp) == 0
+        drop_args = (key, thr, c, mp)
+    ref = _attn_ref(qf, kf, vf, scale, masks)
     o = torch.zeros(R, C, dtype=torch.bfloat16, device=DEV)
     oj = [torch.zeros(R, C, dtype=torch.bfloat16, device=DEV) for _ in range(ns)]
     lse = [torch.zeros(B * H * T, device=DEV) for _ in range(ns)]
-    L = ML.lib()
     kp = (ctypes.c_void_p * ns)(*[t.data_ptr() for t in kptr])
     vp = (ctypes.c_void_p * ns)(*[t.data_ptr() for t in vptr])
-    rc = L.mmt_op_attention_fwd(_s(), B, T, H, hs, ns, ML.ptr(q), q_ld, kp, vp, kv_ld, kv_hs, ML.ptr(o), C,
-                                ML.ptr_array(oj), ML.ptr_array(lse))
+    fwd_args = (_s(), B, T, H, hs, ns, ML.ptr(q), q_ld, kp, vp, kv_ld, kv_hs, ML.ptr(o), C, ML.ptr_array(oj),
+                ML.ptr_array(lse))
+    rc = L.mmt_op_attention_fwd_drop(*fwd_args, *drop_args) if drop else L.mmt_op_attention_fwd(*fwd_args)
     assert rc == 0
     _sync()
     out = o.float().reshape(B, T, H, hs).permute(0, 2, 1, 3)
     assert rel(out, ref) < 1e-2, rel(out, ref)
+    errs = [rel(out, ref)]
+    if drop:  # lse is the unmasked softmax's, in the log2 domain: log2 sum_s 2^(log2(e) scale q.k_s)
+        causal = torch.tril(torch.ones(T, T, device=DEV)) == 0
+        for j in range(ns):
+            a = (qf.detach().double() @ kf[j].detach().double().transpose(-1, -2)) * (scale * 1.4426950408889634)
+            a = a.masked_fill(causal, float("-inf"))
+            want = torch.log2(torch.exp2(a).sum(-1))
+            got = lse[j].reshape(B, H, T).double()
+            # relative 1e-5 of the row's magnitude. An lse, and a score itself, can cancel to near 0 while the
+            # products it is summed from are O(1) (row 0 is one score): the fp32 dot product's error is relative to
+            # sum_i |q_i k_i|, so the scale is the larger of |lse| and the row's largest sum_i |q_i k_i| (log2 domain)
+            ab = (qf.detach().double().abs() @ kf[j].detach().double().abs().transpose(-1, -2)) * (scale * 1.4426950408889634)
+            mag = torch.maximum(want.abs(), ab.masked_fill(causal, 0.0).amax(-1))
+            ratio = (got - want).abs() / mag
+            i = int(ratio.argmax())
+            print(f"lse hs {hs} T {T} stream {j}: largest |error| / magnitude {ratio.flatten()[i].item():.3e} at row "
+                  f"{i % T} (lse {want.flatten()[i].item():.6f}, got {got.flatten()[i].item():.6f}, "
+                  f"largest sum |q k| {mag.flatten()[i].item():.3f})")
+            assert (ratio <= 1e-5).all(), (j, ratio.max().item())
     # backward
     do = bf(torch.randn(R, C, device=DEV))
     ref.backward(heads(do))
@@ -587,7 +624,13 @@ def test_attention_fwd_bwd(B, T, H, hs, ns, scratch=False):
             dkv_ld, dkv_hs]
     if scratch:  # fp32 dQ rows for the one-pass hs-32 backward over several KV streams (poisoned: fully written)
         dq32 = torch.full((R, C + 4), float("nan"), device=DEV)
-        rc = L.mmt_op_attention_bwd_ws(*args, ML.ptr(dq32), C + 4)
+        ws = (ML.ptr(dq32), C + 4)
+    else:
+        ws = (None, 0)
+    if drop:
+        rc = L.mmt_op_attention_bwd_drop(*args, *ws, *drop_args)
+    elif scratch:
+        rc = L.mmt_op_attention_bwd_ws(*args, *ws)
     else:
         rc = L.mmt_op_attention_bwd(*args)
     assert rc == 0
@@ -604,6 +647,39 @@ def test_attention_fwd_bwd(B, T, H, hs, ns, scratch=False):
     for j in range(ns):
         assert rel(heads(got_k[j]), kf[j].grad) < 2e-2, (j, rel(heads(got_k[j]), kf[j].grad))
         assert rel(heads(got_v[j]), vf[j].grad) < 2e-2, (j, rel(heads(got_v[j]), vf[j].grad))
+    if not drop:
+        return
+    # the masks act: the unmasked reference is more than 3x the achieved error away, in every output
+    errs += [rel(heads(got_q), qf.grad)]
+    errs += [rel(heads(got_k[j]), kf[j].grad) for j in range(ns)] + [rel(heads(got_v[j]), vf[j].grad) for j in range(ns)]
+    masked = [ref.detach(), qf.grad] + [k.grad for k in kf] + [v.grad for v in vf]
+    q0 = qf.detach().clone().requires_grad_(True)
+    k0 = [k.detach().clone().requires_grad_(True) for k in kf]
+    v0 = [v.detach().clone().requires_grad_(True) for v in vf]
+    plain = _attn_ref(q0, k0, v0, scale)
+    plain.backward(heads(do))
+    unmasked = [plain.detach(), q0.grad] + [k.grad for k in k0] + [v.grad for v in v0]
+    for e, a, b in zip(errs, masked, unmasked):
+        assert rel(b, a) > 3 * e, (rel(b, a), e)
+
+
+# one T per kernel path of tests/test_gpu_attn_dropout.py's table (the larger): (ring, hs, T, streams, scratch)
+DROP_PATHS = [(15, 16, 45, 1, False), (15, 16, 45, 2, False), (15, 32, 300, 1, False), (15, 32, 300, 3, False),
+              (15, 48, 96, 2, False), (79, 32, 256, 1, False), (79 | 128, 32, 100, 3, True), (0, 64, 160, 1, False),
+              (0, 64, 160, 2, False), (15, 64, 300, 1, False), (15, 64, 300, 3, False), (47, 64, 300, 1, False)]
+
+
+@pytest.mark.parametrize("ring,hs,T,ns,scratch", DROP_PATHS)
+def test_attention_fwd_bwd_dropout(ring, hs, T, ns, scratch):
+    """Random N(0, 1) inputs under dropout (p = 0.1) through every attention kernel family, all three gradients:
+    the read-outs of test_gpu_attn_dropout.py leave dK at zero and P uniform. The tolerances are
+    test_attention_fwd_bwd's; also lse, which dropout must not change."""
+    L = ML.lib()
+    old = L.mmt_attn_set_ring(ring)
+    try:
+        test_attention_fwd_bwd(2, T, 3, hs, ns, scratch, drop=0.1)
+    finally:
+        L.mmt_attn_set_ring(old)
 
 
 @pytest.mark.parametrize("ring", [0, 1, 3, 7, 8, 15, 47])

@@ -1539,6 +1539,9 @@ static hipError_t attn_dispatch(const AttnBatch& b, int B, int T, int H, int hs,
     if (b.p[g].drop_thr)  // dropout reads the keep bits of mmt_launch_attn_mask
       for (int j = 0; j < b.p[g].nstreams; ++j)
         if (!b.p[g].dmask[j]) return hipErrorInvalidValue;
+    // one instantiation serves the whole batch (attn_launch: DROP if any problem drops), and the DROP one
+    // reads every problem's dmask: a batch that mixes dropout on and off is refused
+    if ((b.p[g].drop_thr != 0) != (b.p[0].drop_thr != 0)) return hipErrorInvalidValue;
   }
   for (int g = 0; g < b.count; ++g) {  // O / O_j leave the forward as 16-B row pieces
     if (b.p[g].o_ld & 7 || ((uintptr_t)b.p[g].o & 15)) return hipErrorInvalidValue;

@@ -160,14 +160,45 @@ static void fill_attn(AttnProblem& p, int nstreams, const void* q, int q_ld, con
   for (int j = 0; j < nstreams; ++j) { p.k[j] = (const bf16_t*)k[j]; p.v[j] = (const bf16_t*)v[j]; }
 }
 
-int mmt_op_attention_fwd(void* stream, int32_t B, int32_t T, int32_t H, int32_t hs, int32_t nstreams, const void* q,
-                         int32_t q_ld, const void* const* k, const void* const* v, int32_t kv_ld, int32_t kv_hstride,
-                         void* o, int32_t o_ld, void* const* oj, float* const* lse) {
+// dropout of the normalised probabilities (AttnProblem::drop_*): the keep bits come from mmt_op_attention_mask
+static void fill_drop(AttnProblem& p, int nstreams, uint32_t drop_key, uint32_t drop_thr, float drop_scale,
+                      uint32_t* const* dmask) {
+  p.drop_key = drop_key; p.drop_thr = drop_thr; p.drop_scale = drop_scale;
+  for (int j = 0; j < nstreams; ++j) p.dmask[j] = (drop_thr && dmask) ? dmask[j] : nullptr;
+}
+
+int64_t mmt_op_attention_mask_dwords(int32_t B, int32_t H, int32_t T) { return mmt_attn_mask_dwords(B, H, T); }
+
+int mmt_op_attention_mask(void* stream, int32_t count, int32_t B, int32_t T, int32_t H, const int32_t* nstreams,
+                          const uint32_t* drop_key, const uint32_t* drop_thr, uint32_t* const* dmask) {
+  if (count < 1 || count > MMT_MAX_GROUP || !nstreams || !drop_key || !drop_thr || !dmask) return MMT_ERR_INVALID;
+  if (B < 0 || T < 0 || H < 0) return MMT_ERR_INVALID;
+  AttnBatch b{};
+  b.count = count;
+  for (int g = 0; g < count; ++g) {
+    if (nstreams[g] < 1 || nstreams[g] > MMT_MAX_STREAMS) return MMT_ERR_INVALID;
+    AttnProblem& p = b.p[g];
+    p.nstreams = nstreams[g];
+    p.drop_key = drop_key[g]; p.drop_thr = drop_thr[g];
+    for (int j = 0; j < nstreams[g]; ++j) {
+      p.dmask[j] = dmask[g * MMT_MAX_STREAMS + j];
+      if (drop_thr[g] && !p.dmask[j]) return MMT_ERR_INVALID;
+    }
+  }
+  return st(mmt_launch_attn_mask(b, B, T, H, (hipStream_t)stream));
+}
+
+int mmt_op_attention_fwd_drop(void* stream, int32_t B, int32_t T, int32_t H, int32_t hs, int32_t nstreams,
+                              const void* q, int32_t q_ld, const void* const* k, const void* const* v, int32_t kv_ld,
+                              int32_t kv_hstride, void* o, int32_t o_ld, void* const* oj, float* const* lse,
+                              uint32_t drop_key, uint32_t drop_thr, float drop_scale, uint32_t* const* dmask) {
   if (nstreams < 1 || nstreams > MMT_MAX_STREAMS) return MMT_ERR_INVALID;
+  if (drop_thr && !dmask) return MMT_ERR_INVALID;
   AttnBatch b{};
   b.count = 1;
   AttnProblem& p = b.p[0];
   fill_attn(p, nstreams, q, q_ld, k, v, kv_ld, kv_hstride);
+  fill_drop(p, nstreams, drop_key, drop_thr, drop_scale, dmask);
   p.o = (bf16_t*)o; p.o_ld = o_ld;
   for (int j = 0; j < nstreams; ++j) {
     p.oj[j] = oj ? (bf16_t*)oj[j] : nullptr;
@@ -178,32 +209,27 @@ int mmt_op_attention_fwd(void* stream, int32_t B, int32_t T, int32_t H, int32_t 
   return e == hipErrorInvalidValue ? MMT_ERR_UNSUPPORTED : st(e);
 }
 
-int mmt_op_attention_bwd_ws(void* stream, int32_t B, int32_t T, int32_t H, int32_t hs, int32_t nstreams,
-                            const void* q, int32_t q_ld, const void* const* k, const void* const* v, int32_t kv_ld,
-                            int32_t kv_hstride, const void* o, int32_t o_ld, const void* const* oj,
-                            const float* const* lse, const void* dout, int32_t dout_ld, float* const* dvec, void* dq,
-                            int32_t dq_ld, void* const* dk, void* const* dv, int32_t dkv_ld, int32_t dkv_hstride,
-                            float* dq32, int32_t dq32_ld);
-int mmt_op_attention_bwd(void* stream, int32_t B, int32_t T, int32_t H, int32_t hs, int32_t nstreams, const void* q,
+int mmt_op_attention_fwd(void* stream, int32_t B, int32_t T, int32_t H, int32_t hs, int32_t nstreams, const void* q,
                          int32_t q_ld, const void* const* k, const void* const* v, int32_t kv_ld, int32_t kv_hstride,
-                         const void* o, int32_t o_ld, const void* const* oj, const float* const* lse, const void* dout,
-                         int32_t dout_ld, float* const* dvec, void* dq, int32_t dq_ld, void* const* dk, void* const* dv,
-                         int32_t dkv_ld, int32_t dkv_hstride) {
-  return mmt_op_attention_bwd_ws(stream, B, T, H, hs, nstreams, q, q_ld, k, v, kv_ld, kv_hstride, o, o_ld, oj, lse, dout,
-                                 dout_ld, dvec, dq, dq_ld, dk, dv, dkv_ld, dkv_hstride, nullptr, 0);
+                         void* o, int32_t o_ld, void* const* oj, float* const* lse) {
+  return mmt_op_attention_fwd_drop(stream, B, T, H, hs, nstreams, q, q_ld, k, v, kv_ld, kv_hstride, o, o_ld, oj, lse,
+                                   0, 0, 0.f, nullptr);
 }
 
-int mmt_op_attention_bwd_ws(void* stream, int32_t B, int32_t T, int32_t H, int32_t hs, int32_t nstreams,
-                            const void* q, int32_t q_ld, const void* const* k, const void* const* v, int32_t kv_ld,
-                            int32_t kv_hstride, const void* o, int32_t o_ld, const void* const* oj,
-                            const float* const* lse, const void* dout, int32_t dout_ld, float* const* dvec, void* dq,
-                            int32_t dq_ld, void* const* dk, void* const* dv, int32_t dkv_ld, int32_t dkv_hstride,
-                            float* dq32, int32_t dq32_ld) {
+int mmt_op_attention_bwd_drop(void* stream, int32_t B, int32_t T, int32_t H, int32_t hs, int32_t nstreams,
+                              const void* q, int32_t q_ld, const void* const* k, const void* const* v, int32_t kv_ld,
+                              int32_t kv_hstride, const void* o, int32_t o_ld, const void* const* oj,
+                              const float* const* lse, const void* dout, int32_t dout_ld, float* const* dvec, void* dq,
+                              int32_t dq_ld, void* const* dk, void* const* dv, int32_t dkv_ld, int32_t dkv_hstride,
+                              float* dq32, int32_t dq32_ld, uint32_t drop_key, uint32_t drop_thr, float drop_scale,
+                              uint32_t* const* dmask) {
   if (nstreams < 1 || nstreams > MMT_MAX_STREAMS) return MMT_ERR_INVALID;
+  if (drop_thr && !dmask) return MMT_ERR_INVALID;
   AttnBatch b{};
   b.count = 1;
   AttnProblem& p = b.p[0];
   fill_attn(p, nstreams, q, q_ld, k, v, kv_ld, kv_hstride);
+  fill_drop(p, nstreams, drop_key, drop_thr, drop_scale, dmask);
   p.o = (bf16_t*)o; p.o_ld = o_ld;
   for (int j = 0; j < nstreams; ++j) {
     p.oj[j] = oj ? (bf16_t*)oj[j] : nullptr;
@@ -218,6 +244,27 @@ int mmt_op_attention_bwd_ws(void* stream, int32_t B, int32_t T, int32_t H, int32
   const float scale = 1.0f / __builtin_sqrtf((float)hs);
   const hipError_t e = mmt_launch_attn_bwd(b, B, T, H, hs, scale, (hipStream_t)stream);
   return e == hipErrorInvalidValue ? MMT_ERR_UNSUPPORTED : st(e);
+}
+
+int mmt_op_attention_bwd_ws(void* stream, int32_t B, int32_t T, int32_t H, int32_t hs, int32_t nstreams,
+                            const void* q, int32_t q_ld, const void* const* k, const void* const* v, int32_t kv_ld,
+                            int32_t kv_hstride, const void* o, int32_t o_ld, const void* const* oj,
+                            const float* const* lse, const void* dout, int32_t dout_ld, float* const* dvec, void* dq,
+                            int32_t dq_ld, void* const* dk, void* const* dv, int32_t dkv_ld, int32_t dkv_hstride,
+                            float* dq32, int32_t dq32_ld) {
+  return mmt_op_attention_bwd_drop(stream, B, T, H, hs, nstreams, q, q_ld, k, v, kv_ld, kv_hstride, o, o_ld, oj, lse,
+                                   dout, dout_ld, dvec, dq, dq_ld, dk, dv, dkv_ld, dkv_hstride, dq32, dq32_ld, 0, 0, 0.f,
+                                   nullptr);
+}
+
+int mmt_op_attention_bwd(void* stream, int32_t B, int32_t T, int32_t H, int32_t hs, int32_t nstreams, const void* q,
+                         int32_t q_ld, const void* const* k, const void* const* v, int32_t kv_ld, int32_t kv_hstride,
+                         const void* o, int32_t o_ld, const void* const* oj, const float* const* lse, const void* dout,
+                         int32_t dout_ld, float* const* dvec, void* dq, int32_t dq_ld, void* const* dk, void* const* dv,
+                         int32_t dkv_ld, int32_t dkv_hstride) {
+  return mmt_op_attention_bwd_drop(stream, B, T, H, hs, nstreams, q, q_ld, k, v, kv_ld, kv_hstride, o, o_ld, oj, lse,
+                                   dout, dout_ld, dvec, dq, dq_ld, dk, dv, dkv_ld, dkv_hstride, nullptr, 0, 0, 0, 0.f,
+                                   nullptr);
 }
 
 // KV-cache decode attention (mmt_decode.hip), the launcher mmt_decode_step calls; everything the kernel
@@ -270,23 +317,31 @@ int mmt_op_attention_decode_fanout(void* stream, int32_t B, int32_t samples, int
 }
 
 // hs-32 self-attention with Q / K / V made on chip from the stage-1 rows (AttnProblem::oc_*)
-int mmt_op_attention_fwd_h1(void* stream, int32_t B, int32_t T, int32_t H, const void* h1, int32_t ld_h1, const float* w2,
-                            void* o, int32_t o_ld, float* lse) {
-  if (!h1 || !w2 || !o || !lse) return MMT_ERR_INVALID;
+int mmt_op_attention_fwd_h1_drop(void* stream, int32_t B, int32_t T, int32_t H, const void* h1, int32_t ld_h1,
+                                 const float* w2, void* o, int32_t o_ld, float* lse, uint32_t drop_key, uint32_t drop_thr,
+                                 float drop_scale, uint32_t* dmask) {
+  if (!h1 || !w2 || !o || !lse || (drop_thr && !dmask)) return MMT_ERR_INVALID;
   AttnBatch b{};
   b.count = 1;
   AttnProblem& p = b.p[0];
   p.nstreams = 1;
   p.oc_h1 = (const bf16_t*)h1; p.oc_ld = ld_h1; p.oc_w2 = w2;
   p.o = (bf16_t*)o; p.o_ld = o_ld; p.lse[0] = lse;
+  p.drop_key = drop_key; p.drop_thr = drop_thr; p.drop_scale = drop_scale; p.dmask[0] = drop_thr ? dmask : nullptr;
   const hipError_t e = mmt_launch_attn_fwd(b, B, T, H, 32, 1.0f / __builtin_sqrtf(32.f), (hipStream_t)stream);
   return e == hipErrorInvalidValue ? MMT_ERR_UNSUPPORTED : st(e);
 }
 
-int mmt_op_attention_bwd_h1(void* stream, int32_t B, int32_t T, int32_t H, const void* h1, int32_t ld_h1, const float* w2,
-                            const void* o, int32_t o_ld, const float* lse, const void* dout, int32_t dout_ld, void* dh1,
-                            float* dw2, float* db1) {
-  if (!h1 || !w2 || !o || !lse || !dout || !dh1 || !dw2 || !db1) return MMT_ERR_INVALID;
+int mmt_op_attention_fwd_h1(void* stream, int32_t B, int32_t T, int32_t H, const void* h1, int32_t ld_h1, const float* w2,
+                            void* o, int32_t o_ld, float* lse) {
+  return mmt_op_attention_fwd_h1_drop(stream, B, T, H, h1, ld_h1, w2, o, o_ld, lse, 0, 0, 0.f, nullptr);
+}
+
+int mmt_op_attention_bwd_h1_drop(void* stream, int32_t B, int32_t T, int32_t H, const void* h1, int32_t ld_h1,
+                                 const float* w2, const void* o, int32_t o_ld, const float* lse, const void* dout,
+                                 int32_t dout_ld, void* dh1, float* dw2, float* db1, uint32_t drop_key, uint32_t drop_thr,
+                                 float drop_scale, uint32_t* dmask) {
+  if (!h1 || !w2 || !o || !lse || !dout || !dh1 || !dw2 || !db1 || (drop_thr && !dmask)) return MMT_ERR_INVALID;
   AttnBatch b{};
   b.count = 1;
   AttnProblem& p = b.p[0];
@@ -296,8 +351,16 @@ int mmt_op_attention_bwd_h1(void* stream, int32_t B, int32_t T, int32_t H, const
   p.q2_dh1 = (bf16_t*)dh1; p.q2_dw2 = dw2; p.q2_db1 = db1;
   p.o = (bf16_t*)o; p.o_ld = o_ld; p.lse[0] = (float*)lse;
   p.dout = (const bf16_t*)dout; p.dout_ld = dout_ld;
+  p.drop_key = drop_key; p.drop_thr = drop_thr; p.drop_scale = drop_scale; p.dmask[0] = drop_thr ? dmask : nullptr;
   const hipError_t e = mmt_launch_attn_bwd(b, B, T, H, 32, 1.0f / __builtin_sqrtf(32.f), (hipStream_t)stream);
   return e == hipErrorInvalidValue ? MMT_ERR_UNSUPPORTED : st(e);
+}
+
+int mmt_op_attention_bwd_h1(void* stream, int32_t B, int32_t T, int32_t H, const void* h1, int32_t ld_h1, const float* w2,
+                            const void* o, int32_t o_ld, const float* lse, const void* dout, int32_t dout_ld, void* dh1,
+                            float* dw2, float* db1) {
+  return mmt_op_attention_bwd_h1_drop(stream, B, T, H, h1, ld_h1, w2, o, o_ld, lse, dout, dout_ld, dh1, dw2, db1, 0, 0,
+                                      0.f, nullptr);
 }
 
 int mmt_op_qkv2_fwd(void* stream, int32_t R, int32_t nblk, int32_t hs, const void* h1, int32_t ld_h1, const float* w2,

@@ -198,6 +198,23 @@ _SIGS = {
                                         ctypes.POINTER(c_vp), c_i32, c_i32, c_vp, c_i32, ctypes.POINTER(c_vp),
                                         ctypes.POINTER(c_vp), c_vp, c_i32, ctypes.POINTER(c_vp), c_vp, c_i32,
                                         ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_i32, c_i32, c_vp, c_i32]),
+    "mmt_op_attention_mask_dwords": (c_i64, [c_i32, c_i32, c_i32]),
+    "mmt_op_attention_mask": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(c_i32),
+                                      ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32),
+                                      ctypes.POINTER(c_vp)]),
+    "mmt_op_attention_fwd_drop": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, ctypes.POINTER(c_vp),
+                                          ctypes.POINTER(c_vp), c_i32, c_i32, c_vp, c_i32, ctypes.POINTER(c_vp),
+                                          ctypes.POINTER(c_vp), ctypes.c_uint32, ctypes.c_uint32, c_f32,
+                                          ctypes.POINTER(c_vp)]),
+    "mmt_op_attention_bwd_drop": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, ctypes.POINTER(c_vp),
+                                          ctypes.POINTER(c_vp), c_i32, c_i32, c_vp, c_i32, ctypes.POINTER(c_vp),
+                                          ctypes.POINTER(c_vp), c_vp, c_i32, ctypes.POINTER(c_vp), c_vp, c_i32,
+                                          ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_i32, c_i32, c_vp, c_i32,
+                                          ctypes.c_uint32, ctypes.c_uint32, c_f32, ctypes.POINTER(c_vp)]),
+    "mmt_op_attention_fwd_h1_drop": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp,
+                                             ctypes.c_uint32, ctypes.c_uint32, c_f32, c_vp]),
+    "mmt_op_attention_bwd_h1_drop": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp,
+                                             c_i32, c_vp, c_vp, c_vp, ctypes.c_uint32, ctypes.c_uint32, c_f32, c_vp]),
     "mmt_op_attention_decode": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32,
                                         ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_i32, c_i32, c_vp, c_i32]),
     "mmt_op_attention_decode_fanout": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp,
