@@ -258,6 +258,85 @@ int mmt_resample(void* stream, int32_t batch, int32_t samples, int32_t count, co
 int mmt_fanout_gather(mmt_ctx* ctx, void* stream, int32_t batch, int32_t samples, int32_t n0, int32_t max_new,
                       int32_t npos, const int32_t* ancestors, const void* src_fan, void* dst_fan);
 
+/* Forecast distributions of rollouts. A rollout returns paths; a forecast needs, per future step, the distribution
+ * of the next token given the prompt: the average, over a prompt's paths, of the law each path draws its token
+ * from, the paths weighted by their evidence. mmt_forecast_multi computes that mixture for one generated step,
+ * mmt_pmf_stats reduces stored mixtures to summaries. Both need no context.
+ *
+ * mmt_forecast_multi: `count` problems (the heads of the step) over `batch` prompts of `samples` rows each, row
+ * r = b * samples + s. V, logits, row_stride, temperature, top_k, top_p are HOST arrays of `count` entries with
+ * mmt_sample_multi's meaning. Per problem the fp32 output row of prompt b is pmf[p] + b * pmf_stride[p]
+ * (pmf_stride >= V: column j of a [B, N, V] tensor is written in place, stride N * V), and, where given,
+ * ess[p][b] (fp64) and live[p][b] (int32); the arrays ess / live and their entries may be NULL. Weights in
+ * mmt_resample's form: `wcount` <= 8 log-probability matrices (HOST arrays logprob / lp_stride), the column range
+ * [j0, j1), logw fp64 [batch * samples] (nullable); logw_out (nullable, fp64 [batch * samples], not overlapping logw)
+ * receives rule 2's a_s, so a loop that hands them back as the next step's logw folds one column per step and forms,
+ * bit for bit, the serial sum over all of them. scratch: mmt_forecast_scratch_bytes(count, batch, samples)
+ * bytes of device memory, 16-byte aligned, its contents unspecified before and after.
+ * The rule, per problem p and prompt b:
+ *   1. row law. For every row r, steps 1 - 4 of mmt_sample's rule with problem p's settings, by the sampler's own
+ *      device code: z, m, the threshold key K of top-k then top-p, e_i = exp(z_i - m) (fp32, 1 at the maximum) on the
+ *      kept set and 0 elsewhere, S_r their fp64 sum over the sampler's tree. The law is P_r(i) = e_i / S_r.
+ *      temperature == 0: the point mass on the lowest index among the maxima of the raw logits (S_r = 1). A row with
+ *      no finite logit has no law and is dead in this problem.
+ *   2. path weight, mmt_resample's rules 1 - 2: a_s = logw[r] + the columns j0..j1-1 of the matrices (serial fp64 sum,
+ *      NaN as -inf); mx = max over the rows that are not dead; d_s = (float)(a_s - mx); w_s = 1 where d_s == 0, else
+ *      expf(d_s); w_s = 0 for dead rows and for a_s = -inf. W = sum w_s and Q = sum w_s^2 in fp64 over
+ *      mmt_resample's tree; ess = W^2 / Q; live = #{ w_s > 0 }. Without weights (wcount == 0 and logw == NULL)
+ *      w_s = 1 on every row that is not dead, W = Q = ess = live.
+ *   3. mixture. c_s = (double) w_s / S_r; q(i) = (sum over s of e_i c_s) / W: fp64, one fused multiply-add per row,
+ *      the rows of a prompt in sixteen consecutive blocks of ceil(samples / 16), each summed in row order, the sixteen
+ *      partial sums added left to right; q is rounded to fp32 once. live == 0 gives an all-zero row and ess 0.
+ * No float atomics: a launch is bit-identical run to run, a prompt launched alone (same samples) gives the bits it
+ * gives in company, and so does a problem. Nothing outside the V columns of a pmf row is written.
+ * Launches: one over (rows, problems) for the row laws (a second one for problems with V > 8192, the sampler's
+ * re-read variant), with weights one over (prompts, problems), one over (prompts x 64-column chunks, problems);
+ * more than 8 problems go in chunks of 8. With weights samples <= 4096 (the weights of a prompt stay in LDS);
+ * without, any.
+ * MMT_ERR_INVALID before any launch, nothing written: count < 0, batch < 0, samples < 1, batch * samples >= 2^31,
+ * wcount outside 0..8, j0 < 0, j1 < j0; with count > 0 a null V / logits / row_stride / temperature / top_k /
+ * top_p / pmf / pmf_stride array; per problem mmt_sample's refusals, pmf_stride < V, a null logits / pmf with
+ * batch > 0; with wcount > 0 and j1 > j0 a null logprob / lp_stride or entry, lp_stride < j1; with batch > 0 a
+ * null, misaligned or undersized scratch; logw_out without weights or equal to logw.
+ * MMT_ERR_UNSUPPORTED: V > 2^20; with weights samples > 4096 or
+ * count > 65535. count == 0 or batch == 0 launches nothing. mmt_forecast_scratch_bytes returns -1 for arguments
+ * the entry refuses. */
+int64_t mmt_forecast_scratch_bytes(int32_t count, int32_t batch, int32_t samples);
+int mmt_forecast_multi(void* stream, int32_t count, int32_t batch, int32_t samples, const int32_t* V,
+                       const float* const* logits, const int64_t* row_stride, const float* temperature,
+                       const int32_t* top_k, const float* top_p, float* const* pmf, const int64_t* pmf_stride,
+                       int32_t wcount, const float* const* logprob, const int64_t* lp_stride, int32_t j0, int32_t j1,
+                       const double* logw /* nullable */, double* logw_out /* nullable */,
+                       double* const* ess /* nullable, entries nullable */,
+                       int32_t* const* live /* nullable, entries nullable */, void* scratch, int64_t scratch_bytes);
+
+/* mmt_pmf_stats: summaries of stored pmf rows, `count` problems over the same `rows`, grid (rows, problems). Per
+ * problem (HOST arrays): V, the fp32 pmf (row r at pmf[p] + r * pmf_stride[p]), values (device fp64 [V],
+ * non-decreasing in token order; the array and its entries nullable), is_percent (nullable: all 0), origin (device
+ * int64, row r's at origin[p][r * origin_stride[p]]; nullable), stats (device fp64 [rows, 8]), qtok (device int32
+ * [rows, nq]). levels: `nq` <= 16 HOST fp64 values in (0, 1).
+ * Everything is a function of the fp32 row as stored, in fp64; an entry that is not > 0 holds no mass. Sums run in
+ * vocabulary order over the sampler's tree (thread t of 256 owns the c = ceil(V / 256) | 1 elements from t c).
+ *   stats[0] T = sum q          stats[1] entropy -sum (q/T) ln (q/T), nats
+ *   stats[2] mean sum (q/T) v   stats[3] variance sum (q/T) (v - mean)^2
+ *   stats[4..6] p_down, p_flat, p_up: the mass / T of the tokens whose direction sign is -1 / 0 / +1, the sign of
+ *               v_i for a percent series (origin is not read) and of v_i - v[origin] for a value series (the
+ *               reference's _get_direction_sign against the origin token)
+ *   stats[7] the largest q / T
+ *   qtok[k] the first token with mass whose inclusive prefix sum reaches levels[k] * T (should rounding leave
+ *           none, the last token with mass)
+ * Without values stats[2..6] are NaN (the quantiles are those of the token index); an origin outside 0..V-1, or
+ * none for a value series, gives NaN in stats[4..6] and nothing is read out of range. A row with T == 0 gives
+ * stats[0] = 0, NaN in stats[1..7] and qtok -1.
+ * MMT_ERR_INVALID before any launch: count < 0, rows < 0, nq outside 0..16, a level outside (0, 1) or NaN, a null
+ * V / pmf / pmf_stride / stats array, qtok null with nq > 0, origin without origin_stride, V < 1, pmf_stride < V,
+ * a null pmf / stats / qtok entry with rows > 0; MMT_ERR_UNSUPPORTED for V > 2^20. */
+int mmt_pmf_stats(void* stream, int32_t count, int32_t rows, const int32_t* V, const float* const* pmf,
+                  const int64_t* pmf_stride, const double* const* values /* nullable, entries nullable */,
+                  const int32_t* is_percent /* nullable */, const int64_t* const* origin /* nullable */,
+                  const int64_t* origin_stride, int32_t nq, const double* levels, double* const* stats,
+                  int32_t* const* qtok);
+
 /* failure detection (the reference's guard is the NaN check on eval losses,
  * main.py:606): byte offset in the workspace of two int32 bitmasks (the same for every batch size;
  * the query never touches the workspace plan of a pending backward or decode). The

@@ -28,6 +28,14 @@ Evidence of a given series (modalities 0..2 sampled, modality 3 given): --paths 
 --samples; with --samples, --paths fanout_given,fanout_weights,fanout_resample1,fanout_resample8,fanout_resample32
 (evidence="resample" with ess_threshold 0.5 at resample_every 1 / 8 / 32). --gather adds mmt_fanout_gather alone
 after half the new tokens: its bytes (read plus written) and us per call.
+
+Forecast distributions (--forecast): without --samples the paths joint,joint_forecast,joint_hook and
+joint_weights,joint_weights_forecast; with --samples fanout_joint,fanout_joint_forecast,fanout_joint_hook and
+fanout_weights,fanout_weights_forecast. `_forecast` is the same call with forecast=True; `_hook` is what a caller can
+write without it: a logits_hook that computes the unfiltered, unweighted mixture per step with torch (softmax, mean over
+a prompt's paths, a copy into a [B, N, V] tensor). --forecast also adds the two entries alone: us per
+mmt_forecast_multi call over the four heads at 64 rows (64 prompts of one path), 512 and 4096 rows (one prompt),
+without and with weights, and us per mmt_pmf_stats launch over the four heads at 64 / 512 / 4096 pmf rows.
 """
 import argparse
 import json
@@ -56,7 +64,12 @@ def main():
     ap.add_argument("--samples", type=int, default=0, help="continuations per prompt (0: the single-path benchmark)")
     ap.add_argument("--attn", action="store_true", help="with --samples: the two decode attention kernels alone")
     ap.add_argument("--gather", action="store_true", help="with --samples: mmt_fanout_gather alone (this tree only)")
+    ap.add_argument("--forecast", action="store_true",
+                    help="the forecast paths by default, and the two forecast entries alone (this tree only)")
     a = ap.parse_args()
+    if a.forecast and a.paths == "default,device":
+        a.paths = ("fanout_joint,fanout_joint_forecast,fanout_joint_hook,fanout_weights,fanout_weights_forecast"
+                   if a.samples else "joint,joint_forecast,joint_hook,joint_weights,joint_weights_forecast")
     if a.samples and a.paths == "default,device":
         a.paths = "fanout,tiled"
     sys.path.insert(0, os.path.join(os.path.abspath(a.tree), "trade-aid-multimodal-transformer_amd"))
@@ -93,6 +106,10 @@ def main():
     gkw = dict(max_new_tokens=a.new, modality_to_generate=[0, 1, 2], given=scen, temperature=1.0, seed=11)
     calls["joint_given"] = lambda: model.generate(prompt, **gkw)
     calls["joint_weights"] = lambda: model.generate(prompt, evidence="weights", **gkw)[0]
+    jkw = dict(max_new_tokens=a.new, modality_to_generate="all", temperature=1.0, seed=11)
+    calls["joint_forecast"] = lambda: model.generate(prompt, forecast=True, **jkw)[0]
+    calls["joint_hook"] = lambda: model.generate(prompt, logits_hook=mixture_hook(torch, dev, a, 1), **jkw)
+    calls["joint_weights_forecast"] = lambda: model.generate(prompt, evidence="weights", forecast=True, **gkw)[0]
     paths = [p for p in a.paths.split(",") if p]
     if a.samples:
         return fanout_bench(a, torch, dev, model, prompt, paths)
@@ -117,7 +134,89 @@ def main():
         res["sampler_us"] = sampler_alone(torch, dev, a.batch, a.rounds)
     if a.sampler_multi:
         res["sampler_multi_us"] = sampler_multi_alone(torch, dev, a.rounds)
+    if a.forecast:
+        res["forecast_us"] = forecast_alone(torch, dev, a.rounds)
     print(json.dumps(res), flush=True)
+
+
+def mixture_hook(torch, dev, a, S):
+    """The logits_hook a caller can write without forecast=: per step and head the softmax of the [B * S, V] logits,
+    averaged over each prompt's S paths, copied into column j of a [B, N, V] tensor (no top-k / top-p law, no evidence
+    weights: those are not available to a hook)."""
+    store = {}
+
+    def hook(n, views):
+        j = n - a.prompt
+        for i, v in enumerate(views):
+            if i not in store:
+                store[i] = torch.zeros(a.batch, a.new, v.shape[1], dtype=torch.float32, device=dev)
+            p = torch.softmax(v, dim=-1)
+            store[i][:, j] = p.view(a.batch, S, -1).mean(1) if S > 1 else p
+
+    return hook
+
+
+def forecast_alone(torch, dev, rounds, reps=100):
+    """us per mmt_forecast_multi call (its two launches, three with weights) over the four C1 heads at 64 rows (64
+    prompts of one path), 512 and 4096 rows (one prompt of as many paths), without weights and with 32 columns of one
+    log-probability matrix plus logw; and us per mmt_pmf_stats launch over the four heads at as many pmf rows. HIP
+    events around `reps` back-to-back calls over rotating N(0, 3^2) logits, best of `rounds`."""
+    import mmt_lib as ML
+    import mmt_sample as MS
+    L, st = ML.lib(), ML.stream_ptr(dev)
+    Vs = C1["V"]
+    out = {}
+
+    def timed(fn):
+        best = None
+        for _ in range(rounds):
+            for k in range(8):
+                fn(k)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            for k in range(reps):
+                fn(k)
+            e1.record()
+            torch.cuda.synchronize()
+            us = e0.elapsed_time(e1) / reps * 1e3
+            best = us if best is None else min(best, us)
+        return round(best, 2)
+
+    for rows in (64, 512, 4096):
+        B, S = (64, 1) if rows == 64 else (1, rows)
+        bufs = [[torch.randn(rows, V, device=dev) * 3.0 for V in Vs] for _ in range(8)]
+        pmf = [torch.zeros(B, V, device=dev) for V in Vs]
+        ess = [torch.zeros(B, dtype=torch.float64, device=dev) for _ in Vs]
+        live = [torch.zeros(B, dtype=torch.int32, device=dev) for _ in Vs]
+        glp = -torch.rand(rows, 32, device=dev)
+        logw = torch.zeros(rows, dtype=torch.float64, device=dev)
+        for name, weighted in (("plain", False), ("weights", True)):
+            fl = MS.ForecastLaunch(Vs, [(1.0, 0, 1.0)] * 4, Vs, [glp.data_ptr()] if weighted else [],
+                                   [32] if weighted else [])
+            for i in range(4):
+                fl.pmf[i], fl.ess[i], fl.live[i] = pmf[i].data_ptr(), ess[i].data_ptr(), live[i].data_ptr()
+            nbytes = fl.scratch_bytes(L, B, S)
+            scratch = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+
+            def one(k):
+                for i in range(4):
+                    fl.logits[i] = bufs[k % 8][i].data_ptr()
+                fl.run(L, st, B, S, 0, 32 if weighted else 0, logw.data_ptr() if weighted else 0, scratch.data_ptr(),
+                       nbytes)
+
+            out[f"forecast_rows{rows}_{name}"] = timed(one)
+        rowsets = [torch.softmax(torch.randn(rows, V, device=dev) * 3.0, dim=-1) for V in Vs]
+        sl = MS.StatsLaunch(Vs, Vs, [False] * 4, (0.05, 0.5, 0.95))
+        vals = [torch.linspace(-1.0, 1.0, V, dtype=torch.float64, device=dev) for V in Vs]
+        org = torch.zeros(rows, dtype=torch.int64, device=dev)
+        stats = [torch.zeros(rows, 8, dtype=torch.float64, device=dev) for _ in Vs]
+        qtok = [torch.zeros(rows, 3, dtype=torch.int32, device=dev) for _ in Vs]
+        for i in range(4):
+            sl.pmf[i], sl.values[i], sl.origin[i] = rowsets[i].data_ptr(), vals[i].data_ptr(), org.data_ptr()
+            sl.stats[i], sl.qtok[i] = stats[i].data_ptr(), qtok[i].data_ptr()
+        out[f"pmf_stats_rows{rows}"] = timed(lambda k: sl.run(L, st, rows))
+    return out
 
 
 def fanout_bench(a, torch, dev, model, prompt, paths):
@@ -136,6 +235,10 @@ def fanout_bench(a, torch, dev, model, prompt, paths):
     for every in (1, 8, 32):
         calls[f"fanout_resample{every}"] = lambda every=every: model.generate(
             prompt, evidence="resample", resample_every=every, ess_threshold=0.5, **gkw)[0]
+    jkw = dict(kw, modality_to_generate="all", num_samples=S)
+    calls["fanout_joint_forecast"] = lambda: model.generate(prompt, forecast=True, **jkw)[0]
+    calls["fanout_joint_hook"] = lambda: model.generate(prompt, logits_hook=mixture_hook(torch, dev, a, S), **jkw)
+    calls["fanout_weights_forecast"] = lambda: model.generate(prompt, evidence="weights", forecast=True, **gkw)[0]
     rec = {p: {"paths_per_s": [], "tokens_per_s": [], "peak_bytes": []} for p in paths}
 
     def one(p, timed):
@@ -167,6 +270,8 @@ def fanout_bench(a, torch, dev, model, prompt, paths):
         res["attn_us"] = attention_alone(torch, dev, B, S, a.prompt, a.prompt + a.new, a.rounds)
     if a.gather:
         res["gather"] = gather_alone(torch, dev, model, prompt, B, S, a.prompt, a.new, a.rounds)
+    if a.forecast:
+        res["forecast_us"] = forecast_alone(torch, dev, a.rounds)
     print(json.dumps(res), flush=True)
 
 

@@ -341,6 +341,42 @@ struct GatherSeg { const char* src; char* dst; int64_t row_bytes, bytes; };
 struct GatherBatch { GatherSeg seg[MMT_GATHER_SEGS]; int count; };
 hipError_t mmt_launch_row_gather(const GatherBatch& b, const int32_t* anc, int rows, hipStream_t s);
 
+// Forecast distributions (mmt_forecast_multi / mmt_pmf_stats, mmt_forecast.hip). Row r = b * samples + s. The
+// launchers validate nothing: the C entries do. `index` is the problem's place in the scratch, which holds per
+// (problem, row) the row law and the path weight and per (problem, prompt) W, ESS and the live count.
+struct ForecastRowInfo { double S; float m; uint32_t K; };        // S == 0: a dead row; greedy: K is the token
+struct ForecastPromptInfo { double W, ess; int32_t live, pad; };
+struct ForecastProblem {
+  const float* logits; int64_t row_stride;
+  float* pmf; int64_t pmf_stride;
+  double* ess; int32_t* live;                                     // nullable
+  float inv_t, top_p;
+  int V, greedy, top_k, index;
+};
+struct ForecastBatch { ForecastProblem p[MMT_MAX_GROUP]; };
+struct ForecastWeights { const float* lp[MMT_MAX_GROUP]; int64_t stride[MMT_MAX_GROUP]; int count; };
+// the row laws of n problems of one kind (onchip: every V <= 8192), grid (rows, n)
+hipError_t mmt_launch_forecast_law(const ForecastBatch& b, int n, bool onchip, int64_t rows, ForecastRowInfo* info,
+                                   hipStream_t s);
+// the path weights of every (prompt, problem), grid (batch, count); samples <= 4096
+hipError_t mmt_launch_forecast_weights(const ForecastWeights& w, int count, int batch, int samples, int j0, int j1,
+                                       const double* logw, double* logw_out, const ForecastRowInfo* info,
+                                       float* omega, ForecastPromptInfo* pinfo, hipStream_t s);
+// the mixtures of n problems, grid (batch * column chunks, n)
+hipError_t mmt_launch_forecast_mix(const ForecastBatch& b, int n, bool weighted, int batch, int samples,
+                                   const ForecastRowInfo* info, const float* omega, const ForecastPromptInfo* pinfo,
+                                   hipStream_t s);
+#define MMT_PMF_MAX_Q 16
+struct PmfStatsProblem {
+  const float* pmf; int64_t stride;
+  const double* values;                                           // nullable
+  const int64_t* origin; int64_t origin_stride;                   // nullable
+  double* stats; int32_t* qtok;
+  int V, is_percent;
+};
+struct PmfStatsBatch { PmfStatsProblem p[MMT_MAX_GROUP]; double level[MMT_PMF_MAX_Q]; int nq; };
+hipError_t mmt_launch_pmf_stats(const PmfStatsBatch& b, int n, int rows, hipStream_t s);
+
 // ------------------------------------------------------------------------------------------
 // Per-head Q/K/V stage 2: block-diagonal [hs/2 -> hs] maps (model.py:39,44,49), nblk = 3*H.
 //   out[r, blk*hs + o] = sum_i W2[blk][o][i] * h1[r, blk*hs/2 + i]

@@ -122,6 +122,16 @@ _SIGS = {
                                 ctypes.POINTER(c_vp), ctypes.POINTER(c_i64)]),
     "mmt_resample": (c_i32, [c_vp, c_i32, c_i32, c_i32, ctypes.POINTER(c_vp), ctypes.POINTER(c_i64), c_i32, c_i32,
                              c_vp, c_vp, ctypes.c_double, ctypes.c_uint64, ctypes.c_uint32, c_vp, c_vp]),
+    "mmt_forecast_scratch_bytes": (c_i64, [c_i32, c_i32, c_i32]),
+    "mmt_forecast_multi": (c_i32, [c_vp, c_i32, c_i32, c_i32, ctypes.POINTER(c_i32), ctypes.POINTER(c_vp),
+                                   ctypes.POINTER(c_i64), ctypes.POINTER(c_f32), ctypes.POINTER(c_i32),
+                                   ctypes.POINTER(c_f32), ctypes.POINTER(c_vp), ctypes.POINTER(c_i64), c_i32,
+                                   ctypes.POINTER(c_vp), ctypes.POINTER(c_i64), c_i32, c_i32, c_vp, c_vp,
+                                   ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp, c_i64]),
+    "mmt_pmf_stats": (c_i32, [c_vp, c_i32, c_i32, ctypes.POINTER(c_i32), ctypes.POINTER(c_vp), ctypes.POINTER(c_i64),
+                              ctypes.POINTER(c_vp), ctypes.POINTER(c_i32), ctypes.POINTER(c_vp),
+                              ctypes.POINTER(c_i64), c_i32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(c_vp),
+                              ctypes.POINTER(c_vp)]),
     "mmt_fanout_gather": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "mmt_backward_stage_count": (c_i32, [c_vp]),
     "mmt_backward_stage_range": (c_i32, [c_vp, c_i32, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),

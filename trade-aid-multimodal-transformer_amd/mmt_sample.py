@@ -18,6 +18,12 @@ particle-filter step over the S paths of each prompt (mmt_resample):
     lps = mmt_sample.score_multi([logits_1], [tokens_1])
     ancestors, resampled = mmt_sample.resample(lps_list, logw, log_evidence, samples=S, ess_threshold=0.5,
                                                seed=1234, pos=n)
+
+Forecast distributions (generate's forecast=): per prompt the mixture of the laws its paths draw their next token from,
+weighted as mmt_resample weighs them (mmt_forecast_multi), and the summaries of stored pmf rows (mmt_pmf_stats):
+
+    pmfs, ess, live = mmt_sample.forecast_multi([logits_0], samples=S, temperature=0.8, top_k=50, logprobs=lps_list)
+    stats, qtok = mmt_sample.pmf_stats(pmfs, values=[vocab_values_0], is_percent=True, quantiles=(0.05, 0.5, 0.95))
 """
 import ctypes
 
@@ -231,6 +237,215 @@ def score_multi(logits_list, tokens_list):
     with torch.cuda.device(dev):
         sl.run(ML.lib(), ML.stream_ptr(dev), B)
     return lps
+
+
+class ForecastLaunch:
+    """The host arrays of one mmt_forecast_multi call over P problems (include/mmt.h), made once and updated in place
+    between launches, as MultiLaunch: a decode loop changes `logits[p]` / `row_stride[p]` / `pmf[p]` / `ess[p]` /
+    `live[p]` (raw addresses; ess / live 0 = absent) and calls `run`. settings: P triples from check_settings;
+    lp_ptrs / lp_strides: the G <= 8 log-probability matrices of the weights (none: unweighted unless `run` gets a
+    logw)."""
+
+    def __init__(self, V, settings, pmf_stride, lp_ptrs=(), lp_strides=()):
+        P = self.P = len(V)
+        G = self.G = len(lp_ptrs)
+        if G > 8:
+            raise ValueError("forecast: at most 8 log-probability matrices")
+        if len(lp_strides) != G or len(settings) != P or len(pmf_stride) != P:
+            raise ValueError("forecast: one setting and pmf stride per problem, one stride per log-probability matrix")
+        n, g = max(1, P), max(1, G)
+        self.V = (ctypes.c_int32 * n)(*[int(v) for v in V])
+        self.temperature = (ctypes.c_float * n)(*[s[0] for s in settings])
+        self.top_k = (ctypes.c_int32 * n)(*[s[1] for s in settings])
+        self.top_p = (ctypes.c_float * n)(*[s[2] for s in settings])
+        self.logits = (ctypes.c_void_p * n)()
+        self.row_stride = (ctypes.c_int64 * n)(*[int(v) for v in V])
+        self.pmf = (ctypes.c_void_p * n)()
+        self.pmf_stride = (ctypes.c_int64 * n)(*[int(x) for x in pmf_stride])
+        self.ess = (ctypes.c_void_p * n)()
+        self.live = (ctypes.c_void_p * n)()
+        self.lp = (ctypes.c_void_p * g)(*[int(x) for x in lp_ptrs])
+        self.lp_stride = (ctypes.c_int64 * g)(*[int(x) for x in lp_strides])
+
+    def scratch_bytes(self, L, batch, samples):
+        """mmt_forecast_scratch_bytes for this launch's problems; ValueError for a shape the entry refuses."""
+        n = L.mmt_forecast_scratch_bytes(self.P, int(batch), int(samples))
+        if n < 0:
+            raise ValueError(f"forecast: {batch} prompts x {samples} samples are more rows than a launch addresses")
+        return int(n)
+
+    def run(self, L, stream, batch, samples, j0, j1, logw_ptr, scratch_ptr, scratch_bytes, logw_out_ptr=0):
+        """One mmt_forecast_multi (logw_ptr / logw_out_ptr: raw addresses, 0 = absent). Raises MmtError on a non-zero
+        status."""
+        rc = L.mmt_forecast_multi(stream, self.P, batch, samples, self.V, self.logits, self.row_stride,
+                                  self.temperature, self.top_k, self.top_p, self.pmf, self.pmf_stride, self.G, self.lp,
+                                  self.lp_stride, j0, j1, logw_ptr or None, logw_out_ptr or None, self.ess, self.live,
+                                  scratch_ptr, scratch_bytes)
+        if rc != 0:
+            raise ML.MmtError(f"mmt_forecast_multi failed (status {rc})")
+
+
+def forecast_multi(logits_list, *, samples, temperature=1.0, top_k=0, top_p=1.0, logprobs=None, logw=None, j0=0,
+                   j1=None):
+    """The forecast distribution of one step (mmt_forecast_multi, include/mmt.h): logits_list holds P fp32
+    [B * samples, V_p] tensors on one GPU (rows may be strided, as for `sample`), row b * samples + s being path s of
+    prompt b; temperature / top_k / top_p are scalars or sequences of P, the settings the sampler draws with. Returns
+    (pmfs, ess, live): lists of P fp32 [B, V_p], fp64 [B] and int32 [B]. pmfs[p][b] is the mixture of the laws the
+    prompt's rows draw their token from; with logprobs (up to 8 fp32 [B * samples, N], columns [j0, j1), default all)
+    and / or logw (fp64 [B * samples]) the rows are weighted as mmt_resample weighs them (samples <= 4096). No sync."""
+    P = len(logits_list)
+    ts, ks, ps = (_per_problem(temperature, P, "temperature"), _per_problem(top_k, P, "top_k"),
+                  _per_problem(top_p, P, "top_p"))
+    settings = [check_settings(t, k, p) for t, k, p in zip(ts, ks, ps)]
+    S = int(samples)
+    if S < 1:
+        raise ValueError(f"forecast_multi: samples must be >= 1, got {samples!r}")
+    if P == 0:
+        return [], [], []
+    R, dev = logits_list[0].shape[0], logits_list[0].device
+    if R % S:
+        raise ValueError(f"forecast_multi: {R} rows are no multiple of samples={samples}")
+    B = R // S
+    for lg in logits_list:
+        if lg.dim() != 2 or lg.dtype != torch.float32 or lg.device.type != "cuda" or lg.device != dev:
+            raise ValueError("forecast_multi: every logits must be an fp32 [rows, V] tensor on the same GPU")
+        if lg.shape[0] != R:
+            raise ValueError("forecast_multi: the problems must share the number of rows")
+        V = lg.shape[1]
+        if V < 1 or (V > 1 and lg.stride(1) != 1) or (R > 1 and lg.stride(0) < V):
+            raise ValueError("forecast_multi: the elements of a row must be contiguous and rows must not overlap")
+    logprobs = [] if logprobs is None else list(logprobs)
+    N = None
+    for lp in logprobs:
+        if lp.dtype != torch.float32 or lp.dim() != 2 or lp.shape[0] != R or lp.device != dev or (
+                lp.shape[1] > 1 and lp.stride(1) != 1):
+            raise ValueError(f"forecast_multi: every logprobs must be an fp32 [{R}, N] tensor on the GPU, rows "
+                             "contiguous")
+        if N is not None and lp.shape[1] != N:
+            raise ValueError("forecast_multi: the logprobs must share N")
+        N = lp.shape[1]
+    N = 0 if N is None else N
+    j1 = N if j1 is None else int(j1)
+    if not 0 <= int(j0) <= j1 <= N:
+        raise ValueError(f"forecast_multi: columns [{j0}, {j1}) outside 0..{N}")
+    if logw is not None and (logw.dtype != torch.float64 or logw.shape != (R,) or not logw.is_contiguous()
+                             or logw.device != dev):
+        raise ValueError(f"forecast_multi: logw must be a contiguous fp64 [{R}] tensor on the GPU")
+    if (logprobs or logw is not None) and S > RESAMPLE_MAX_SAMPLES:
+        raise ValueError(f"forecast_multi: weights are folded over at most {RESAMPLE_MAX_SAMPLES} samples, got {S}")
+    pmfs = [torch.empty(B, lg.shape[1], dtype=torch.float32, device=dev) for lg in logits_list]
+    ess = [torch.empty(B, dtype=torch.float64, device=dev) for _ in range(P)]
+    live = [torch.empty(B, dtype=torch.int32, device=dev) for _ in range(P)]
+    fl = ForecastLaunch([lg.shape[1] for lg in logits_list], settings, [lg.shape[1] for lg in logits_list],
+                        [lp.data_ptr() for lp in logprobs], [max(int(lp.stride(0)), N) for lp in logprobs])
+    for p, lg in enumerate(logits_list):
+        fl.logits[p] = lg.data_ptr()
+        fl.row_stride[p] = max(int(lg.stride(0)), lg.shape[1]) if R > 1 else lg.shape[1]
+        fl.pmf[p], fl.ess[p], fl.live[p] = pmfs[p].data_ptr(), ess[p].data_ptr(), live[p].data_ptr()
+    L = ML.lib()
+    nbytes = fl.scratch_bytes(L, B, S)
+    scratch = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        fl.run(L, ML.stream_ptr(dev), B, S, int(j0), j1, logw.data_ptr() if logw is not None else 0,
+               scratch.data_ptr(), nbytes)
+    return pmfs, ess, live
+
+
+STATS_FIELDS = ("total", "entropy", "mean", "var", "p_down", "p_flat", "p_up", "p_max")  # stats[..., k] of mmt_pmf_stats
+PMF_MAX_QUANTILES = 16
+
+
+def check_quantiles(quantiles):
+    """The quantile levels as mmt_pmf_stats takes them: at most 16 floats in (0, 1); ValueError otherwise."""
+    try:
+        q = [float(x) for x in quantiles]
+    except (TypeError, ValueError):
+        raise ValueError(f"forecast: quantiles must be a sequence of numbers in (0, 1), got {quantiles!r}") from None
+    if len(q) > PMF_MAX_QUANTILES:
+        raise ValueError(f"forecast: at most {PMF_MAX_QUANTILES} quantile levels, got {len(q)}")
+    for x in q:
+        if not 0.0 < x < 1.0:
+            raise ValueError(f"forecast: a quantile level must lie in (0, 1), got {x!r}")
+    return q
+
+
+def check_values(values, V, name="values"):
+    """A vocabulary's values as mmt_pmf_stats takes them: V numbers, none NaN, non-decreasing in token order (the
+    reference's vocabulary is sorted(set(...))). Returns a CPU fp64 tensor; checked once on the host. ValueError
+    otherwise."""
+    v = torch.as_tensor(values, dtype=torch.float64).detach().cpu().reshape(-1)
+    if v.shape[0] != V:
+        raise ValueError(f"forecast: {name} must hold {V} numbers, got {v.shape[0]}")
+    if bool(torch.isnan(v).any()) or (V > 1 and bool((v[1:] < v[:-1]).any())):
+        raise ValueError(f"forecast: {name} must be non-decreasing in token order, without NaN")
+    return v
+
+
+class StatsLaunch:
+    """The host arrays of one mmt_pmf_stats call over P problems (raw addresses; values / origin 0 = absent)."""
+
+    def __init__(self, V, pmf_stride, is_percent, quantiles):
+        P = self.P = len(V)
+        n = max(1, P)
+        q = check_quantiles(quantiles)
+        self.nq = len(q)
+        self.V = (ctypes.c_int32 * n)(*[int(v) for v in V])
+        self.pmf = (ctypes.c_void_p * n)()
+        self.pmf_stride = (ctypes.c_int64 * n)(*[int(x) for x in pmf_stride])
+        self.values = (ctypes.c_void_p * n)()
+        self.is_percent = (ctypes.c_int32 * n)(*[1 if x else 0 for x in is_percent])
+        self.origin = (ctypes.c_void_p * n)()
+        self.origin_stride = (ctypes.c_int64 * n)(*([1] * P))
+        self.levels = (ctypes.c_double * max(1, self.nq))(*q)
+        self.stats = (ctypes.c_void_p * n)()
+        self.qtok = (ctypes.c_void_p * n)()
+
+    def run(self, L, stream, rows):
+        rc = L.mmt_pmf_stats(stream, self.P, rows, self.V, self.pmf, self.pmf_stride, self.values, self.is_percent,
+                             self.origin, self.origin_stride, self.nq, self.levels, self.stats, self.qtok)
+        if rc != 0:
+            raise ML.MmtError(f"mmt_pmf_stats failed (status {rc})")
+
+
+def pmf_stats(pmf_list, *, values=None, is_percent=False, origin=None, quantiles=(0.05, 0.5, 0.95)):
+    """Summaries of pmf rows (mmt_pmf_stats, include/mmt.h): pmf_list holds P fp32 [..., V_p] tensors on one GPU with
+    the same leading shape (contiguous; e.g. generate's [B, N, V]). values: None or a list of P entries, each None or
+    V_p non-decreasing numbers (checked on the host); is_percent: a bool or P bools; origin: None or a list of P
+    entries, each None or an int64 tensor of the leading shape (the token a value series' direction is measured
+    from). Returns (stats, qtok): lists of P fp64 [..., 8] (STATS_FIELDS) and int32 [..., Q]."""
+    P = len(pmf_list)
+    q = check_quantiles(quantiles)
+    if P == 0:
+        return [], []
+    dev, lead = pmf_list[0].device, tuple(pmf_list[0].shape[:-1])
+    vals = _per_problem(values, P, "values") if isinstance(values, (list, tuple)) else [values] * P
+    pct = _per_problem(is_percent, P, "is_percent")
+    org = _per_problem(origin, P, "origin") if isinstance(origin, (list, tuple)) else [origin] * P
+    rows = 1
+    for d in lead:
+        rows *= int(d)
+    keep = []
+    sl = StatsLaunch([t.shape[-1] for t in pmf_list], [t.shape[-1] for t in pmf_list], pct, q)
+    stats = [torch.empty(*lead, 8, dtype=torch.float64, device=dev) for _ in range(P)]
+    qtok = [torch.empty(*lead, len(q), dtype=torch.int32, device=dev) for _ in range(P)]
+    for p, t in enumerate(pmf_list):
+        if t.dim() < 1 or t.dtype != torch.float32 or t.device.type != "cuda" or t.device != dev or (
+                tuple(t.shape[:-1]) != lead) or not t.is_contiguous() or t.shape[-1] < 1:
+            raise ValueError("pmf_stats: every pmf must be a contiguous fp32 [..., V] tensor on the same GPU, the "
+                             "leading shapes equal")
+        sl.pmf[p], sl.stats[p], sl.qtok[p] = t.data_ptr(), stats[p].data_ptr(), qtok[p].data_ptr()
+        if vals[p] is not None:
+            keep.append(check_values(vals[p], t.shape[-1]).to(dev))
+            sl.values[p] = keep[-1].data_ptr()
+        if org[p] is not None:
+            o = org[p]
+            if o.dtype != torch.int64 or tuple(o.shape) != lead or o.device != dev:
+                raise ValueError("pmf_stats: an origin must be an int64 tensor of the pmf's leading shape on its GPU")
+            keep.append(o.contiguous())
+            sl.origin[p] = keep[-1].data_ptr()
+    with torch.cuda.device(dev):
+        sl.run(ML.lib(), ML.stream_ptr(dev), rows)
+    return stats, qtok
 
 
 RESAMPLE_MAX_SAMPLES = 4096  # csrc/mmt_evidence.hip RS_MAX_S: the S weights of a prompt stay in LDS

@@ -64,6 +64,7 @@ class JointPlan:
         self.roles, self.generated, self.given, self.B, self.n0, self.N = roles, generated, given, B, n0, N
         self.evidence, self.resample_every, self.ess_threshold = evidence, resample_every, ess_threshold
         self.points = resample_points(N, resample_every) if evidence == "resample" else []
+        self.forecast = None  # check_forecast's result: the forecast settings, None when off
 
 
 EVIDENCE_MODES = (None, "weights", "resample")
@@ -75,8 +76,40 @@ def resample_points(N, resample_every):
     return [j for j in range(N - 1) if (j + 1) % resample_every == 0]
 
 
+DEFAULT_QUANTILES = (0.05, 0.5, 0.95)
+
+
+def check_forecast(forecast, generated, vocab_sizes):
+    """generate's forecast= for the generated modalities: None / False (off), True, or a dict with the optional keys
+    "quantiles" (at most 16 levels in (0, 1)), "values" {i: V_i non-decreasing numbers} and "is_percent" {i: bool},
+    i generated. Returns None or {"quantiles": [floats], "values": {i: CPU fp64 [V_i]}, "is_percent": {i: bool}};
+    ValueError for anything else (checked on the host, once)."""
+    import mmt_sample as MS
+    if forecast is None or forecast is False:
+        return None
+    if forecast is True:
+        forecast = {}
+    if not isinstance(forecast, dict):
+        raise ValueError(f"generate: forecast must be True or a dict, got {forecast!r}")
+    for k in forecast:
+        if k not in ("quantiles", "values", "is_percent"):
+            raise ValueError(f"generate: forecast has no key {k!r} (quantiles, values, is_percent)")
+    out = {"quantiles": MS.check_quantiles(forecast.get("quantiles", DEFAULT_QUANTILES)), "values": {},
+           "is_percent": {}}
+    for name in ("values", "is_percent"):
+        d = forecast.get(name) or {}
+        if not isinstance(d, dict):
+            raise ValueError(f"generate: forecast[{name!r}] must be a dict {{modality: ...}}")
+        for i, x in d.items():
+            if i not in generated:
+                raise ValueError(f"generate: forecast[{name!r}] names modality {i!r}, which is not generated")
+            out[name][i] = (MS.check_values(x, vocab_sizes[i], f"forecast['values'][{i}]") if name == "values"
+                            else bool(x))
+    return out
+
+
 def plan_joint(modality_to_generate, given, vocab_sizes, prompt_shapes, max_new_tokens, num_samples=None,
-               evidence=None, resample_every=1, ess_threshold=0.5):
+               evidence=None, resample_every=1, ess_threshold=0.5, forecast=None):
     """generate's `modality_to_generate` and `given` as per-modality roles, every refusal of the list form that
     needs no device in one place. An int (the int form: one modality sampled, generate as it always ran) returns
     None, and refuses `given`. A sequence of distinct ints, even of one, or "all" is the list form (a joint
@@ -110,6 +143,9 @@ def plan_joint(modality_to_generate, given, vocab_sizes, prompt_shapes, max_new_
     if isinstance(g, int) and not isinstance(g, bool):
         if given is not None:
             raise ValueError("generate: given= needs the list form of modality_to_generate (a sequence or \"all\")")
+        if forecast is not None and forecast is not False:
+            raise ValueError(f"generate: forecast= needs the list form of modality_to_generate: pass [{g}] (a "
+                             "sequence, even of one, or \"all\")")
         return None
     if isinstance(g, str):
         if g != "all":
@@ -156,8 +192,10 @@ def plan_joint(modality_to_generate, given, vocab_sizes, prompt_shapes, max_new_
         if t.numel() and (int(t.min()) < 0 or int(t.max()) >= vocab_sizes[i]):
             raise ValueError(f"generate: given[{i}] holds tokens outside 0..{vocab_sizes[i] - 1}")
     roles = [GENERATED if i in gen else GIVEN if i in given else HELD for i in range(M)]
-    return JointPlan(roles, sorted(gen), dict(given), B, n0, N, evidence, resample_every,
+    plan = JointPlan(roles, sorted(gen), dict(given), B, n0, N, evidence, resample_every,
                      0.5 if evidence is None else float(ess_threshold))
+    plan.forecast = check_forecast(forecast, plan.generated, vocab_sizes)
+    return plan
 
 
 def joint_setting(value, generated, name):
@@ -627,7 +665,7 @@ class MultimodalTransformer(nn.Module):
     @torch.no_grad()
     def generate(self, idx_list, max_new_tokens=1, modality_to_generate=0, use_cache=True, sample_fn=None, *,
                  temperature=None, top_k=None, top_p=None, seed=None, return_logprobs=False, logits_hook=None,
-                 num_samples=None, given=None, evidence=None, resample_every=1, ess_threshold=0.5):
+                 num_samples=None, given=None, evidence=None, resample_every=1, ess_threshold=0.5, forecast=None):
         """model.py:404-446: per new token, the logits of the last position of the (block_size
         cropped) context, a sample from the softmax of the target modality's last logits
         (torch.multinomial, as the reference; `sample_fn(probs) -> [B, 1]` overrides it), appended;
@@ -687,11 +725,29 @@ class MultimodalTransformer(nn.Module):
         (seed, current row, position), so copies of one ancestor diverge at the next step. It needs num_samples
         (at most 4096) and the fan-out engine's conditions and raises ValueError otherwise (no fallback), and it
         holds two fan buffers. Returned rows are the final paths: "given_logprobs" are those of each path's own
-        history, "log_weights" the weights since the last resampling point."""
+        history, "log_weights" the weights since the last resampling point.
+
+        Forecast distributions (list form only; an int is refused, pass [g]): forecast=True, or a dict {"quantiles":
+        levels in (0, 1), at most 16 (default 0.05, 0.5, 0.95), "values": {i: fp64 [V_i], non-decreasing in token
+        order}, "is_percent": {i: bool}}, adds a last element `fc` = {i: {...}} per generated modality i: per new
+        token j and prompt the mixture of the laws the prompt's paths draw token j from (temperature / top-k / top-p
+        as the sampler applies them), weighted by the evidence where evidence= is on (mmt_forecast_multi in
+        include/mmt.h, one call per token after the sampling, on every path of the list form; with evidence the weights
+        are the carried log-weights times the given columns since the last resampling point through j, so step j
+        estimates p(token j | prompt, given series through j), taken before a resampling at j). Without
+        num_samples every row is a prompt of one path and the pmf is the sampler's own distribution of that row.
+        Keys: "pmf" fp32 [Bp, N, V_i]; "ess" fp64 and "live" int32 [Bp, N] (the effective number and the number of
+        paths behind each pmf); after the loop one mmt_pmf_stats gives "entropy" (nats), "mean", "var" (of the value;
+        NaN without values), "p_down" / "p_flat" / "p_up" (the mass of tokens below / at / above zero for a percent
+        series, the prompt's last token of that modality for a value series: at step 0 the reference's directional
+        certainty), fp64 [Bp, N]; "quantile_tokens" int32 [Bp, N, Q] and "quantile_values" fp64 [Bp, N, Q] (NaN
+        without values). Sequences, log-probabilities and `ev` are bit-identical to the call without forecast=. Out
+        of scope: direction against each path's own previous token at steps j > 0 (it depends on the path, not on
+        the mixture), and smoothing weights from the whole given series (step j sees the series through j only)."""
         if num_samples is not None:
             num_samples = check_num_samples(num_samples)
         plan = plan_joint(modality_to_generate, given, self.vocab_sizes, [tuple(s.shape) for s in idx_list],
-                          max_new_tokens, num_samples, evidence, resample_every, ess_threshold)
+                          max_new_tokens, num_samples, evidence, resample_every, ess_threshold, forecast)
         if plan is not None:
             if sample_fn is not None:
                 raise ValueError("generate: sample_fn cannot be combined with a joint rollout (a list of modalities "
@@ -927,7 +983,9 @@ class MultimodalTransformer(nn.Module):
         modality's last-position logits in place. With plan.evidence a step also issues one mmt_score_multi over
         the given modalities' views and the given tokens of column n, which the sequence buffers hold; "resample"
         adds, at the plan's points, mmt_resample, an index_select of every per-row buffer and mmt_fanout_gather
-        into the second fan buffer; a closing mmt_resample folds the remaining columns."""
+        into the second fan buffer; a closing mmt_resample folds the remaining columns. With plan.forecast a step
+        also issues one mmt_forecast_multi over the generated modalities' views, after the sampling and scoring and
+        before a resampling, into column j of preallocated [Bp, N, V_i] buffers; one mmt_pmf_stats follows the loop."""
         import mmt_sample as MS
         flat = self.flat_params
         dev = flat.device
@@ -981,16 +1039,32 @@ class MultimodalTransformer(nn.Module):
         # evidence: one scoring problem per given modality, over the views the sampler reads and the given token of
         # column n, which the sequence buffers already hold; the fp64 weights per row and evidence per prompt
         giv = sorted(plan.given) if plan.evidence is not None else []
+        Bp, Sp = (plan.B, S) if S is not None else (R, 1)  # without num_samples every row is a prompt of one path
         if giv:
             glp = {i: torch.zeros(R, N, dtype=torch.float32, device=dev) for i in giv}
             sl = MS.ScoreLaunch([self.vocab_sizes[i] for i in giv], [cap] * len(giv), [N] * len(giv))
-            Bp, Sp = (plan.B, S) if S is not None else (R, 1)  # without num_samples every row is a prompt of one path
             logw = torch.zeros(R, dtype=torch.float64, device=dev)
             logev = torch.zeros(Bp, dtype=torch.float64, device=dev)
             npts = len(plan.points)
             anc = torch.empty(npts + 1, R, dtype=torch.int32, device=dev)  # the last row: the closing fold's identity
             res = torch.empty(npts + 1, Bp, dtype=torch.int32, device=dev)
             rl = MS.ResampleLaunch([glp[i].data_ptr() for i in giv], [N] * len(giv))
+        # forecast: per generated modality the pmf of every (prompt, new token), ESS and live count as [N, Bp] (a
+        # step writes one contiguous row); the weights are those the evidence carries: logw and the given columns
+        fc = plan.forecast
+        if fc is not None:
+            fpmf = {i: torch.zeros(Bp, N, self.vocab_sizes[i], dtype=torch.float32, device=dev) for i in gen}
+            fess = {i: torch.zeros(N, Bp, dtype=torch.float64, device=dev) for i in gen}
+            flive = {i: torch.zeros(N, Bp, dtype=torch.int32, device=dev) for i in gen}
+            fl = MS.ForecastLaunch([self.vocab_sizes[i] for i in gen], settings,
+                                   [max(N, 1) * self.vocab_sizes[i] for i in gen],
+                                   [glp[i].data_ptr() for i in giv], [N] * len(giv))
+            fbytes = fl.scratch_bytes(L, Bp, Sp)
+            fscratch = torch.empty(max(fbytes, 16), dtype=torch.uint8, device=dev)
+            # with evidence the forecast carries rule 2's a_s itself, from one buffer into the other, and folds ONE
+            # column per step: the serial fp64 sum over the columns since the last point, bit for bit, at O(1) a step
+            facc = torch.zeros(2, R, dtype=torch.float64, device=dev) if giv else None
+            fcur = 0
 
         def decode_args(j):
             """The pointer arrays of the decode step that reads the tokens of new position j (made at first use)."""
@@ -1003,6 +1077,7 @@ class MultimodalTransformer(nn.Module):
                 p_idx[i] = st.data_ptr() + 8 * R * j
 
         def sample(n, j, views):
+            nonlocal fcur
             if logits_hook is not None:
                 logits_hook(n, views)
             for p, i in enumerate(gen):
@@ -1018,6 +1093,20 @@ class MultimodalTransformer(nn.Module):
                     sl.tok[p] = bufs[i].data_ptr() + 8 * n
                     sl.logprob[p] = glp[i].data_ptr() + 4 * j
                 sl.run(L, stream, R)
+            if fc is not None:  # the mixture of the laws just drawn from, weighted by the given columns since..j
+                for p, i in enumerate(gen):
+                    Vi = self.vocab_sizes[i]
+                    fl.logits[p] = views[i].data_ptr()
+                    fl.row_stride[p] = int(views[i].stride(0)) if R > 1 else Vi
+                    fl.pmf[p] = fpmf[i].data_ptr() + 4 * Vi * j
+                    fl.ess[p] = fess[i].data_ptr() + 8 * Bp * j
+                    fl.live[p] = flive[i].data_ptr() + 4 * Bp * j
+                if giv:
+                    fl.run(L, stream, Bp, Sp, j, j + 1, facc[fcur].data_ptr(), fscratch.data_ptr(), fbytes,
+                           facc[1 - fcur].data_ptr())
+                    fcur = 1 - fcur
+                else:
+                    fl.run(L, stream, Bp, Sp, 0, 0, 0, fscratch.data_ptr(), fbytes)
 
         def fold(j0, j1, threshold, pos, point):
             """mmt_resample over the given log-probabilities of the new tokens j0..j1-1 into row `point` of the
@@ -1061,6 +1150,8 @@ class MultimodalTransformer(nn.Module):
                         # a prompt that did not trigger), then every per-row buffer and the tails follow them
                         fold(last_point, j + 1, plan.ess_threshold, n, point)
                         follow(anc[point])
+                        if fc is not None:  # the forecast's carried sums restart from the folded weights
+                            facc[fcur].copy_(logw)
                         if j >= 1:
                             rc = L.mmt_fanout_gather(self._ctx, stream, plan.B, S, n0, N, j,
                                                      anc.data_ptr() + 4 * R * point, p_fan, p_fan2)
@@ -1089,11 +1180,38 @@ class MultimodalTransformer(nn.Module):
                 if giv:
                     fold(0, N, -1.0, n0 + N - 1, 0)
         seqs = [buf.to(idx_list[i].dtype) for i, buf in enumerate(bufs)]
+        out = [seqs] + ([lps] if return_logprobs else [])
         if giv:
-            ev = {"given_logprobs": glp, "log_weights": logw, "log_evidence": logev, "ancestors": anc[:npts],
-                  "resampled": res[:npts], "steps": list(plan.points)}
-            return (seqs, lps, ev) if return_logprobs else (seqs, ev)
-        return (seqs, lps) if return_logprobs else seqs
+            out.append({"given_logprobs": glp, "log_weights": logw, "log_evidence": logev, "ancestors": anc[:npts],
+                        "resampled": res[:npts], "steps": list(plan.points)})
+        if fc is not None:
+            # one mmt_pmf_stats over every (prompt, new token) row of every generated modality; the origin of a value
+            # series' direction is the prompt's last token of that modality
+            Q = len(fc["quantiles"])
+            st = MS.StatsLaunch([self.vocab_sizes[i] for i in gen], [self.vocab_sizes[i] for i in gen],
+                                [fc["is_percent"].get(i, False) for i in gen], fc["quantiles"])
+            stats = {i: torch.empty(Bp, N, 8, dtype=torch.float64, device=dev) for i in gen}
+            qtok = {i: torch.empty(Bp, N, Q, dtype=torch.int32, device=dev) for i in gen}
+            vals = {i: v.to(dev) for i, v in fc["values"].items()}
+            origin = {i: prompts[i][:, -1:].expand(Bp, N).contiguous() for i in gen}
+            for p, i in enumerate(gen):
+                st.pmf[p], st.stats[p], st.qtok[p] = fpmf[i].data_ptr(), stats[i].data_ptr(), qtok[i].data_ptr()
+                st.values[p] = vals[i].data_ptr() if i in vals else None
+                st.origin[p] = origin[i].data_ptr()
+            with torch.cuda.device(dev):
+                st.run(L, ML.stream_ptr(dev), Bp * N)
+            res_fc = {}
+            for i in gen:
+                s, qt = stats[i], qtok[i]
+                if i in vals:
+                    qv = torch.where(qt >= 0, vals[i][qt.clamp_min(0).long()], float("nan"))
+                else:
+                    qv = torch.full((Bp, N, Q), float("nan"), dtype=torch.float64, device=dev)
+                res_fc[i] = {"pmf": fpmf[i], "ess": fess[i].t().contiguous(), "live": flive[i].t().contiguous(),
+                             "entropy": s[..., 1], "mean": s[..., 2], "var": s[..., 3], "p_down": s[..., 4],
+                             "p_flat": s[..., 5], "p_up": s[..., 6], "quantile_tokens": qt, "quantile_values": qv}
+            out.append(res_fc)
+        return out[0] if len(out) == 1 else tuple(out)
 
     @torch.no_grad()
     def _decode_step(self, tokens, pos):
