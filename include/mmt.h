@@ -337,6 +337,64 @@ int mmt_pmf_stats(void* stream, int32_t count, int32_t rows, const int32_t* V, c
                   const int64_t* origin_stride, int32_t nq, const double* levels, double* const* stats,
                   int32_t* const* qtok);
 
+/* Horizon forecasts. mmt_forecast_multi gives the law of the token at new step j: for a percent series the law of one
+ * step's change. Where the series stands after j steps, its quantiles there and whether it touched a barrier by then
+ * depend on each path's own history. mmt_horizon_stats computes them from the finished paths and their log-weights,
+ * in one call after the loop. No context.
+ *
+ * `count` problems (modalities) over `batch` prompts of `samples` rows each, row r = b * samples + s, `steps` new
+ * tokens per row. Per problem (HOST arrays): V; tok (device int64, token j of row r at tok[p] + r * tok_stride[p] + j:
+ * the caller points at the first new column of a sequence buffer); values (device fp64 [V], required); is_percent
+ * (nullable: all 0); origin (device int64, row r's at origin[p][r * origin_stride[p]]; required for a value series,
+ * not read for a percent series). Shared by all problems: logw fp64 [batch * samples] (nullable), `nq` <= 16 HOST
+ * levels in (0, 1), `nb` <= 8 barriers per problem (HOST array of HOST arrays, every entry finite and non-zero).
+ * Outputs per problem: stats fp64 [batch, steps, 12], qval fp64 and qrow int32 [batch, steps, nq], hit fp64 [batch,
+ * steps, nb], ess fp64 [batch], live int32 [batch]; qval / qrow / hit may be NULL when nq / nb is 0, the arrays ess /
+ * live and their entries may be NULL. scratch: mmt_horizon_scratch_bytes(count, batch, samples, steps) bytes of
+ * device memory, 16-byte aligned, its contents unspecified before and after.
+ * The rule, per problem and prompt b, with v = values:
+ *   1. path quantities, per row and step in fp64, serially in step order, every line ONE IEEE operation (nothing is
+ *      contracted into a multiply-add). Percent series: c = v[t_j] / 100; u = 1 + c; g_j = g_{j-1} * u (g_{-1} = 1);
+ *      e = g_j - 1; x_j = e * 100. Value series: x_j = v[t_j] - v[origin]. Running extremes including the origin:
+ *      hi_j = max(hi_{j-1}, x_j), lo_j = min(lo_{j-1}, x_j), hi_{-1} = lo_{-1} = 0. Step direction d_j: the sign of
+ *      v[t_j] for a percent series, of v[t_j] - v[t_{j-1}] for a value series with t_{-1} the origin (the reference's
+ *      _get_direction_sign against each path's own previous token). A row is dead in the problem when one of its
+ *      tokens is outside 0..V-1, when it is a value series and its origin is outside 0..V-1, or when some x_j is not
+ *      finite. Nothing is read out of range.
+ *   2. weights, mmt_resample's rules 1 - 2 as in mmt_forecast_multi: a_s = logw[r] (NaN counts as -inf); mx = max over
+ *      the rows that are not dead; w_s = 1 where (float)(a_s - mx) == 0, else expf of it; dead rows and a_s = -inf
+ *      get 0. W = sum w_s and Q = sum w_s^2 in fp64 over mmt_resample's tree; ess = W^2 / Q; live = #{ w_s > 0 }.
+ *      Without logw w_s = 1 on every row that is not dead.
+ *   3. stats[b, j, 0..11], fp64 sums over the prompt's rows in row order over the same tree:
+ *        [0] mean sum w x / W            [1] variance sum w (x - mean)^2 / W
+ *        [2..4] the mass / W of x < 0, x == 0, x > 0 (direction over the horizon)
+ *        [5..7] the mass / W of d = -1, 0, +1 (step direction)
+ *        [8] mean of hi   [9] mean of lo   [10], [11] the smallest and the largest x over the rows with w > 0
+ *   4. quantiles: the rows with w > 0 in the order (x_j, s) ascending; qrow[k] is the local path index s of the first
+ *      row whose inclusive fp64 prefix sum of w in that order reaches levels[k] * W (one fp64 product; should
+ *      rounding leave none, the last row with weight), qval[k] that row's x_j, bit for bit.
+ *   5. barriers: hit[b, j, k] = sum w [hi_j >= u] / W for u > 0 and sum w [lo_j <= u] / W for u < 0: the probability
+ *      of having touched the barrier by step j, which does not decrease in j.
+ * live == 0 gives NaN stats, NaN qval, qrow -1, NaN hit, ess 0. No float atomics: bit-identical run to run; a prompt
+ * launched alone (same samples) gives the bits it gives in company, and so does a problem. Nothing outside the named
+ * outputs is written.
+ * Launches: one over (rows / 256, problems) for rule 1, one over (prompts x steps, problems) for the rest (the
+ * weights of a prompt and the keys of one step in LDS, 56 KiB at 4096 rows); more than 8 problems go in chunks of 8.
+ * MMT_ERR_INVALID before any launch, nothing written: a negative count, batch or steps; samples < 1; batch * samples
+ * >= 2^31; nq outside 0..16 or nb outside 0..8; a level outside (0, 1) or NaN; a barrier that is zero, NaN or
+ * infinite; V < 1; tok_stride < steps; a null required array or entry; a value series without origin; a scratch that
+ * is null, misaligned or undersized. MMT_ERR_UNSUPPORTED: V > 2^20, samples > 4096, batch * steps >= 2^31. count,
+ * batch or steps of 0 launches nothing. mmt_horizon_scratch_bytes returns -1 for arguments the entry refuses. */
+int64_t mmt_horizon_scratch_bytes(int32_t count, int32_t batch, int32_t samples, int32_t steps);
+int mmt_horizon_stats(void* stream, int32_t count, int32_t batch, int32_t samples, int32_t steps, const int32_t* V,
+                      const int64_t* const* tok, const int64_t* tok_stride, const double* const* values,
+                      const int32_t* is_percent /* nullable */, const int64_t* const* origin,
+                      const int64_t* origin_stride, const double* logw /* nullable */, int32_t nq,
+                      const double* levels, int32_t nb, const double* const* barriers, double* const* stats,
+                      double* const* qval, int32_t* const* qrow, double* const* hit,
+                      double* const* ess /* nullable, entries nullable */,
+                      int32_t* const* live /* nullable, entries nullable */, void* scratch, int64_t scratch_bytes);
+
 /* failure detection (the reference's guard is the NaN check on eval losses,
  * main.py:606): byte offset in the workspace of two int32 bitmasks (the same for every batch size;
  * the query never touches the workspace plan of a pending backward or decode). The

@@ -36,6 +36,13 @@ write without it: a logits_hook that computes the unfiltered, unweighted mixture
 a prompt's paths, a copy into a [B, N, V] tensor). --forecast also adds the two entries alone: us per
 mmt_forecast_multi call over the four heads at 64 rows (64 prompts of one path), 512 and 4096 rows (one prompt),
 without and with weights, and us per mmt_pmf_stats launch over the four heads at 64 / 512 / 4096 pmf rows.
+
+Horizon forecasts (--horizon): without --samples the paths joint,joint_horizon and joint_weights,joint_weights_horizon;
+with --samples fanout_joint,fanout_joint_horizon and fanout_weights,fanout_weights_horizon. `_horizon` is the same call
+with horizon={"values": ..., "is_percent": {0: True}, "barriers": ...} over every generated head. --horizon also adds
+the entry alone: us per mmt_horizon_stats call over the four heads and 128 steps at 64 rows (64 prompts of one path),
+512 and 4096 rows (one prompt), without and with log-weights, beside the torch formulation a caller can write on the
+same device (value gather, cumprod, sort, cumsum of the sorted weights, searchsorted).
 """
 import argparse
 import json
@@ -66,7 +73,12 @@ def main():
     ap.add_argument("--gather", action="store_true", help="with --samples: mmt_fanout_gather alone (this tree only)")
     ap.add_argument("--forecast", action="store_true",
                     help="the forecast paths by default, and the two forecast entries alone (this tree only)")
+    ap.add_argument("--horizon", action="store_true",
+                    help="the horizon paths by default, and mmt_horizon_stats alone against torch (this tree only)")
     a = ap.parse_args()
+    if a.horizon and a.paths == "default,device":
+        a.paths = ("fanout_joint,fanout_joint_horizon,fanout_weights,fanout_weights_horizon"
+                   if a.samples else "joint,joint_horizon,joint_weights,joint_weights_horizon")
     if a.forecast and a.paths == "default,device":
         a.paths = ("fanout_joint,fanout_joint_forecast,fanout_joint_hook,fanout_weights,fanout_weights_forecast"
                    if a.samples else "joint,joint_forecast,joint_hook,joint_weights,joint_weights_forecast")
@@ -110,6 +122,9 @@ def main():
     calls["joint_forecast"] = lambda: model.generate(prompt, forecast=True, **jkw)[0]
     calls["joint_hook"] = lambda: model.generate(prompt, logits_hook=mixture_hook(torch, dev, a, 1), **jkw)
     calls["joint_weights_forecast"] = lambda: model.generate(prompt, evidence="weights", forecast=True, **gkw)[0]
+    calls["joint_horizon"] = lambda: model.generate(prompt, horizon=horizon_arg(torch, range(4)), **jkw)[0]
+    calls["joint_weights_horizon"] = lambda: model.generate(prompt, evidence="weights",
+                                                            horizon=horizon_arg(torch, range(3)), **gkw)[0]
     paths = [p for p in a.paths.split(",") if p]
     if a.samples:
         return fanout_bench(a, torch, dev, model, prompt, paths)
@@ -136,7 +151,77 @@ def main():
         res["sampler_multi_us"] = sampler_multi_alone(torch, dev, a.rounds)
     if a.forecast:
         res["forecast_us"] = forecast_alone(torch, dev, a.rounds)
+    if a.horizon:
+        res["horizon_us"] = horizon_alone(torch, dev, a.new, a.rounds)
     print(json.dumps(res), flush=True)
+
+
+def horizon_arg(torch, mods):
+    """generate's horizon= over the heads `mods`: a sorted vocabulary of percent changes per head (modality 0 a percent
+    series, the others value series), two barriers each."""
+    return {"values": {i: torch.linspace(-2.0, 2.0, C1["V"][i], dtype=torch.float64) for i in mods},
+            "is_percent": {0: True}, "barriers": {i: [1.0, -1.0] for i in mods}}
+
+
+def horizon_alone(torch, dev, steps, rounds, reps=20):
+    """us per mmt_horizon_stats call (its two launches) over the four C1 heads and `steps` new tokens at 64 rows (64
+    prompts of one path), 512 and 4096 rows (one prompt of as many paths), without and with log-weights, three
+    levels and two barriers; and the torch formulation of one head's quantiles a caller could write: gather the
+    values, cumprod, sort every (prompt, step) column, cumsum of the gathered weights, searchsorted (times four for
+    the four heads; no moments, directions, extremes or barriers). HIP events around `reps` calls, best of `rounds`."""
+    import mmt_lib as ML
+    import mmt_sample as MS
+    L, st = ML.lib(), ML.stream_ptr(dev)
+    Vs = C1["V"]
+    out = {}
+
+    def timed(fn):
+        best = None
+        for _ in range(rounds):
+            fn()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            for _k in range(reps):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            us = e0.elapsed_time(e1) / reps * 1e3
+            best = us if best is None else min(best, us)
+        return round(best, 2)
+
+    g = torch.Generator().manual_seed(9)
+    for rows in (64, 512, 4096):
+        B, S = (64, 1) if rows == 64 else (1, rows)
+        toks = [torch.randint(0, V, (rows, steps), generator=g).to(dev) for V in Vs]
+        org = [torch.randint(0, V, (rows,), generator=g).to(dev) for V in Vs]
+        vals = [torch.linspace(-2.0, 2.0, V, dtype=torch.float64, device=dev) for V in Vs]
+        logw = (torch.randn(rows, generator=g, dtype=torch.float64) * 2.0).to(dev)
+        hl = MS.HorizonLaunch(Vs, [steps] * 4, [True, False, False, False], (0.05, 0.5, 0.95), [[1.0, -1.0]] * 4)
+        outs = MS.horizon_outputs(4, B, steps, hl.nq, hl.nb, dev)
+        for i in range(4):
+            hl.tok[i], hl.values[i], hl.origin[i] = toks[i].data_ptr(), vals[i].data_ptr(), org[i].data_ptr()
+            hl.stats[i], hl.qval[i], hl.qrow[i], hl.hit[i], hl.ess[i], hl.live[i] = [x.data_ptr() for x in outs[i]]
+        nbytes = hl.scratch_bytes(L, B, S, steps)
+        scratch = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+        levels = torch.tensor([0.05, 0.5, 0.95], dtype=torch.float64, device=dev)
+
+        def torch_form(weighted):
+            for i in range(4):
+                v = vals[i][toks[i]]                                        # [rows, steps]
+                x = ((1.0 + v / 100.0).cumprod(1) - 1.0) * 100.0 if i == 0 else v - vals[i][org[i]][:, None]
+                xs, order = x.view(B, S, steps).sort(dim=1)                 # every (prompt, step) column
+                w = torch.exp(logw - logw.max()) if weighted else torch.ones_like(logw)
+                cw = w.view(B, S, 1).expand(B, S, steps).gather(1, order).cumsum(1)
+                tgt = levels.view(1, 1, 3) * cw[:, -1:, :].transpose(1, 2)  # [B, steps, 3]
+                pos = torch.searchsorted(cw.transpose(1, 2).contiguous(), tgt.contiguous()).clamp_(max=S - 1)
+                xs.transpose(1, 2).gather(2, pos)
+
+        for name, weighted in (("plain", False), ("weights", True)):
+            lw = logw.data_ptr() if weighted else 0
+            out[f"horizon_rows{rows}_{name}"] = timed(lambda: hl.run(L, st, B, S, steps, lw, scratch.data_ptr(), nbytes))
+            out[f"torch_rows{rows}_{name}"] = timed(lambda: torch_form(weighted))
+    return out
 
 
 def mixture_hook(torch, dev, a, S):
@@ -239,6 +324,9 @@ def fanout_bench(a, torch, dev, model, prompt, paths):
     calls["fanout_joint_forecast"] = lambda: model.generate(prompt, forecast=True, **jkw)[0]
     calls["fanout_joint_hook"] = lambda: model.generate(prompt, logits_hook=mixture_hook(torch, dev, a, S), **jkw)
     calls["fanout_weights_forecast"] = lambda: model.generate(prompt, evidence="weights", forecast=True, **gkw)[0]
+    calls["fanout_joint_horizon"] = lambda: model.generate(prompt, horizon=horizon_arg(torch, range(4)), **jkw)[0]
+    calls["fanout_weights_horizon"] = lambda: model.generate(prompt, evidence="weights",
+                                                             horizon=horizon_arg(torch, range(3)), **gkw)[0]
     rec = {p: {"paths_per_s": [], "tokens_per_s": [], "peak_bytes": []} for p in paths}
 
     def one(p, timed):
@@ -272,6 +360,8 @@ def fanout_bench(a, torch, dev, model, prompt, paths):
         res["gather"] = gather_alone(torch, dev, model, prompt, B, S, a.prompt, a.new, a.rounds)
     if a.forecast:
         res["forecast_us"] = forecast_alone(torch, dev, a.rounds)
+    if a.horizon:
+        res["horizon_us"] = horizon_alone(torch, dev, a.new, a.rounds)
     print(json.dumps(res), flush=True)
 
 

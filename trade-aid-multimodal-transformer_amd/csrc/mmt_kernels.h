@@ -377,6 +377,25 @@ struct PmfStatsProblem {
 struct PmfStatsBatch { PmfStatsProblem p[MMT_MAX_GROUP]; double level[MMT_PMF_MAX_Q]; int nq; };
 hipError_t mmt_launch_pmf_stats(const PmfStatsBatch& b, int n, int rows, hipStream_t s);
 
+// Horizon forecasts (mmt_horizon_stats, mmt_horizon.hip). Row r = b * samples + s. The launcher validates nothing: the
+// C entry does. `index` is the problem's place in the scratch (per bytes a problem), which holds per (problem, step,
+// row) the path quantities of rule 1 and per (problem, row) the dead flag.
+#define MMT_HZ_MAX_Q 16
+#define MMT_HZ_MAX_B 8
+struct HorizonProblem {
+  const int64_t* tok; int64_t tok_stride;
+  const double* values;
+  const int64_t* origin; int64_t origin_stride;                   // not read for a percent series
+  double* stats; double* qval; int32_t* qrow; double* hit;        // qval / qrow / hit: null with nq / nb == 0
+  double* ess; int32_t* live;                                     // nullable
+  double barrier[MMT_HZ_MAX_B];
+  int V, is_percent, index;
+};
+struct HorizonBatch { HorizonProblem p[MMT_MAX_GROUP]; double level[MMT_HZ_MAX_Q]; int nq, nb; };
+// walk, grid (ceil(rows / 256), n), then reduce, grid (batch * steps, n); samples <= 4096
+hipError_t mmt_launch_horizon(const HorizonBatch& b, int n, void* scratch, int64_t rows, int64_t per, int batch,
+                              int samples, int steps, const double* logw, hipStream_t s);
+
 // ------------------------------------------------------------------------------------------
 // Per-head Q/K/V stage 2: block-diagonal [hs/2 -> hs] maps (model.py:39,44,49), nblk = 3*H.
 //   out[r, blk*hs + o] = sum_i W2[blk][o][i] * h1[r, blk*hs/2 + i]

@@ -132,6 +132,13 @@ _SIGS = {
                               ctypes.POINTER(c_vp), ctypes.POINTER(c_i32), ctypes.POINTER(c_vp),
                               ctypes.POINTER(c_i64), c_i32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(c_vp),
                               ctypes.POINTER(c_vp)]),
+    "mmt_horizon_scratch_bytes": (c_i64, [c_i32, c_i32, c_i32, c_i32]),
+    "mmt_horizon_stats": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(c_i32), ctypes.POINTER(c_vp),
+                                  ctypes.POINTER(c_i64), ctypes.POINTER(c_vp), ctypes.POINTER(c_i32),
+                                  ctypes.POINTER(c_vp), ctypes.POINTER(c_i64), c_vp, c_i32,
+                                  ctypes.POINTER(ctypes.c_double), c_i32, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp),
+                                  ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), ctypes.POINTER(c_vp),
+                                  ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp, c_i64]),
     "mmt_fanout_gather": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "mmt_backward_stage_count": (c_i32, [c_vp]),
     "mmt_backward_stage_range": (c_i32, [c_vp, c_i32, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),

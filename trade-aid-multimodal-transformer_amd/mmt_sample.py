@@ -24,6 +24,12 @@ weighted as mmt_resample weighs them (mmt_forecast_multi), and the summaries of 
 
     pmfs, ess, live = mmt_sample.forecast_multi([logits_0], samples=S, temperature=0.8, top_k=50, logprobs=lps_list)
     stats, qtok = mmt_sample.pmf_stats(pmfs, values=[vocab_values_0], is_percent=True, quantiles=(0.05, 0.5, 0.95))
+
+Horizon forecasts (generate's horizon=): where a series stands after j new steps, from the finished paths and their
+log-weights (mmt_horizon_stats): cumulative change per path, its weighted moments, quantiles and barrier hits:
+
+    hz = mmt_sample.horizon_stats([seqs_0[:, n0:]], samples=S, values=[vocab_values_0], is_percent=True,
+                                  logw=ev["log_weights"], barriers=[[-2.0, 2.0]])
 """
 import ctypes
 
@@ -446,6 +452,164 @@ def pmf_stats(pmf_list, *, values=None, is_percent=False, origin=None, quantiles
     with torch.cuda.device(dev):
         sl.run(ML.lib(), ML.stream_ptr(dev), rows)
     return stats, qtok
+
+
+HORIZON_FIELDS = ("mean", "var", "p_down", "p_flat", "p_up", "step_down", "step_flat", "step_up", "mean_high",
+                  "mean_low", "min", "max")  # stats[..., k] of mmt_horizon_stats
+HORIZON_MAX_BARRIERS = 8
+HORIZON_MAX_SAMPLES = 4096  # csrc/mmt_horizon.hip HZ_MAX_S: the rows of a (prompt, step) are sorted in LDS
+
+
+def check_barriers(barriers):
+    """The barriers of one problem as mmt_horizon_stats takes them: at most 8 finite non-zero numbers (None: none);
+    ValueError otherwise."""
+    if barriers is None:
+        return []
+    try:
+        u = [float(x) for x in barriers]
+    except (TypeError, ValueError):
+        raise ValueError(f"horizon: barriers must be a sequence of numbers, got {barriers!r}") from None
+    if len(u) > HORIZON_MAX_BARRIERS:
+        raise ValueError(f"horizon: at most {HORIZON_MAX_BARRIERS} barriers, got {len(u)}")
+    for x in u:
+        if x != x or x in (float("inf"), float("-inf")) or x == 0.0:
+            raise ValueError(f"horizon: a barrier must be finite and non-zero, got {x!r}")
+    return u
+
+
+class HorizonLaunch:
+    """The host arrays of one mmt_horizon_stats call over P problems (include/mmt.h), made once: the caller fills
+    `tok[p]` / `values[p]` / `origin[p]` / `stats[p]` / `qval[p]` / `qrow[p]` / `hit[p]` / `ess[p]` / `live[p]` (raw
+    addresses; ess / live 0 = absent) and the strides, and calls `run`. barriers: P lists of the same length."""
+
+    def __init__(self, V, tok_stride, is_percent, quantiles, barriers):
+        P = self.P = len(V)
+        n = max(1, P)
+        q = check_quantiles(quantiles)
+        bars = [check_barriers(b) for b in barriers]
+        if len(bars) != P or len({len(b) for b in bars}) > 1:
+            raise ValueError("horizon: one list of barriers per problem, all of one length")
+        self.nq, self.nb = len(q), len(bars[0]) if bars else 0
+        self.V = (ctypes.c_int32 * n)(*[int(v) for v in V])
+        self.tok = (ctypes.c_void_p * n)()
+        self.tok_stride = (ctypes.c_int64 * n)(*[int(x) for x in tok_stride])
+        self.values = (ctypes.c_void_p * n)()
+        self.is_percent = (ctypes.c_int32 * n)(*[1 if x else 0 for x in is_percent])
+        self.origin = (ctypes.c_void_p * n)()
+        self.origin_stride = (ctypes.c_int64 * n)(*([1] * P))
+        self.levels = (ctypes.c_double * max(1, self.nq))(*q)
+        self._bars = [(ctypes.c_double * max(1, self.nb))(*b) for b in bars]  # kept alive: `barriers` points at them
+        self.barriers = (ctypes.c_void_p * n)(*[ctypes.addressof(b) for b in self._bars])
+        self.stats = (ctypes.c_void_p * n)()
+        self.qval = (ctypes.c_void_p * n)()
+        self.qrow = (ctypes.c_void_p * n)()
+        self.hit = (ctypes.c_void_p * n)()
+        self.ess = (ctypes.c_void_p * n)()
+        self.live = (ctypes.c_void_p * n)()
+
+    def scratch_bytes(self, L, batch, samples, steps):
+        """mmt_horizon_scratch_bytes for this launch's problems; ValueError for a shape the entry refuses."""
+        n = L.mmt_horizon_scratch_bytes(self.P, int(batch), int(samples), int(steps))
+        if n < 0:
+            raise ValueError(f"horizon: {batch} prompts x {samples} samples x {steps} steps is a shape the entry "
+                             f"refuses (at most {HORIZON_MAX_SAMPLES} samples per prompt)")
+        return int(n)
+
+    def run(self, L, stream, batch, samples, steps, logw_ptr, scratch_ptr, scratch_bytes):
+        """One mmt_horizon_stats (logw_ptr: a raw address, 0 = absent). Raises MmtError on a non-zero status."""
+        rc = L.mmt_horizon_stats(stream, self.P, batch, samples, steps, self.V, self.tok, self.tok_stride, self.values,
+                                 self.is_percent, self.origin, self.origin_stride, logw_ptr or None, self.nq,
+                                 self.levels, self.nb, self.barriers, self.stats, self.qval, self.qrow, self.hit,
+                                 self.ess, self.live, scratch_ptr, scratch_bytes)
+        if rc != 0:
+            raise ML.MmtError(f"mmt_horizon_stats failed (status {rc})")
+
+
+def horizon_outputs(P, batch, steps, nq, nb, dev):
+    """The output tensors of one mmt_horizon_stats call, per problem: (stats, qval, qrow, hit, ess, live)."""
+    return [(torch.empty(batch, steps, 12, dtype=torch.float64, device=dev),
+             torch.empty(batch, steps, nq, dtype=torch.float64, device=dev),
+             torch.empty(batch, steps, nq, dtype=torch.int32, device=dev),
+             torch.empty(batch, steps, nb, dtype=torch.float64, device=dev),
+             torch.zeros(batch, dtype=torch.float64, device=dev),  # zeros: steps == 0 launches nothing
+             torch.zeros(batch, dtype=torch.int32, device=dev)) for _ in range(P)]
+
+
+def horizon_dict(outs):
+    """One problem's outputs as the dict generate(horizon=) and horizon_stats return: the HORIZON_FIELDS as fp64
+    [B, N], "quantile_values" fp64 and "quantile_paths" int32 [B, N, Q], "hit" fp64 [B, N, nb], "ess", "live" [B]."""
+    stats, qval, qrow, hit, ess, live = outs
+    d = {name: stats[..., k] for k, name in enumerate(HORIZON_FIELDS)}
+    d.update(quantile_values=qval, quantile_paths=qrow, hit=hit, ess=ess, live=live)
+    return d
+
+
+def horizon_stats(tokens_list, *, samples, values, is_percent=False, origin=None, logw=None,
+                  quantiles=(0.05, 0.5, 0.95), barriers=None):
+    """Horizon forecasts of finished paths (mmt_horizon_stats, include/mmt.h): tokens_list holds P int64 [B * samples,
+    N] tensors on one GPU (the new tokens of each path; rows may be strided, e.g. `seqs[i][:, n0:]`), row b * samples
+    + s being path s of prompt b. values: a list of P vocabularies (V_p non-decreasing numbers each, required);
+    is_percent: a bool or P bools; origin: None or a list of P entries, each None (a percent series) or an int64
+    [B * samples] tensor (the token a value series' change is measured from: the column before the new ones); logw:
+    None or fp64 [B * samples] log-weights, weighed as mmt_resample weighs them; quantiles: at most 16 levels;
+    barriers: None or a list of P lists (one length) of at most 8 finite non-zero numbers. Returns a list of P dicts
+    (horizon_dict): per (prompt, step) the weighted moments of the cumulative change x, the masses of its sign and of
+    the step direction, the means of the running high and low, min / max, quantiles with the path that carries each,
+    the probability of having touched each barrier; per prompt ess and live. No sync."""
+    P = len(tokens_list)
+    q = check_quantiles(quantiles)
+    S = int(samples)
+    if S < 1:
+        raise ValueError(f"horizon_stats: samples must be >= 1, got {samples!r}")
+    if S > HORIZON_MAX_SAMPLES:
+        raise ValueError(f"horizon_stats: at most {HORIZON_MAX_SAMPLES} samples per prompt, got {S}")
+    if not isinstance(values, (list, tuple)) or len(values) != P:
+        raise ValueError(f"horizon_stats: values must be a list of {P} vocabularies (a horizon has no meaning on "
+                         "token indices)")
+    pct = _per_problem(is_percent, P, "is_percent")
+    org = _per_problem(origin, P, "origin") if isinstance(origin, (list, tuple)) else [origin] * P
+    bars = [[] for _ in range(P)] if barriers is None else [check_barriers(b) for b in barriers]
+    if len(bars) != P:
+        raise ValueError(f"horizon_stats: barriers must be a list of {P} lists")
+    if P == 0:
+        return []
+    R, N = tokens_list[0].shape[0], tokens_list[0].shape[1] if tokens_list[0].dim() == 2 else -1
+    dev = tokens_list[0].device
+    if R % S:
+        raise ValueError(f"horizon_stats: {R} rows are no multiple of samples={samples}")
+    B = R // S
+    if logw is not None and (logw.dtype != torch.float64 or logw.shape != (R,) or not logw.is_contiguous()
+                             or logw.device != dev):
+        raise ValueError(f"horizon_stats: logw must be a contiguous fp64 [{R}] tensor on the GPU")
+    keep = []
+    for p, t in enumerate(tokens_list):
+        if t.dim() != 2 or t.dtype != torch.int64 or t.device.type != "cuda" or t.device != dev or (
+                tuple(t.shape) != (R, N)) or (N > 1 and t.stride(1) != 1) or (R > 1 and t.stride(0) < N):
+            raise ValueError("horizon_stats: every tokens must be an int64 [rows, N] tensor on the same GPU, the "
+                             "elements of a row contiguous")
+        if values[p] is None:
+            raise ValueError(f"horizon_stats: problem {p} has no values")
+        if not pct[p]:
+            o = org[p]
+            if o is None or o.dtype != torch.int64 or tuple(o.shape) != (R,) or o.device != dev:
+                raise ValueError(f"horizon_stats: a value series needs an int64 [{R}] origin on the GPU (problem {p})")
+    hl = HorizonLaunch([len(torch.as_tensor(v).reshape(-1)) for v in values],
+                       [max(int(t.stride(0)), N) if R > 1 else max(N, 1) for t in tokens_list], pct, q, bars)
+    outs = horizon_outputs(P, B, N, hl.nq, hl.nb, dev)
+    for p, t in enumerate(tokens_list):
+        keep.append(check_values(values[p], hl.V[p]).to(dev))
+        hl.tok[p], hl.values[p] = t.data_ptr(), keep[-1].data_ptr()
+        if not pct[p]:
+            hl.origin[p] = org[p].data_ptr()
+            hl.origin_stride[p] = max(int(org[p].stride(0)), 1)
+        (hl.stats[p], hl.qval[p], hl.qrow[p], hl.hit[p], hl.ess[p],
+         hl.live[p]) = [x.data_ptr() if x.numel() else None for x in outs[p]]
+    L = ML.lib()
+    nbytes = hl.scratch_bytes(L, B, S, N)
+    scratch = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        hl.run(L, ML.stream_ptr(dev), B, S, N, logw.data_ptr() if logw is not None else 0, scratch.data_ptr(), nbytes)
+    return [horizon_dict(o) for o in outs]
 
 
 RESAMPLE_MAX_SAMPLES = 4096  # csrc/mmt_evidence.hip RS_MAX_S: the S weights of a prompt stay in LDS

@@ -65,6 +65,7 @@ class JointPlan:
         self.evidence, self.resample_every, self.ess_threshold = evidence, resample_every, ess_threshold
         self.points = resample_points(N, resample_every) if evidence == "resample" else []
         self.forecast = None  # check_forecast's result: the forecast settings, None when off
+        self.horizon = None  # check_horizon's result: the horizon settings, None when off
 
 
 EVIDENCE_MODES = (None, "weights", "resample")
@@ -108,8 +109,45 @@ def check_forecast(forecast, generated, vocab_sizes):
     return out
 
 
+def check_horizon(horizon, generated, vocab_sizes, forecast=None):
+    """generate's horizon= for the generated modalities: None / False (off), True, or a dict with the optional keys
+    "quantiles" (at most 16 levels in (0, 1)), "values" {i: V_i non-decreasing numbers}, "is_percent" {i: bool} and
+    "barriers" {i: at most 8 finite non-zero numbers}, i generated. values and is_percent default to those of
+    `forecast` (check_forecast's result) where it is given. Returns None or {"quantiles", "values" {i: CPU fp64 [V_i]},
+    "is_percent" {i: bool}, "barriers" {i: [floats]}, "modalities": the generated modalities with values, ascending};
+    ValueError for anything else, and when no generated modality has values (a horizon has no meaning on token
+    indices)."""
+    import mmt_sample as MS
+    if horizon is None or horizon is False:
+        return None
+    if horizon is True:
+        horizon = {}
+    if not isinstance(horizon, dict):
+        raise ValueError(f"generate: horizon must be True or a dict, got {horizon!r}")
+    for k in horizon:
+        if k not in ("quantiles", "values", "is_percent", "barriers"):
+            raise ValueError(f"generate: horizon has no key {k!r} (quantiles, values, is_percent, barriers)")
+    out = {"quantiles": MS.check_quantiles(horizon.get("quantiles", DEFAULT_QUANTILES)),
+           "values": dict(forecast["values"]) if forecast else {},
+           "is_percent": dict(forecast["is_percent"]) if forecast else {}, "barriers": {}}
+    for name in ("values", "is_percent", "barriers"):
+        d = horizon.get(name) or {}
+        if not isinstance(d, dict):
+            raise ValueError(f"generate: horizon[{name!r}] must be a dict {{modality: ...}}")
+        for i, x in d.items():
+            if i not in generated:
+                raise ValueError(f"generate: horizon[{name!r}] names modality {i!r}, which is not generated")
+            out[name][i] = (MS.check_values(x, vocab_sizes[i], f"horizon['values'][{i}]") if name == "values"
+                            else MS.check_barriers(x) if name == "barriers" else bool(x))
+    out["modalities"] = [i for i in generated if i in out["values"]]
+    if not out["modalities"]:
+        raise ValueError("generate: horizon= needs the values of a generated modality (horizon={\"values\": {i: ...}} "
+                         "or forecast's): a horizon has no meaning on token indices")
+    return out
+
+
 def plan_joint(modality_to_generate, given, vocab_sizes, prompt_shapes, max_new_tokens, num_samples=None,
-               evidence=None, resample_every=1, ess_threshold=0.5, forecast=None):
+               evidence=None, resample_every=1, ess_threshold=0.5, forecast=None, horizon=None):
     """generate's `modality_to_generate` and `given` as per-modality roles, every refusal of the list form that
     needs no device in one place. An int (the int form: one modality sampled, generate as it always ran) returns
     None, and refuses `given`. A sequence of distinct ints, even of one, or "all" is the list form (a joint
@@ -120,7 +158,9 @@ def plan_joint(modality_to_generate, given, vocab_sizes, prompt_shapes, max_new_
     number of prompts; prompts that are not [B, n0 >= 1] of one shape (the reference's pad / crop rule is defined
     around one generated modality). `evidence` ("weights" or "resample": the importance weights of the given series,
     generate's docstring) is refused without a given modality, with an unknown value, with resample_every < 1
-    or no integer, with a negative or NaN ess_threshold, and as "resample" without num_samples."""
+    or no integer, with a negative or NaN ess_threshold, and as "resample" without num_samples. `horizon`
+    (check_horizon) is refused in the int form and with num_samples > 4096 (the paths of a prompt are sorted on
+    chip)."""
     M = len(vocab_sizes)
     g = modality_to_generate
     if evidence not in EVIDENCE_MODES:
@@ -145,6 +185,9 @@ def plan_joint(modality_to_generate, given, vocab_sizes, prompt_shapes, max_new_
             raise ValueError("generate: given= needs the list form of modality_to_generate (a sequence or \"all\")")
         if forecast is not None and forecast is not False:
             raise ValueError(f"generate: forecast= needs the list form of modality_to_generate: pass [{g}] (a "
+                             "sequence, even of one, or \"all\")")
+        if horizon is not None and horizon is not False:
+            raise ValueError(f"generate: horizon= needs the list form of modality_to_generate: pass [{g}] (a "
                              "sequence, even of one, or \"all\")")
         return None
     if isinstance(g, str):
@@ -195,6 +238,12 @@ def plan_joint(modality_to_generate, given, vocab_sizes, prompt_shapes, max_new_
     plan = JointPlan(roles, sorted(gen), dict(given), B, n0, N, evidence, resample_every,
                      0.5 if evidence is None else float(ess_threshold))
     plan.forecast = check_forecast(forecast, plan.generated, vocab_sizes)
+    plan.horizon = check_horizon(horizon, plan.generated, vocab_sizes, plan.forecast)
+    if plan.horizon is not None and num_samples is not None:
+        import mmt_sample as MS
+        if num_samples > MS.HORIZON_MAX_SAMPLES:
+            raise ValueError(f"generate: horizon= sorts at most {MS.HORIZON_MAX_SAMPLES} samples per prompt, got "
+                             f"num_samples={num_samples}")
     return plan
 
 
@@ -665,7 +714,8 @@ class MultimodalTransformer(nn.Module):
     @torch.no_grad()
     def generate(self, idx_list, max_new_tokens=1, modality_to_generate=0, use_cache=True, sample_fn=None, *,
                  temperature=None, top_k=None, top_p=None, seed=None, return_logprobs=False, logits_hook=None,
-                 num_samples=None, given=None, evidence=None, resample_every=1, ess_threshold=0.5, forecast=None):
+                 num_samples=None, given=None, evidence=None, resample_every=1, ess_threshold=0.5, forecast=None,
+                 horizon=None):
         """model.py:404-446: per new token, the logits of the last position of the (block_size
         cropped) context, a sample from the softmax of the target modality's last logits
         (torch.multinomial, as the reference; `sample_fn(probs) -> [B, 1]` overrides it), appended;
@@ -741,13 +791,36 @@ class MultimodalTransformer(nn.Module):
         NaN without values), "p_down" / "p_flat" / "p_up" (the mass of tokens below / at / above zero for a percent
         series, the prompt's last token of that modality for a value series: at step 0 the reference's directional
         certainty), fp64 [Bp, N]; "quantile_tokens" int32 [Bp, N, Q] and "quantile_values" fp64 [Bp, N, Q] (NaN
-        without values). Sequences, log-probabilities and `ev` are bit-identical to the call without forecast=. Out
-        of scope: direction against each path's own previous token at steps j > 0 (it depends on the path, not on
-        the mixture), and smoothing weights from the whole given series (step j sees the series through j only)."""
+        without values). Sequences, log-probabilities and `ev` are bit-identical to the call without forecast=. The
+        direction against each path's own previous token at steps j > 0 depends on the path, not on the mixture:
+        horizon= reports it. Out of scope: smoothing weights from the whole given series (step j sees the series
+        through j only).
+
+        Horizon forecasts (list form only; an int is refused, pass [g]): forecast= gives the law of the token at
+        step j, for a percent series the law of ONE step's change. horizon=True, or a dict {"quantiles": levels,
+        "values": {i: ...}, "is_percent": {i: bool}, "barriers": {i: at most 8 finite non-zero numbers}} (values and
+        is_percent default to forecast='s, when that is given too), adds a last element `hz` = {i: {...}} after
+        `fc`, for every generated modality i with values (none: ValueError, a horizon has no meaning on token
+        indices): where the series stands after j steps on each path, x_j = ((prod over the steps of 1 + v / 100)
+        - 1) * 100 for a percent series and v[token j] - v[the prompt's last token] for a value series, summarised
+        over a prompt's paths under their final weights. One mmt_horizon_stats call (include/mmt.h) after the loop,
+        over the sequence buffers and, with evidence=, the final log_weights; no torch op or sync per token, on every
+        path of the list form (fan-out, tiled, no num_samples: then every row is a prompt of one path). Keys, fp64
+        [Bp, N]: "mean", "var" (of x); "p_down" / "p_flat" / "p_up" (the mass of x < 0, == 0, > 0: direction over the
+        horizon); "step_down" / "step_flat" / "step_up" (the direction of step j against each path's own previous
+        token, the reference's _get_direction_sign); "mean_high" / "mean_low" (the running extremes since the origin,
+        which counts as 0); "min" / "max"; "quantile_values" fp64 and "quantile_paths" int32 [Bp, N, Q] (the weighted
+        quantile of x and the path s of the prompt that carries it); "hit" fp64 [Bp, N, nb] (the probability of having
+        touched barrier u by step j: running high >= u for u > 0, running low <= u for u < 0; it does not decrease in
+        j); "ess" fp64 and "live" int32 [Bp]. Under evidence="resample" the rows are the final paths and follow their
+        ancestors, so every step's statistic is that of the surviving histories under the final weights: the
+        SMOOTHED estimate (given the whole series), not the filtered one forecast= reports; after heavy resampling
+        the early steps rest on few distinct ancestors. num_samples > 4096 is refused before the prefill. Sequences,
+        log-probabilities, `ev` and `fc` are bit-identical to the call without horizon=."""
         if num_samples is not None:
             num_samples = check_num_samples(num_samples)
         plan = plan_joint(modality_to_generate, given, self.vocab_sizes, [tuple(s.shape) for s in idx_list],
-                          max_new_tokens, num_samples, evidence, resample_every, ess_threshold, forecast)
+                          max_new_tokens, num_samples, evidence, resample_every, ess_threshold, forecast, horizon)
         if plan is not None:
             if sample_fn is not None:
                 raise ValueError("generate: sample_fn cannot be combined with a joint rollout (a list of modalities "
@@ -985,7 +1058,8 @@ class MultimodalTransformer(nn.Module):
         adds, at the plan's points, mmt_resample, an index_select of every per-row buffer and mmt_fanout_gather
         into the second fan buffer; a closing mmt_resample folds the remaining columns. With plan.forecast a step
         also issues one mmt_forecast_multi over the generated modalities' views, after the sampling and scoring and
-        before a resampling, into column j of preallocated [Bp, N, V_i] buffers; one mmt_pmf_stats follows the loop."""
+        before a resampling, into column j of preallocated [Bp, N, V_i] buffers; one mmt_pmf_stats follows the loop.
+        With plan.horizon one mmt_horizon_stats follows the loop too, over the sequence buffers' new columns."""
         import mmt_sample as MS
         flat = self.flat_params
         dev = flat.device
@@ -1211,6 +1285,34 @@ class MultimodalTransformer(nn.Module):
                              "entropy": s[..., 1], "mean": s[..., 2], "var": s[..., 3], "p_down": s[..., 4],
                              "p_flat": s[..., 5], "p_up": s[..., 6], "quantile_tokens": qt, "quantile_values": qv}
             out.append(res_fc)
+        hz = plan.horizon
+        if hz is not None:
+            # one mmt_horizon_stats over the final paths: tok at column n0 of the sequence buffers, the origin of a
+            # value series at column n0 - 1, the weights the final log_weights. One nb per call: shorter barrier lists
+            # are padded (with 1.0) and their columns cut from the result.
+            mods = hz["modalities"]
+            nbar = max([len(hz["barriers"].get(i, [])) for i in mods])
+            bars = [list(hz["barriers"].get(i, [])) for i in mods]
+            hl = MS.HorizonLaunch([self.vocab_sizes[i] for i in mods], [cap] * len(mods),
+                                  [hz["is_percent"].get(i, False) for i in mods], hz["quantiles"],
+                                  [b + [1.0] * (nbar - len(b)) for b in bars])
+            houts = MS.horizon_outputs(len(mods), Bp, N, hl.nq, hl.nb, dev)
+            hvals = [hz["values"][i].to(dev) for i in mods]
+            for p, i in enumerate(mods):
+                hl.tok[p] = bufs[i].data_ptr() + 8 * n0
+                hl.origin[p], hl.origin_stride[p] = bufs[i].data_ptr() + 8 * (n0 - 1), cap
+                hl.values[p] = hvals[p].data_ptr()
+                (hl.stats[p], hl.qval[p], hl.qrow[p], hl.hit[p], hl.ess[p],
+                 hl.live[p]) = [x.data_ptr() if x.numel() else None for x in houts[p]]
+            hbytes = hl.scratch_bytes(L, Bp, Sp, N)
+            hscratch = torch.empty(max(hbytes, 16), dtype=torch.uint8, device=dev)
+            with torch.cuda.device(dev):
+                hl.run(L, ML.stream_ptr(dev), Bp, Sp, N, logw.data_ptr() if giv else 0, hscratch.data_ptr(), hbytes)
+            res_hz = {}
+            for p, i in enumerate(mods):
+                res_hz[i] = MS.horizon_dict(houts[p])
+                res_hz[i]["hit"] = res_hz[i]["hit"][..., :len(bars[p])]
+            out.append(res_hz)
         return out[0] if len(out) == 1 else tuple(out)
 
     @torch.no_grad()
