@@ -672,7 +672,10 @@ int mmt_op_mlp2(void* stream, int32_t M, int32_t C, const void* x, int32_t ldx, 
 /* its backward-data pair as ONE launch (the engine's backward path at C = 256 / 512; replaces
  * mmt_op_gemm(dtanh_bf16) + mmt_op_gemm(store_bf16)): dh[M, C/2] = bf16(alpha (dy[M, C] W2[C, C/2]) (1 - h^2))
  * with db0 (nullable) += its fp32 column sums, dx[M, C] = bf16(dh W0[C/2, C]); W2 / W0 are the forward
- * weights as stored ([C][C/2] / [C/2][C], row strides ldw2 / ldw0), h the forward's saved tanh output */
+ * weights as stored ([C][C/2] / [C/2][C], row strides ldw2 / ldw0), h the forward's saved tanh output.
+ * db0 sums the fp32 values alpha (dy W2) (1 - h^2) BEFORE their bf16 store, not the stored dh (the unfused pair's
+ * dtanh_bf16 epilogue sums the same fp32 values); dx is the product of the STORED bf16 dh. Pinned bit for bit by
+ * tests/test_gpu_exact_kernels.py test_mlp2_bwd_exact, on inputs where the two sums differ. */
 int mmt_op_mlp2_bwd(void* stream, int32_t M, int32_t C, const void* dy, int32_t lddy, const void* w2, int32_t ldw2,
                     const void* h, int32_t ldh, float alpha, const void* w0, int32_t ldw0, void* dh, int32_t lddh,
                     float* db0, void* dx);
