@@ -1,5 +1,5 @@
-"""generate's device path (temperature / top_k / top_p / seed / return_logprobs / logits_hook: model.py
-_generate_device over mmt_sample) on the f_small fixture (d64, T32, B4, V = [57, 13, 24, 5], cross-attention).
+"""generate's device path (temperature / top_k / top_p / seed / return_logprobs / logits_hook: mmt_rollout.py
+rollout_int over mmt_sample_multi) on the f_small fixture (d64, T32, B4, V = [57, 13, 24, 5], cross-attention).
 
 Tokens and log-probabilities are compared with the CPU restatement of the rule (tests/sampling_ref.py) on exactly
 the logits the sampler read (logits_hook), under the clear / ambiguous rule and the delta and log-probability bounds

@@ -1,4 +1,4 @@
-"""Joint rollouts of generate (model.py `_generate_joint`: a list of modalities or "all", `given=`), on the f_small
+"""Joint rollouts of generate (mmt_rollout.py `rollout`: a list of modalities or "all", `given=`), on the f_small
 fixture (d64, L2, T32, B4, V = [57, 13, 24, 5], cross-attention on modalities 0 and 2).
 
 The keying rule is checked as in tests/test_gpu_generate_device.py: the tokens and log-probabilities of modality i
@@ -200,6 +200,36 @@ def test_joint_greedy_cache_modes_and_the_int_form(peaked):
         old = m.generate(start, max_new_tokens=1, modality_to_generate=i,
                          sample_fn=lambda probs: probs.argmax(dim=-1, keepdim=True))
         assert torch.equal(old[i][:, 5], a[i][:, 5]), i
+
+
+@pytest.mark.parametrize("mode", ["cached", "cached_one_row", "reforward", "fanout", "tiled"])
+def test_int_form_is_a_list_of_one_under_the_seed_relation(small, mode):
+    """generate(modality_to_generate=g, seed=modality_seed(SEED, g)) and generate(modality_to_generate=[g], seed=SEED)
+    are the same rollout: every returned sequence equal, the log-probabilities equal as bit patterns. cached crosses
+    block_size (the prefill, decode steps and three re-forwards); one row takes the other row-stride branch."""
+    meta, idx, m = small
+    T, g = meta["block_size"], 2
+    B = {"cached_one_row": 1, "fanout": 2, "tiled": 2}.get(mode, idx[0].shape[0])
+    start = [t[:B, :5].cuda() for t in idx]
+    kw = dict(temperature=0.9, top_k=6, top_p=0.9, return_logprobs=True)
+    if mode in ("cached", "cached_one_row"):
+        kw.update(max_new_tokens=T + 3 - 5)
+    elif mode == "reforward":
+        kw.update(max_new_tokens=6, use_cache=False)
+    else:
+        kw.update(max_new_tokens=9, num_samples=3, use_cache=mode == "fanout")
+    m.last_generate_path = None
+    seqs, lp = m.generate(start, modality_to_generate=g, seed=MS.modality_seed(SEED, g), **kw)
+    path = m.last_generate_path
+    m.last_generate_path = None
+    seqs1, lps = m.generate(start, modality_to_generate=[g], seed=SEED, **kw)
+    assert path == m.last_generate_path == (mode if mode in ("fanout", "tiled") else None)
+    rows = B * kw.get("num_samples", 1)
+    assert len(seqs) == len(seqs1) == len(meta["V"]) and sorted(lps) == [g]
+    for a, b in zip(seqs, seqs1):
+        assert tuple(a.shape) == (rows, 5 + kw["max_new_tokens"]) and torch.equal(a, b)
+    assert tuple(lp.shape) == (rows, kw["max_new_tokens"]) and lp.dtype == torch.float32
+    assert torch.equal(lp.view(torch.int32), lps[g].view(torch.int32))
 
 
 def test_joint_fanout(small, peaked):

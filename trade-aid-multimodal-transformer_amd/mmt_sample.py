@@ -4,8 +4,8 @@
     tok = mmt_sample.sample(logits, temperature=0.8, top_k=50, top_p=0.9, seed=1234, pos=n)
     tok, lp = mmt_sample.sample(logits, ..., return_logprobs=True)
 
-`model.generate(..., temperature=..., top_k=..., top_p=..., seed=...)` runs on `launch` below; `sample` is the
-same entry for users with their own decode loop. The rule is stated in include/mmt.h and INTEGRATION.md.
+`model.generate(..., temperature=..., top_k=..., top_p=..., seed=...)` runs on `MultiLaunch` below (one problem:
+bit for bit mmt_sample); `sample` is the entry for users with their own decode loop. The rule is stated in include/mmt.h and INTEGRATION.md.
 
 Several heads of one step in one launch (mmt_sample_multi), as the joint rollouts of generate use it:
 
@@ -142,6 +142,14 @@ class MultiLaunch:
             raise ML.MmtError(f"mmt_sample_multi failed (status {rc})")
 
 
+def bind_view(launch, p, view, rows):
+    """Point problem p of a launch object (MultiLaunch, ScoreLaunch, ForecastLaunch) at a [rows, V_p] logits view:
+    its address and its row stride in elements (V_p for one row, whatever the view's stride says)."""
+    V = int(launch.V[p])
+    launch.logits[p] = view.data_ptr()
+    launch.row_stride[p] = max(int(view.stride(0)), V) if rows > 1 else V
+
+
 def _per_problem(value, P, name):
     if isinstance(value, (list, tuple)):
         if len(value) != P:
@@ -176,8 +184,7 @@ def sample_multi(logits_list, *, temperature=1.0, top_k=0, top_p=1.0, seeds, pos
     lps = [torch.empty(B, dtype=torch.float32, device=dev) for _ in range(P)] if return_logprobs else None
     ml = MultiLaunch([lg.shape[1] for lg in logits_list], settings, seeds, [1] * P, [1] * P)
     for p, lg in enumerate(logits_list):
-        ml.logits[p] = lg.data_ptr()
-        ml.row_stride[p] = max(int(lg.stride(0)), lg.shape[1]) if B > 1 else lg.shape[1]
+        bind_view(ml, p, lg, B)
         ml.tok[p] = toks[p].data_ptr()
         ml.logprob[p] = lps[p].data_ptr() if lps is not None else None
     with torch.cuda.device(dev):
@@ -236,8 +243,7 @@ def score_multi(logits_list, tokens_list):
     lps = [torch.empty(B, dtype=torch.float32, device=dev) for _ in range(P)]
     sl = ScoreLaunch([lg.shape[1] for lg in logits_list], [max(int(tk.stride(0)), 1) for tk in tokens_list], [1] * P)
     for p, (lg, tk) in enumerate(zip(logits_list, tokens_list)):
-        sl.logits[p] = lg.data_ptr()
-        sl.row_stride[p] = max(int(lg.stride(0)), lg.shape[1]) if B > 1 else lg.shape[1]
+        bind_view(sl, p, lg, B)
         sl.tok[p] = tk.data_ptr()
         sl.logprob[p] = lps[p].data_ptr()
     with torch.cuda.device(dev):
@@ -345,8 +351,7 @@ def forecast_multi(logits_list, *, samples, temperature=1.0, top_k=0, top_p=1.0,
     fl = ForecastLaunch([lg.shape[1] for lg in logits_list], settings, [lg.shape[1] for lg in logits_list],
                         [lp.data_ptr() for lp in logprobs], [max(int(lp.stride(0)), N) for lp in logprobs])
     for p, lg in enumerate(logits_list):
-        fl.logits[p] = lg.data_ptr()
-        fl.row_stride[p] = max(int(lg.stride(0)), lg.shape[1]) if R > 1 else lg.shape[1]
+        bind_view(fl, p, lg, R)
         fl.pmf[p], fl.ess[p], fl.live[p] = pmfs[p].data_ptr(), ess[p].data_ptr(), live[p].data_ptr()
     L = ML.lib()
     nbytes = fl.scratch_bytes(L, B, S)

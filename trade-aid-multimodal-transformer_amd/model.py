@@ -33,229 +33,12 @@ import torch
 import torch.nn as nn
 
 import mmt_lib as ML
+import mmt_rollout as MR
 from config_utils import (_get_block_size, _get_deterministic, _get_dropout, _get_n_embd, _get_n_head, _get_n_layer,
                           _get_precision)
-
-
-def check_num_samples(num_samples):
-    """generate's num_samples: an integer >= 1 (a bool is none)."""
-    if isinstance(num_samples, bool) or not isinstance(num_samples, int) or num_samples < 1:
-        raise ValueError(f"generate: num_samples must be an integer >= 1 or None, got {num_samples!r}")
-    return num_samples
-
-
-def tile_prompts(idx_list, num_samples):
-    """The row order of generate(num_samples=S): row b*S + s of every returned tensor is sample s of prompt b,
-    i.e. each prompt repeated S times in place."""
-    return [p.repeat_interleave(num_samples, 0) for p in idx_list]
-
-
-GENERATED, GIVEN, HELD = "generated", "given", "held"
-
-
-class JointPlan:
-    """What plan_joint returns for the list form of generate: `roles[i]` in (GENERATED, GIVEN, HELD), `generated`
-    the generated modalities in ascending order, `given` {modality: the caller's int64 tensor}, and the checked
-    shape: B prompts of n0 tokens, N new tokens. `evidence` is None, "weights" or "resample", with it
-    `resample_every`, `ess_threshold` and `points`, the new-token indices j after whose sampling the paths are
-    resampled (resample_points; empty unless evidence == "resample")."""
-
-    def __init__(self, roles, generated, given, B, n0, N, evidence=None, resample_every=1, ess_threshold=0.5):
-        self.roles, self.generated, self.given, self.B, self.n0, self.N = roles, generated, given, B, n0, N
-        self.evidence, self.resample_every, self.ess_threshold = evidence, resample_every, ess_threshold
-        self.points = resample_points(N, resample_every) if evidence == "resample" else []
-        self.forecast = None  # check_forecast's result: the forecast settings, None when off
-        self.horizon = None  # check_horizon's result: the horizon settings, None when off
-
-
-EVIDENCE_MODES = (None, "weights", "resample")
-
-
-def resample_points(N, resample_every):
-    """The fixed schedule of generate(evidence="resample"): the paths are resampled after the sampling of new token
-    j whenever (j + 1) % resample_every == 0 and j < N - 1 (after the last token nothing is left to steer)."""
-    return [j for j in range(N - 1) if (j + 1) % resample_every == 0]
-
-
-DEFAULT_QUANTILES = (0.05, 0.5, 0.95)
-
-
-def check_forecast(forecast, generated, vocab_sizes):
-    """generate's forecast= for the generated modalities: None / False (off), True, or a dict with the optional keys
-    "quantiles" (at most 16 levels in (0, 1)), "values" {i: V_i non-decreasing numbers} and "is_percent" {i: bool},
-    i generated. Returns None or {"quantiles": [floats], "values": {i: CPU fp64 [V_i]}, "is_percent": {i: bool}};
-    ValueError for anything else (checked on the host, once)."""
-    import mmt_sample as MS
-    if forecast is None or forecast is False:
-        return None
-    if forecast is True:
-        forecast = {}
-    if not isinstance(forecast, dict):
-        raise ValueError(f"generate: forecast must be True or a dict, got {forecast!r}")
-    for k in forecast:
-        if k not in ("quantiles", "values", "is_percent"):
-            raise ValueError(f"generate: forecast has no key {k!r} (quantiles, values, is_percent)")
-    out = {"quantiles": MS.check_quantiles(forecast.get("quantiles", DEFAULT_QUANTILES)), "values": {},
-           "is_percent": {}}
-    for name in ("values", "is_percent"):
-        d = forecast.get(name) or {}
-        if not isinstance(d, dict):
-            raise ValueError(f"generate: forecast[{name!r}] must be a dict {{modality: ...}}")
-        for i, x in d.items():
-            if i not in generated:
-                raise ValueError(f"generate: forecast[{name!r}] names modality {i!r}, which is not generated")
-            out[name][i] = (MS.check_values(x, vocab_sizes[i], f"forecast['values'][{i}]") if name == "values"
-                            else bool(x))
-    return out
-
-
-def check_horizon(horizon, generated, vocab_sizes, forecast=None):
-    """generate's horizon= for the generated modalities: None / False (off), True, or a dict with the optional keys
-    "quantiles" (at most 16 levels in (0, 1)), "values" {i: V_i non-decreasing numbers}, "is_percent" {i: bool} and
-    "barriers" {i: at most 8 finite non-zero numbers}, i generated. values and is_percent default to those of
-    `forecast` (check_forecast's result) where it is given. Returns None or {"quantiles", "values" {i: CPU fp64 [V_i]},
-    "is_percent" {i: bool}, "barriers" {i: [floats]}, "modalities": the generated modalities with values, ascending};
-    ValueError for anything else, and when no generated modality has values (a horizon has no meaning on token
-    indices)."""
-    import mmt_sample as MS
-    if horizon is None or horizon is False:
-        return None
-    if horizon is True:
-        horizon = {}
-    if not isinstance(horizon, dict):
-        raise ValueError(f"generate: horizon must be True or a dict, got {horizon!r}")
-    for k in horizon:
-        if k not in ("quantiles", "values", "is_percent", "barriers"):
-            raise ValueError(f"generate: horizon has no key {k!r} (quantiles, values, is_percent, barriers)")
-    out = {"quantiles": MS.check_quantiles(horizon.get("quantiles", DEFAULT_QUANTILES)),
-           "values": dict(forecast["values"]) if forecast else {},
-           "is_percent": dict(forecast["is_percent"]) if forecast else {}, "barriers": {}}
-    for name in ("values", "is_percent", "barriers"):
-        d = horizon.get(name) or {}
-        if not isinstance(d, dict):
-            raise ValueError(f"generate: horizon[{name!r}] must be a dict {{modality: ...}}")
-        for i, x in d.items():
-            if i not in generated:
-                raise ValueError(f"generate: horizon[{name!r}] names modality {i!r}, which is not generated")
-            out[name][i] = (MS.check_values(x, vocab_sizes[i], f"horizon['values'][{i}]") if name == "values"
-                            else MS.check_barriers(x) if name == "barriers" else bool(x))
-    out["modalities"] = [i for i in generated if i in out["values"]]
-    if not out["modalities"]:
-        raise ValueError("generate: horizon= needs the values of a generated modality (horizon={\"values\": {i: ...}} "
-                         "or forecast's): a horizon has no meaning on token indices")
-    return out
-
-
-def plan_joint(modality_to_generate, given, vocab_sizes, prompt_shapes, max_new_tokens, num_samples=None,
-               evidence=None, resample_every=1, ess_threshold=0.5, forecast=None, horizon=None):
-    """generate's `modality_to_generate` and `given` as per-modality roles, every refusal of the list form that
-    needs no device in one place. An int (the int form: one modality sampled, generate as it always ran) returns
-    None, and refuses `given`. A sequence of distinct ints, even of one, or "all" is the list form (a joint
-    rollout): those modalities are GENERATED, the keys of `given` are GIVEN (tokens supplied by the caller,
-    int64 [B, N] or [B * num_samples, N] with N = max_new_tokens), every other modality is HELD at its last prompt
-    token. ValueError for: a modality named twice, out of range or not an int; an empty list; a modality both
-    generated and given; a given tensor of another dtype or shape, or with a token outside 0..V_i - 1; a wrong
-    number of prompts; prompts that are not [B, n0 >= 1] of one shape (the reference's pad / crop rule is defined
-    around one generated modality). `evidence` ("weights" or "resample": the importance weights of the given series,
-    generate's docstring) is refused without a given modality, with an unknown value, with resample_every < 1
-    or no integer, with a negative or NaN ess_threshold, and as "resample" without num_samples. `horizon`
-    (check_horizon) is refused in the int form and with num_samples > 4096 (the paths of a prompt are sorted on
-    chip)."""
-    M = len(vocab_sizes)
-    g = modality_to_generate
-    if evidence not in EVIDENCE_MODES:
-        raise ValueError(f"generate: evidence must be None, \"weights\" or \"resample\", got {evidence!r}")
-    if evidence is not None:
-        if not given:
-            raise ValueError("generate: evidence= needs a given modality (given={modality: tokens}): the weights are "
-                             "the probabilities of the given tokens")
-        if isinstance(resample_every, bool) or not isinstance(resample_every, int) or resample_every < 1:
-            raise ValueError(f"generate: resample_every must be an integer >= 1, got {resample_every!r}")
-        try:
-            thr_ok = float(ess_threshold) >= 0.0
-        except (TypeError, ValueError):
-            thr_ok = False
-        if not thr_ok:
-            raise ValueError(f"generate: ess_threshold must be a number >= 0, got {ess_threshold!r}")
-        if evidence == "resample" and num_samples is None:
-            raise ValueError("generate: evidence=\"resample\" resamples the num_samples paths of each prompt: pass "
-                             "num_samples")
-    if isinstance(g, int) and not isinstance(g, bool):
-        if given is not None:
-            raise ValueError("generate: given= needs the list form of modality_to_generate (a sequence or \"all\")")
-        if forecast is not None and forecast is not False:
-            raise ValueError(f"generate: forecast= needs the list form of modality_to_generate: pass [{g}] (a "
-                             "sequence, even of one, or \"all\")")
-        if horizon is not None and horizon is not False:
-            raise ValueError(f"generate: horizon= needs the list form of modality_to_generate: pass [{g}] (a "
-                             "sequence, even of one, or \"all\")")
-        return None
-    if isinstance(g, str):
-        if g != "all":
-            raise ValueError(f"generate: modality_to_generate must be an int, a sequence of ints or \"all\", got {g!r}")
-        gen = list(range(M))
-    else:
-        try:
-            gen = list(g)
-        except TypeError:
-            raise ValueError(f"generate: modality_to_generate must be an int, a sequence of ints or \"all\", "
-                             f"got {g!r}") from None
-    for i in gen:
-        if isinstance(i, bool) or not isinstance(i, int) or not 0 <= i < M:
-            raise ValueError(f"generate: modality_to_generate names {i!r}; modalities are the ints 0..{M - 1}")
-    if len(set(gen)) != len(gen):
-        raise ValueError(f"generate: modality_to_generate names a modality twice: {gen}")
-    if not gen:
-        raise ValueError("generate: modality_to_generate is empty")
-    N = int(max_new_tokens)
-    if N < 0:
-        raise ValueError(f"generate: max_new_tokens must be >= 0, got {max_new_tokens!r}")
-    shapes = [tuple(int(x) for x in s) for s in prompt_shapes]
-    if len(shapes) != M:
-        raise ValueError(f"expected {M} index tensors, got {len(shapes)}")
-    if any(len(s) != 2 for s in shapes) or len(set(shapes)) != 1:
-        raise ValueError(f"generate: a joint rollout needs [B, n0] prompts of one shape, got {shapes}")
-    B, n0 = shapes[0]
-    if n0 < 1:
-        raise ValueError("generate: the prompt must hold at least one token")
-    given = {} if given is None else given
-    if not isinstance(given, dict):
-        raise ValueError("generate: given must be a dict {modality: int64 [B, N] tokens}")
-    rows = (B,) if num_samples is None else (B, B * num_samples)
-    for i, t in given.items():
-        if isinstance(i, bool) or not isinstance(i, int) or not 0 <= i < M:
-            raise ValueError(f"generate: given names {i!r}; modalities are the ints 0..{M - 1}")
-        if i in gen:
-            raise ValueError(f"generate: modality {i} is both generated and given")
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.long:
-            raise ValueError(f"generate: given[{i}] must be an int64 tensor")
-        if t.dim() != 2 or t.shape[1] != N or t.shape[0] not in rows:
-            raise ValueError(f"generate: given[{i}] must be [{' or '.join(str(r) for r in rows)}, {N}], "
-                             f"got {tuple(t.shape)}")
-        if t.numel() and (int(t.min()) < 0 or int(t.max()) >= vocab_sizes[i]):
-            raise ValueError(f"generate: given[{i}] holds tokens outside 0..{vocab_sizes[i] - 1}")
-    roles = [GENERATED if i in gen else GIVEN if i in given else HELD for i in range(M)]
-    plan = JointPlan(roles, sorted(gen), dict(given), B, n0, N, evidence, resample_every,
-                     0.5 if evidence is None else float(ess_threshold))
-    plan.forecast = check_forecast(forecast, plan.generated, vocab_sizes)
-    plan.horizon = check_horizon(horizon, plan.generated, vocab_sizes, plan.forecast)
-    if plan.horizon is not None and num_samples is not None:
-        import mmt_sample as MS
-        if num_samples > MS.HORIZON_MAX_SAMPLES:
-            raise ValueError(f"generate: horizon= sorts at most {MS.HORIZON_MAX_SAMPLES} samples per prompt, got "
-                             f"num_samples={num_samples}")
-    return plan
-
-
-def joint_setting(value, generated, name):
-    """A sampling setting of the list form per generated modality: a scalar (or None) for all, or a dict
-    {modality: value} whose keys are generated modalities (the others take the default)."""
-    if not isinstance(value, dict):
-        return {i: value for i in generated}
-    for i in value:
-        if i not in generated:
-            raise ValueError(f"generate: {name} names modality {i!r}, which is not generated")
-    return {i: value.get(i) for i in generated}
+from mmt_rollout import (DEFAULT_QUANTILES, EVIDENCE_MODES, GENERATED, GIVEN, HELD, JointPlan,  # noqa: F401
+                         check_forecast, check_horizon, check_num_samples, joint_setting, plan_joint, resample_points,
+                         tile_prompts)
 
 
 class _MmtStep(torch.autograd.Function):
@@ -732,7 +515,7 @@ class MultimodalTransformer(nn.Module):
         forward GEMMs the bf16 decode would not reproduce) always re-runs the forward.
 
         Any of the keywords temperature / top_k / top_p / seed / return_logprobs / logits_hook selects the
-        device path (`_generate_device`; the rule of mmt_sample in include/mmt.h): sampling
+        device path (mmt_rollout.py; the rule of mmt_sample in include/mmt.h): sampling
         on the device with draws keyed by (seed, row, position), no torch generator consumed, and with
         return_logprobs=True the return value (sequences, logprobs fp32 [B, max_new_tokens]). Without them
         the body below runs as before.
@@ -740,13 +523,12 @@ class MultimodalTransformer(nn.Module):
         num_samples=S (an integer >= 1; it selects the device path too) returns S continuations of every prompt:
         what generate([p.repeat_interleave(S, 0) for p in prompts], ...) returns, row b*S + s being sample s of
         prompt b with its draw at position n keyed by (seed, b*S + s, n), but from ONE prefill over the B prompts
-        and decode steps over B*S rows that share each prompt's keys / values (`_generate_fanout`,
-        mmt_decode_fanout_step). That engine runs with use_cache, in eval mode or without dropout, at bf16, for
+        and decode steps over B*S rows that share each prompt's keys / values (mmt_decode_fanout_step). That engine runs with use_cache, in eval mode or without dropout, at bf16, for
         prompts of one length n0 >= 1 with n0 + max_new_tokens <= block_size; otherwise the prompts are tiled and
         the device path runs as without the keyword. `last_generate_path` says which ran: "fanout" or "tiled".
 
         Joint rollouts: modality_to_generate as a sequence of distinct ints (even of one) or "all" samples each of
-        those modalities per step from its own head and feeds them back together (`_generate_joint`, always the
+        those modalities per step from its own head and feeds them back together (always the
         device path: one decode step and one mmt_sample_multi per token). The draw of modality i, row r, position n
         is mmt_sample's with the seed mmt_sample.modality_seed(seed, i), whatever else is generated. given={i:
         int64 [B, N] or [B * S, N]} makes modality i follow the caller's tokens (a scenario, or a series known in
@@ -825,495 +607,18 @@ class MultimodalTransformer(nn.Module):
             if sample_fn is not None:
                 raise ValueError("generate: sample_fn cannot be combined with a joint rollout (a list of modalities "
                                  "or \"all\"): it samples on the GPU")
-            return self._generate_joint(idx_list, plan, use_cache, temperature, top_k, top_p, seed, return_logprobs,
-                                        logits_hook, num_samples)
+            return MR.rollout(self, idx_list, plan, use_cache, temperature, top_k, top_p, seed, return_logprobs,
+                              logits_hook, num_samples)
         if not (temperature is None and top_k is None and top_p is None and seed is None and not return_logprobs
                 and logits_hook is None and num_samples is None):
             if sample_fn is not None:
                 raise ValueError("generate: sample_fn cannot be combined with temperature / top_k / top_p / seed / "
                                  "return_logprobs / logits_hook / num_samples (the device path samples on the GPU)")
-            if num_samples is not None:
-                return self._generate_samples(idx_list, max_new_tokens, modality_to_generate, use_cache, temperature,
-                                              top_k, top_p, seed, return_logprobs, logits_hook, num_samples)
-            return self._generate_device(idx_list, max_new_tokens, modality_to_generate, use_cache, temperature, top_k,
-                                         top_p, seed, return_logprobs, logits_hook)
-        seqs = [idx.clone() for idx in idx_list]
-        T = self.block_size
-        g = modality_to_generate
+            return MR.rollout_int(self, idx_list, max_new_tokens, modality_to_generate, use_cache, temperature, top_k,
+                                  top_p, seed, return_logprobs, logits_hook, num_samples)
         sample = sample_fn or (lambda probs: torch.multinomial(probs, num_samples=1))
-        cache = (use_cache and not (self.training and self.dropout_p > 0.0) and self.precision == "bf16"
-                 and len({int(s.shape[1]) for s in seqs}) == 1 and all(s.dim() == 2 for s in seqs))
-        cached_pos = None  # the last position whose keys / values the workspace holds
-        for _ in range(max_new_tokens):
-            n = seqs[g].shape[1]
-            if cache and cached_pos is not None and n - 1 == cached_pos + 1 and n <= T:
-                last = self._decode_step([s[:, n - 1] for s in seqs], n - 1)[g]
-                cached_pos = n - 1
-            else:
-                cond = [s[:, -T:] for s in seqs]
-                logits, _ = self(cond)
-                last = logits[g][:, -1, :]
-                cached_pos = n - 1 if (cache and n <= T) else None
-            probs = torch.softmax(last, dim=-1)
-            nxt = sample(probs).to(seqs[g].dtype)
-            seqs[g] = torch.cat((seqs[g].to(nxt.device), nxt), dim=1)
-            n = seqs[g].shape[1]
-            for i in range(self.num_modalities):
-                if i == g:
-                    continue
-                if seqs[i].shape[1] < n:
-                    seqs[i] = torch.cat((seqs[i], seqs[i][:, -1:]), dim=1)
-                elif seqs[i].shape[1] > n:
-                    seqs[i] = seqs[i][:, :n]
-        return seqs
-
-    @torch.no_grad()
-    def _generate_device(self, idx_list, max_new_tokens, g, use_cache, temperature, top_k, top_p, seed,
-                         return_logprobs, logits_hook):
-        """generate with the sampling on the device (mmt_sample, include/mmt.h). The sequences live in
-        preallocated [B, n0 + max_new_tokens] buffers, the other modalities' pad with their last token is
-        written once before the loop (what the reference's pad / crop rule amounts to for prompts of one
-        length), the sampler writes column n of the target modality's buffer and the compact [B] token buffer
-        the next decode step reads, and the logits buffers and pointer arrays of the decode steps are made
-        once. Per token the host issues mmt_decode_step and mmt_sample, nothing else: no torch op, no sync.
-        Past block_size, with use_cache=False, in training mode with dropout and at fp8 a step is the
-        re-forward over the cropped context (the cache rule of the default path) and mmt_sample on the last
-        position of its logits, read in place. The draw of row b at sequence position n is keyed by
-        (seed, b, n): the same seed and the same logits give the same tokens whatever the cache mode and
-        whatever else is in the batch. seed=None takes one from the device generator (never torch's CPU
-        generator). `logits_hook(n, logits_BV)` sees the [B, V] view the sampler is about to read (the decode
-        steps reuse one buffer: clone it to keep it). Prompts of unequal lengths run the reference's loop with
-        the same sampler."""
-        import mmt_sample as MS
-        t, k, p = MS.check_settings(temperature, top_k, top_p)
-        flat = self.flat_params
-        dev = flat.device
-        M, T, N = self.num_modalities, self.block_size, int(max_new_tokens)
-        if len(idx_list) != M:
-            raise ValueError(f"expected {M} index tensors, got {len(idx_list)}")
-        if not 0 <= g < M:
-            raise ValueError(f"modality_to_generate must be 0..{M - 1}, got {g}")
-        if dev.type != "cuda":
-            raise RuntimeError("MultimodalTransformer (libmmt_hip) runs only on a ROCm GPU: call .to('cuda') "
-                               "(there is no CPU path)")
-        seed = MS.device_seed(dev) if seed is None else int(seed) & MS.MASK64
-        V = self.vocab_sizes[g]
-        B = idx_list[0].shape[0]
-        prompts = [s.to(device=dev, dtype=torch.long) for s in idx_list]
-        lp = torch.empty(B, max(N, 0), dtype=torch.float32, device=dev) if return_logprobs else None
-        L = ML.lib()
-        if len({int(s.shape[1]) for s in prompts}) != 1 or any(s.dim() != 2 for s in prompts):
-            # unequal prompt lengths: the reference's loop (re-forward, pad / crop per step) around the sampler
-            seqs = [s.clone() for s in prompts]
-            for j in range(N):
-                n = seqs[g].shape[1]
-                logits, _ = self([s[:, -T:] for s in seqs])
-                last = logits[g][:, -1, :]
-                if logits_hook is not None:
-                    logits_hook(n, last)
-                nxt, l = MS.sample(last, temperature=t, top_k=k, top_p=p, seed=seed, pos=n, return_logprobs=True)
-                if lp is not None:
-                    lp[:, j] = l
-                seqs[g] = torch.cat((seqs[g], nxt[:, None]), dim=1)
-                for i in range(M):
-                    if i != g and seqs[i].shape[1] < n + 1:
-                        seqs[i] = torch.cat((seqs[i], seqs[i][:, -1:]), dim=1)
-                    elif i != g and seqs[i].shape[1] > n + 1:
-                        seqs[i] = seqs[i][:, :n + 1]
-            seqs = [s.to(idx_list[i].dtype) for i, s in enumerate(seqs)]
-            return (seqs, lp) if return_logprobs else seqs
-        n0 = int(prompts[0].shape[1])
-        if n0 < 1:
-            raise ValueError("generate: the prompt must hold at least one token")
-        cap = n0 + N
-        bufs = []
-        for i, s in enumerate(prompts):
-            buf = torch.zeros(B, cap, dtype=torch.long, device=dev)
-            buf[:, :n0] = s
-            if i != g and N > 0:
-                buf[:, n0:] = s[:, -1:]
-            bufs.append(buf)
-        compact = torch.zeros(B, dtype=torch.long, device=dev)
-        cache = use_cache and not (self.training and self.dropout_p > 0.0) and self.precision == "bf16"
-        cached_pos = None  # the last position whose keys / values the workspace holds
-        dec = None  # (token pointers, logits pointers, logits buffers, workspace pointer) of the decode steps
-        tok_base, lp_base = bufs[g].data_ptr(), (lp.data_ptr() if lp is not None else 0)
-        with torch.cuda.device(dev):
-            stream = ML.stream_ptr(dev)
-            for j in range(N):
-                n = n0 + j
-                if cache and cached_pos is not None and n - 1 == cached_pos + 1 and n <= T:
-                    if dec is None:
-                        dec_idx = [compact if i == g else prompts[i][:, -1].contiguous() for i in range(M)]
-                        dec_logits = [torch.empty(B, Vi, dtype=torch.float32, device=dev) for Vi in self.vocab_sizes]
-                        dec = (ML.ptr_array(dec_idx), ML.ptr_array(dec_logits), dec_logits, ML.ptr(self._ws), dec_idx,
-                               ML.ptr(flat))
-                    rc = L.mmt_decode_step(self._ctx, stream, B, n - 1, dec[0], dec[5], dec[1], dec[3])
-                    ML.check(rc, self._ctx, "mmt_decode_step")
-                    self._gen += 1
-                    cached_pos = n - 1
-                    last = dec[2][g]
-                else:
-                    logits, _ = self([buf[:, max(0, n - T):n] for buf in bufs])
-                    last = logits[g][:, -1, :]
-                    cached_pos = n - 1 if (cache and n <= T) else None
-                if logits_hook is not None:
-                    logits_hook(n, last)
-                MS.launch(L, stream, B, V, last.data_ptr(), int(last.stride(0)) if B > 1 else V, t, k, p, seed, 0, n,
-                          tok_base + 8 * n, cap, compact.data_ptr(), lp_base + 4 * j if lp_base else 0, N)
-        seqs = [buf.to(idx_list[i].dtype) for i, buf in enumerate(bufs)]
-        return (seqs, lp) if return_logprobs else seqs
-
-    @torch.no_grad()
-    def _generate_samples(self, idx_list, max_new_tokens, g, use_cache, temperature, top_k, top_p, seed,
-                          return_logprobs, logits_hook, S):
-        """generate(num_samples=S): the fan-out engine where it applies (the conditions in generate's docstring),
-        else the device path over the tiled prompts, which is the definition of the result."""
-        N, T = int(max_new_tokens), self.block_size
-        shapes = [tuple(s.shape) for s in idx_list]
-        fan = (use_cache and not (self.training and self.dropout_p > 0.0) and self.precision == "bf16"
-               and len(idx_list) == self.num_modalities and 0 <= g < self.num_modalities
-               and all(len(sh) == 2 for sh in shapes) and len(set(shapes)) == 1 and shapes[0][1] >= 1
-               and shapes[0][1] + N <= T and N >= 1 and self.flat_params.device.type == "cuda")
-        if not fan:
-            self.last_generate_path = "tiled"
-            return self._generate_device(tile_prompts(idx_list, S), max_new_tokens, g, use_cache, temperature, top_k,
-                                         top_p, seed, return_logprobs, logits_hook)
-        self.last_generate_path = "fanout"
-        return self._generate_fanout(idx_list, N, g, temperature, top_k, top_p, seed, return_logprobs, logits_hook, S)
-
-    @torch.no_grad()
-    def _generate_fanout(self, idx_list, N, g, temperature, top_k, top_p, seed, return_logprobs, logits_hook, S):
-        """S samples per prompt from one prefill (mmt_decode_fanout_step, include/mmt.h). The prefill runs over the
-        B prompts; its last-position logits, one row per prompt, are expanded to [B*S, V] once and sampled in one
-        mmt_sample launch (row r = b*S + s, position n0). From then on a token costs one fan-out decode step over
-        B*S rows, which reads the prompts' keys / values from the prefill's workspace and keeps the samples' own in
-        the fan buffer, and one mmt_sample launch: no torch op, no sync. Buffers as in `_generate_device`, with
-        B*S rows."""
-        import mmt_sample as MS
-        t, k, p = MS.check_settings(temperature, top_k, top_p)
-        flat = self.flat_params
-        dev = flat.device
-        M = self.num_modalities
-        seed = MS.device_seed(dev) if seed is None else int(seed) & MS.MASK64
-        V = self.vocab_sizes[g]
-        prompts = [s.to(device=dev, dtype=torch.long).contiguous() for s in idx_list]
-        B, n0 = prompts[0].shape
-        R, cap = B * S, n0 + N
-        L = ML.lib()
-        nbytes = L.mmt_fanout_bytes(self._ctx, B, S, N)
-        if nbytes < 0:
-            raise ValueError(f"generate: {B} prompts x {S} samples are more rows than the decode launches address")
-        bufs = []
-        for i, s in enumerate(tile_prompts(prompts, S)):
-            buf = torch.zeros(R, cap, dtype=torch.long, device=dev)
-            buf[:, :n0] = s
-            if i != g:
-                buf[:, n0:] = s[:, -1:]
-            bufs.append(buf)
-        lp = torch.empty(R, N, dtype=torch.float32, device=dev) if return_logprobs else None
-        compact = torch.zeros(R, dtype=torch.long, device=dev)
-        tok_base, lp_base = bufs[g].data_ptr(), (lp.data_ptr() if lp is not None else 0)
-        logits, _ = self(prompts)  # the prefill: leaves every prompt position's keys / values in the workspace
-        rows = torch.arange(B, device=dev).repeat_interleave(S)
-        first = logits[g][:, -1, :].index_select(0, rows)  # [B*S, V]: each sample's copy of its prompt's row
-        fan = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        dec_idx = [compact if i == g else bufs[i][:, n0 - 1].contiguous() for i in range(M)]
-        dec_logits = [torch.empty(R, Vi, dtype=torch.float32, device=dev) for Vi in self.vocab_sizes]
-        p_idx, p_logits, p_flat, p_ws, p_fan = (ML.ptr_array(dec_idx), ML.ptr_array(dec_logits), ML.ptr(flat),
-                                                ML.ptr(self._ws), ML.ptr(fan))
-        with torch.cuda.device(dev):
-            stream = ML.stream_ptr(dev)
-            for j in range(N):
-                n = n0 + j
-                if j == 0:
-                    last = first
-                else:
-                    rc = L.mmt_decode_fanout_step(self._ctx, stream, B, S, n0, N, n - 1, p_idx, p_flat, p_logits, p_ws,
-                                                  p_fan)
-                    ML.check(rc, self._ctx, "mmt_decode_fanout_step")
-                    last = dec_logits[g]
-                if logits_hook is not None:
-                    logits_hook(n, last)
-                MS.launch(L, stream, R, V, last.data_ptr(), V, t, k, p, seed, 0, n, tok_base + 8 * n, cap,
-                          compact.data_ptr(), lp_base + 4 * j if lp_base else 0, N)
-        seqs = [buf.to(idx_list[i].dtype) for i, buf in enumerate(bufs)]
-        return (seqs, lp) if return_logprobs else seqs
-
-    @torch.no_grad()
-    def _generate_joint(self, idx_list, plan, use_cache, temperature, top_k, top_p, seed, return_logprobs,
-                        logits_hook, S):
-        """The list form of generate (a joint rollout): every GENERATED modality is sampled per step from its own
-        head, all of them in one mmt_sample_multi launch, modality i with the seed modality_seed(seed, i); GIVEN
-        modalities follow the caller's tokens; HELD ones stay at their last prompt token. Sequence buffers as in
-        `_generate_device`, given columns and held pads written once before the loop, one compact [rows] buffer per
-        generated modality. The decode step's idx[i] points at that compact buffer, at the held token, or at row j
-        of a [N, rows] transposed copy of the given tokens: the engine reads the pointer array on the host per
-        call, so the host moves a pointer and no kernel copies a token. Per token the host issues one decode step
-        (with num_samples under the fan-out conditions of `_generate_samples`: one fan-out step over B*S rows) and
-        one mmt_sample_multi: no torch op, no sync. Past block_size, with use_cache=False, in training mode with
-        dropout and at fp8 a step is the re-forward over the cropped buffers, and each problem reads its
-        modality's last-position logits in place. With plan.evidence a step also issues one mmt_score_multi over
-        the given modalities' views and the given tokens of column n, which the sequence buffers hold; "resample"
-        adds, at the plan's points, mmt_resample, an index_select of every per-row buffer and mmt_fanout_gather
-        into the second fan buffer; a closing mmt_resample folds the remaining columns. With plan.forecast a step
-        also issues one mmt_forecast_multi over the generated modalities' views, after the sampling and scoring and
-        before a resampling, into column j of preallocated [Bp, N, V_i] buffers; one mmt_pmf_stats follows the loop.
-        With plan.horizon one mmt_horizon_stats follows the loop too, over the sequence buffers' new columns."""
-        import mmt_sample as MS
-        flat = self.flat_params
-        dev = flat.device
-        M, T, N, n0, gen = self.num_modalities, self.block_size, plan.N, plan.n0, plan.generated
-        ts, ks, ps = (joint_setting(temperature, gen, "temperature"), joint_setting(top_k, gen, "top_k"),
-                      joint_setting(top_p, gen, "top_p"))
-        settings = [MS.check_settings(ts[i], ks[i], ps[i]) for i in gen]
-        if dev.type != "cuda":
-            raise RuntimeError("MultimodalTransformer (libmmt_hip) runs only on a ROCm GPU: call .to('cuda') "
-                               "(there is no CPU path)")
-        seed = MS.device_seed(dev) if seed is None else int(seed) & MS.MASK64
-        L = ML.lib()
-        cache = use_cache and not (self.training and self.dropout_p > 0.0) and self.precision == "bf16"
-        fan = S is not None and cache and n0 + N <= T and N >= 1
-        nbytes = L.mmt_fanout_bytes(self._ctx, plan.B, S, N) if fan else 0
-        if nbytes < 0:
-            raise ValueError(f"generate: {plan.B} prompts x {S} samples are more rows than the decode launches address")
-        if plan.evidence == "resample" and not (fan and S <= MS.RESAMPLE_MAX_SAMPLES):
-            raise ValueError(
-                "generate: evidence=\"resample\" runs on the fan-out engine only: it needs num_samples (at most "
-                f"{MS.RESAMPLE_MAX_SAMPLES}), use_cache, eval mode or no dropout, precision bf16, max_new_tokens >= 1 and "
-                "n0 + max_new_tokens <= block_size")
-        if plan.evidence is not None and S is not None and S > MS.RESAMPLE_MAX_SAMPLES:
-            raise ValueError(f"generate: evidence= folds the weights of at most {MS.RESAMPLE_MAX_SAMPLES} samples per "
-                             f"prompt, got num_samples={S}")
-        if S is not None:
-            self.last_generate_path = "fanout" if fan else "tiled"
-        prompts = [s.to(device=dev, dtype=torch.long).contiguous() for s in idx_list]
-        rows = prompts if S is None else tile_prompts(prompts, S)
-        R, cap = rows[0].shape[0], n0 + N
-        bufs, steps = [], {}
-        for i, s in enumerate(rows):
-            buf = torch.zeros(R, cap, dtype=torch.long, device=dev)
-            buf[:, :n0] = s
-            if plan.roles[i] == GIVEN and N > 0:
-                g = plan.given[i].to(dev)
-                buf[:, n0:] = g if g.shape[0] == R else g.repeat_interleave(S, 0)
-                steps[i] = buf[:, n0:].t().contiguous()  # [N, R]: row j is what a decode step of new position j reads
-            elif plan.roles[i] == HELD and N > 0:
-                buf[:, n0:] = s[:, -1:]
-            bufs.append(buf)
-        compact = {i: torch.zeros(R, dtype=torch.long, device=dev) for i in gen}
-        held = {i: rows[i][:, -1].contiguous() for i in range(M) if plan.roles[i] == HELD}
-        lps = {i: torch.empty(R, N, dtype=torch.float32, device=dev) for i in gen} if return_logprobs else None
-        ml = MS.MultiLaunch([self.vocab_sizes[i] for i in gen], settings, [MS.modality_seed(seed, i) for i in gen],
-                            [cap] * len(gen), [N] * len(gen))
-        for p, i in enumerate(gen):
-            ml.compact[p] = compact[i].data_ptr()
-        dec_logits = p_idx = p_logits = None
-        p_flat = ML.ptr(flat)
-        # evidence: one scoring problem per given modality, over the views the sampler reads and the given token of
-        # column n, which the sequence buffers already hold; the fp64 weights per row and evidence per prompt
-        giv = sorted(plan.given) if plan.evidence is not None else []
-        Bp, Sp = (plan.B, S) if S is not None else (R, 1)  # without num_samples every row is a prompt of one path
-        if giv:
-            glp = {i: torch.zeros(R, N, dtype=torch.float32, device=dev) for i in giv}
-            sl = MS.ScoreLaunch([self.vocab_sizes[i] for i in giv], [cap] * len(giv), [N] * len(giv))
-            logw = torch.zeros(R, dtype=torch.float64, device=dev)
-            logev = torch.zeros(Bp, dtype=torch.float64, device=dev)
-            npts = len(plan.points)
-            anc = torch.empty(npts + 1, R, dtype=torch.int32, device=dev)  # the last row: the closing fold's identity
-            res = torch.empty(npts + 1, Bp, dtype=torch.int32, device=dev)
-            rl = MS.ResampleLaunch([glp[i].data_ptr() for i in giv], [N] * len(giv))
-        # forecast: per generated modality the pmf of every (prompt, new token), ESS and live count as [N, Bp] (a
-        # step writes one contiguous row); the weights are those the evidence carries: logw and the given columns
-        fc = plan.forecast
-        if fc is not None:
-            fpmf = {i: torch.zeros(Bp, N, self.vocab_sizes[i], dtype=torch.float32, device=dev) for i in gen}
-            fess = {i: torch.zeros(N, Bp, dtype=torch.float64, device=dev) for i in gen}
-            flive = {i: torch.zeros(N, Bp, dtype=torch.int32, device=dev) for i in gen}
-            fl = MS.ForecastLaunch([self.vocab_sizes[i] for i in gen], settings,
-                                   [max(N, 1) * self.vocab_sizes[i] for i in gen],
-                                   [glp[i].data_ptr() for i in giv], [N] * len(giv))
-            fbytes = fl.scratch_bytes(L, Bp, Sp)
-            fscratch = torch.empty(max(fbytes, 16), dtype=torch.uint8, device=dev)
-            # with evidence the forecast carries rule 2's a_s itself, from one buffer into the other, and folds ONE
-            # column per step: the serial fp64 sum over the columns since the last point, bit for bit, at O(1) a step
-            facc = torch.zeros(2, R, dtype=torch.float64, device=dev) if giv else None
-            fcur = 0
-
-        def decode_args(j):
-            """The pointer arrays of the decode step that reads the tokens of new position j (made at first use)."""
-            nonlocal dec_logits, p_idx, p_logits
-            if p_idx is None:
-                dec_logits = [torch.empty(R, Vi, dtype=torch.float32, device=dev) for Vi in self.vocab_sizes]
-                p_idx = ML.ptr_array([compact[i] if i in compact else held.get(i) for i in range(M)])
-                p_logits = ML.ptr_array(dec_logits)
-            for i, st in steps.items():
-                p_idx[i] = st.data_ptr() + 8 * R * j
-
-        def sample(n, j, views):
-            nonlocal fcur
-            if logits_hook is not None:
-                logits_hook(n, views)
-            for p, i in enumerate(gen):
-                ml.logits[p] = views[i].data_ptr()
-                ml.row_stride[p] = int(views[i].stride(0)) if R > 1 else self.vocab_sizes[i]
-                ml.tok[p] = bufs[i].data_ptr() + 8 * n
-                ml.logprob[p] = lps[i].data_ptr() + 4 * j if lps is not None else None
-            ml.run(L, stream, R, 0, n)
-            if giv:
-                for p, i in enumerate(giv):
-                    sl.logits[p] = views[i].data_ptr()
-                    sl.row_stride[p] = int(views[i].stride(0)) if R > 1 else self.vocab_sizes[i]
-                    sl.tok[p] = bufs[i].data_ptr() + 8 * n
-                    sl.logprob[p] = glp[i].data_ptr() + 4 * j
-                sl.run(L, stream, R)
-            if fc is not None:  # the mixture of the laws just drawn from, weighted by the given columns since..j
-                for p, i in enumerate(gen):
-                    Vi = self.vocab_sizes[i]
-                    fl.logits[p] = views[i].data_ptr()
-                    fl.row_stride[p] = int(views[i].stride(0)) if R > 1 else Vi
-                    fl.pmf[p] = fpmf[i].data_ptr() + 4 * Vi * j
-                    fl.ess[p] = fess[i].data_ptr() + 8 * Bp * j
-                    fl.live[p] = flive[i].data_ptr() + 4 * Bp * j
-                if giv:
-                    fl.run(L, stream, Bp, Sp, j, j + 1, facc[fcur].data_ptr(), fscratch.data_ptr(), fbytes,
-                           facc[1 - fcur].data_ptr())
-                    fcur = 1 - fcur
-                else:
-                    fl.run(L, stream, Bp, Sp, 0, 0, 0, fscratch.data_ptr(), fbytes)
-
-        def fold(j0, j1, threshold, pos, point):
-            """mmt_resample over the given log-probabilities of the new tokens j0..j1-1 into row `point` of the
-            ancestors / resampled records."""
-            rl.run(L, stream, Bp, Sp, j0, j1, logw.data_ptr(), logev.data_ptr(), threshold, seed, pos,
-                   anc.data_ptr() + 4 * R * point, res.data_ptr() + 4 * Bp * point)
-
-        def follow(a):
-            """Every per-row buffer follows its ancestor (in place: the launch arrays keep their addresses)."""
-            a = a.long()
-            for t in bufs + list(compact.values()) + list(glp.values()) + (list(lps.values()) if lps else []):
-                t.copy_(t.index_select(0, a))
-            for st in steps.values():
-                st.copy_(st.index_select(1, a))
-
-        with torch.cuda.device(dev):
-            stream = ML.stream_ptr(dev)
-            if fan:
-                logits, _ = self(prompts)  # the prefill: leaves every prompt position's keys / values in the workspace
-                sel = torch.arange(plan.B, device=dev).repeat_interleave(S)
-                first = [lg[:, -1, :].index_select(0, sel) for lg in logits]  # each sample's copy of its prompt's row
-                fanbuf = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-                p_ws, p_fan = ML.ptr(self._ws), ML.ptr(fanbuf)
-                if plan.points:  # the second fan buffer: the tails are gathered from one into the other
-                    fanbuf2 = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-                    p_fan2 = ML.ptr(fanbuf2)
-                last_point, point = 0, 0
-                for j in range(N):
-                    n = n0 + j
-                    if j == 0:
-                        views = first
-                    else:
-                        decode_args(j - 1)
-                        rc = L.mmt_decode_fanout_step(self._ctx, stream, plan.B, S, n0, N, n - 1, p_idx, p_flat,
-                                                      p_logits, p_ws, p_fan)
-                        ML.check(rc, self._ctx, "mmt_decode_fanout_step")
-                        views = dec_logits
-                    sample(n, j, views)
-                    if point < len(plan.points) and plan.points[point] == j:
-                        # the fixed schedule: weights of the columns since the last point, ancestors (the identity for
-                        # a prompt that did not trigger), then every per-row buffer and the tails follow them
-                        fold(last_point, j + 1, plan.ess_threshold, n, point)
-                        follow(anc[point])
-                        if fc is not None:  # the forecast's carried sums restart from the folded weights
-                            facc[fcur].copy_(logw)
-                        if j >= 1:
-                            rc = L.mmt_fanout_gather(self._ctx, stream, plan.B, S, n0, N, j,
-                                                     anc.data_ptr() + 4 * R * point, p_fan, p_fan2)
-                            ML.check(rc, self._ctx, "mmt_fanout_gather")
-                            p_fan, p_fan2 = p_fan2, p_fan
-                        last_point, point = j + 1, point + 1
-                if giv:
-                    fold(last_point, N, -1.0, n0 + N - 1, len(plan.points))  # the closing fold: no resampling
-            else:
-                cached_pos = None  # the last position whose keys / values the workspace holds
-                for j in range(N):
-                    n = n0 + j
-                    if cache and cached_pos is not None and n - 1 == cached_pos + 1 and n <= T:
-                        decode_args(j - 1)
-                        rc = L.mmt_decode_step(self._ctx, stream, R, n - 1, p_idx, p_flat, p_logits,
-                                               ML.ptr(self._ws))
-                        ML.check(rc, self._ctx, "mmt_decode_step")
-                        self._gen += 1
-                        cached_pos = n - 1
-                        views = dec_logits
-                    else:
-                        logits, _ = self([buf[:, max(0, n - T):n] for buf in bufs])
-                        views = [lg[:, -1, :] for lg in logits]
-                        cached_pos = n - 1 if (cache and n <= T) else None
-                    sample(n, j, views)
-                if giv:
-                    fold(0, N, -1.0, n0 + N - 1, 0)
-        seqs = [buf.to(idx_list[i].dtype) for i, buf in enumerate(bufs)]
-        out = [seqs] + ([lps] if return_logprobs else [])
-        if giv:
-            out.append({"given_logprobs": glp, "log_weights": logw, "log_evidence": logev, "ancestors": anc[:npts],
-                        "resampled": res[:npts], "steps": list(plan.points)})
-        if fc is not None:
-            # one mmt_pmf_stats over every (prompt, new token) row of every generated modality; the origin of a value
-            # series' direction is the prompt's last token of that modality
-            Q = len(fc["quantiles"])
-            st = MS.StatsLaunch([self.vocab_sizes[i] for i in gen], [self.vocab_sizes[i] for i in gen],
-                                [fc["is_percent"].get(i, False) for i in gen], fc["quantiles"])
-            stats = {i: torch.empty(Bp, N, 8, dtype=torch.float64, device=dev) for i in gen}
-            qtok = {i: torch.empty(Bp, N, Q, dtype=torch.int32, device=dev) for i in gen}
-            vals = {i: v.to(dev) for i, v in fc["values"].items()}
-            origin = {i: prompts[i][:, -1:].expand(Bp, N).contiguous() for i in gen}
-            for p, i in enumerate(gen):
-                st.pmf[p], st.stats[p], st.qtok[p] = fpmf[i].data_ptr(), stats[i].data_ptr(), qtok[i].data_ptr()
-                st.values[p] = vals[i].data_ptr() if i in vals else None
-                st.origin[p] = origin[i].data_ptr()
-            with torch.cuda.device(dev):
-                st.run(L, ML.stream_ptr(dev), Bp * N)
-            res_fc = {}
-            for i in gen:
-                s, qt = stats[i], qtok[i]
-                if i in vals:
-                    qv = torch.where(qt >= 0, vals[i][qt.clamp_min(0).long()], float("nan"))
-                else:
-                    qv = torch.full((Bp, N, Q), float("nan"), dtype=torch.float64, device=dev)
-                res_fc[i] = {"pmf": fpmf[i], "ess": fess[i].t().contiguous(), "live": flive[i].t().contiguous(),
-                             "entropy": s[..., 1], "mean": s[..., 2], "var": s[..., 3], "p_down": s[..., 4],
-                             "p_flat": s[..., 5], "p_up": s[..., 6], "quantile_tokens": qt, "quantile_values": qv}
-            out.append(res_fc)
-        hz = plan.horizon
-        if hz is not None:
-            # one mmt_horizon_stats over the final paths: tok at column n0 of the sequence buffers, the origin of a
-            # value series at column n0 - 1, the weights the final log_weights. One nb per call: shorter barrier lists
-            # are padded (with 1.0) and their columns cut from the result.
-            mods = hz["modalities"]
-            nbar = max([len(hz["barriers"].get(i, [])) for i in mods])
-            bars = [list(hz["barriers"].get(i, [])) for i in mods]
-            hl = MS.HorizonLaunch([self.vocab_sizes[i] for i in mods], [cap] * len(mods),
-                                  [hz["is_percent"].get(i, False) for i in mods], hz["quantiles"],
-                                  [b + [1.0] * (nbar - len(b)) for b in bars])
-            houts = MS.horizon_outputs(len(mods), Bp, N, hl.nq, hl.nb, dev)
-            hvals = [hz["values"][i].to(dev) for i in mods]
-            for p, i in enumerate(mods):
-                hl.tok[p] = bufs[i].data_ptr() + 8 * n0
-                hl.origin[p], hl.origin_stride[p] = bufs[i].data_ptr() + 8 * (n0 - 1), cap
-                hl.values[p] = hvals[p].data_ptr()
-                (hl.stats[p], hl.qval[p], hl.qrow[p], hl.hit[p], hl.ess[p],
-                 hl.live[p]) = [x.data_ptr() if x.numel() else None for x in houts[p]]
-            hbytes = hl.scratch_bytes(L, Bp, Sp, N)
-            hscratch = torch.empty(max(hbytes, 16), dtype=torch.uint8, device=dev)
-            with torch.cuda.device(dev):
-                hl.run(L, ML.stream_ptr(dev), Bp, Sp, N, logw.data_ptr() if giv else 0, hscratch.data_ptr(), hbytes)
-            res_hz = {}
-            for p, i in enumerate(mods):
-                res_hz[i] = MS.horizon_dict(houts[p])
-                res_hz[i]["hit"] = res_hz[i]["hit"][..., :len(bars[p])]
-            out.append(res_hz)
-        return out[0] if len(out) == 1 else tuple(out)
+        return MR.reference_loop(self, [idx.clone() for idx in idx_list], max_new_tokens, modality_to_generate,
+                                 use_cache, lambda j, n, last: sample(torch.softmax(last, dim=-1)))
 
     @torch.no_grad()
     def _decode_step(self, tokens, pos):
