@@ -395,6 +395,67 @@ int mmt_horizon_stats(void* stream, int32_t count, int32_t batch, int32_t sample
                       double* const* ess /* nullable, entries nullable */,
                       int32_t* const* live /* nullable, entries nullable */, void* scratch, int64_t scratch_bytes);
 
+/* Evaluation at every position. mmt_eval_direction scores the last position of every window; the evaluation forward
+ * has written the logits of all batch * T rows. mmt_eval_positions scores every row with t >= t_begin: direction,
+ * log score and what a calibration check of the head's probabilities needs, then reduces the rows to tables. No
+ * context.
+ *
+ * `count` problems (the modalities) over the same `batch` and `T`. Per problem (HOST arrays): V; logits (device
+ * fp32 [batch, T, V], row (b, t) at logits[p] + (b T + t) V); xb and yb (device int64 [batch, T]: the token at
+ * position t and the token that followed it, as get_batch makes them); values (device fp64 [V]; the array and its
+ * entries nullable); is_percent (nullable: all 0). Outputs per problem: rec (device fp64 [batch, T, 8]; the array
+ * and its entries nullable: the records then live in the scratch), pos fp64 [T, 8], rel fp64 [3, bins, 3], pit
+ * fp64 [bins]. scratch: mmt_eval_positions_scratch_bytes(count, batch, T, bins) bytes of device memory, 16-byte
+ * aligned, its contents unspecified before and after.
+ * Stage 1, the record of row (b, t), t >= t_begin. The law of the row is mmt_sample's at temperature 1, top_k 0,
+ * top_p 1, by the sampler's own device code: z the logit, NaN as -inf; m = max z; e_i = expf(z_i - m) in fp32, 1 at
+ * the maximum; S the fp64 sum of the e_i over the sampler's tree (thread t of 256 owns the c = ceil(V / 256) | 1
+ * elements from t c: serial sum, shift scan over the lanes, the four wave totals left to right); P(i) = e_i / S. A
+ * mass below is the fp64 sum over that same tree of the e_i of a class (the other leaves zeroed), divided by S once.
+ * The direction sign of token i is that of values[i] for a percent series and of values[i] - values[xb] (one fp64
+ * subtraction) for a value series: the reference's _get_direction_sign, mmt_pmf_stats' stats[4..6] with origin xb.
+ *   rec[0] the log-probability of yb: the fp32 value mmt_score_multi writes for that row and token, widened
+ *   rec[1..3] p_down, p_flat, p_up: the masses of the tokens whose sign is -1 / 0 / +1
+ *   rec[4] the mid-PIT in token order: (mass of { i < yb } before the division + 0.5 e_yb) / S
+ *   rec[5] the rank of yb, #{ i : z_i > z_yb }, exact comparisons: 0 is the arg-max group
+ *   rec[6] the predicted sign: that of the lowest index among the maxima of the raw logits (NaN as -inf), the token
+ *          mmt_eval_direction predicts
+ *   rec[7] the realised sign: that of yb
+ * Without values rec[1..3], rec[6] and rec[7] are NaN. A row with no finite logit, or with xb or yb outside 0..V-1
+ * (neither is then used as an index), is dead: its eight fields are NaN. Records of rows with t < t_begin are not
+ * written.
+ * Stage 2, the tables, a function of the records alone. A row is live when rec[5] is not NaN and has a direction
+ * when rec[6] is not NaN. Every sum is serial in fp64 from 0; counts are therefore exact.
+ *   pos[t, k], over the rows of position t, b ascending (zero for t < t_begin):
+ *     [0] live rows                    [1] wins, rec[6] == rec[7]      [2] losses, rec[6] != rec[7]
+ *     [3] certainty: the sum of the mass rec[1..3] the predicted sign selects (the reference's certainty)
+ *     [4] the sum of -rec[0]           [5] top-1 hits, rec[5] == 0     [6] rows with a direction
+ *     [7] the sum of the mass the realised sign selects
+ *   rel[d, k, 0..2], d = 0, 1, 2 for down, flat, up: a row with a direction enters bin
+ *     k = min(bins - 1, floor(P_d * bins)), P_d = rec[1 + d] (one fp64 product); the cell holds the count, the sum
+ *     of P_d, and the number of rows whose realised sign is d - 1
+ *   pit[k]: the live rows with k = min(bins - 1, floor(rec[4] * bins))
+ * A rel or pit cell is the sum over t = t_begin..T-1 ascending of the position's own sum over b ascending.
+ * accumulate == 0 writes the tables; otherwise each cell is added, with one fp64 addition, to what the buffer
+ * holds. No float atomics: a launch is bit-identical run to run, and a problem gives in company the bits it gives
+ * alone. Nothing outside the named buffers is written.
+ * Launches, per chunk of 8 problems: one over (batch (T - t_begin), problems) for the records (a second one for the
+ * problems with V > 8192, the sampler's re-read variant), one over (T, problems) for the positions, one over
+ * (problems) for the reliability and PIT cells.
+ * MMT_ERR_INVALID before any launch, nothing written: count, batch or T negative; t_begin outside 0..T; bins
+ * outside 1..64; batch * T >= 2^31; with count > 0 a null V / logits / xb / yb / pos / rel / pit array; V < 1; with
+ * batch > 0 and t_begin < T a null logits / xb / yb / pos / rel / pit entry; with batch > 0 a null, misaligned or
+ * undersized scratch. MMT_ERR_UNSUPPORTED for V > 2^20. count == 0, batch == 0 and t_begin == T launch nothing and
+ * write nothing. mmt_eval_positions_scratch_bytes returns -1 for arguments the entry refuses. */
+int64_t mmt_eval_positions_scratch_bytes(int32_t count, int32_t batch, int32_t T, int32_t bins);
+int mmt_eval_positions(void* stream, int32_t count, int32_t batch, int32_t T, int32_t t_begin, int32_t bins,
+                       int32_t accumulate, const int32_t* V, const float* const* logits,
+                       const int64_t* const* xb, const int64_t* const* yb,
+                       const double* const* values /* nullable, entries nullable */,
+                       const int32_t* is_percent /* nullable */,
+                       double* const* rec /* nullable, entries nullable */, double* const* pos,
+                       double* const* rel, double* const* pit, void* scratch, int64_t scratch_bytes);
+
 /* failure detection (the reference's guard is the NaN check on eval losses,
  * main.py:606): byte offset in the workspace of two int32 bitmasks (the same for every batch size;
  * the query never touches the workspace plan of a pending backward or decode). The

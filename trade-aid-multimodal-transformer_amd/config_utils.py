@@ -19,7 +19,9 @@ _DEFAULTS = {
                             # (mmt_optim.AdamW max_grad_norm / skip_nonfinite) and in-place gradient accumulation
                             "grad_clip": None, "grad_accum_steps": 1, "skip_nonfinite_steps": False,
                             # build-only key: per-tensor gradient statistics (mmt_stats.TensorStats)
-                            "grad_stats": "off"},
+                            "grad_stats": "off",
+                            # build-only keys: evaluation at every position (mmt_eval.PositionMetrics in estimate_loss)
+                            "eval_positions": "last", "eval_positions_from": 0},
     "model_architecture": {"n_embd": 384, "n_head": 6, "n_layer": 6, "dropout": 0.2,
                            "fixed_values": [-0.5, -0.2, -0.1, 0, 0.1, 0.2, 0.5],
                            # build-only key (the reference ignores unknown keys): "bf16" | "fp8"
@@ -162,4 +164,23 @@ def _get_grad_stats():
         return "off"
     if not isinstance(v, str) or v not in ("off", "skipped", "every"):
         raise ValueError(f"grad_stats must be 'off', 'skipped' or 'every', got {v!r}")
+    return v
+
+
+def _get_eval_positions():
+    """Build-only knob: which positions estimate_loss evaluates. "last" (default, also when the key is absent): the
+    reference's directional metric on the last position of every window, nothing else. "all": in addition the
+    position metrics of mmt_eval.PositionMetrics over every position from eval_positions_from on."""
+    v = _get_config().get("eval_positions", "last")
+    if not isinstance(v, str) or v not in ("last", "all"):
+        raise ValueError(f"eval_positions must be 'last' or 'all', got {v!r}")
+    return v
+
+
+def _get_eval_positions_from():
+    """Build-only knob: the first position (t_begin) of the position metrics, an integer in 0..block_size; default 0
+    (also when the key is absent). Read only with eval_positions: all."""
+    v = _get_config().get("eval_positions_from", 0)
+    if isinstance(v, bool) or not isinstance(v, int) or v < 0 or v > _get_block_size():
+        raise ValueError(f"eval_positions_from must be an integer in 0..block_size, got {v!r}")
     return v

@@ -396,6 +396,24 @@ struct HorizonBatch { HorizonProblem p[MMT_MAX_GROUP]; double level[MMT_HZ_MAX_Q
 hipError_t mmt_launch_horizon(const HorizonBatch& b, int n, void* scratch, int64_t rows, int64_t per, int batch,
                               int samples, int steps, const double* logw, hipStream_t s);
 
+// Evaluation at every position (mmt_eval_positions, mmt_evalpos.hip). Row r = b * T + t. The launchers validate
+// nothing: the C entry does. `rec` is the caller's record buffer or the problem's place in the scratch, `part` the
+// problem's per-position partial tables [T][10 bins] in the scratch.
+struct EvalPosProblem {
+  const float* logits;                                            // [batch, T, V]
+  const int64_t* xb; const int64_t* yb;                           // [batch, T]
+  const double* values;                                           // nullable
+  double* rec; double* pos; double* rel; double* pit; double* part;
+  int V, is_percent;
+};
+struct EvalPosBatch { EvalPosProblem p[MMT_MAX_GROUP]; };
+// the records of n problems of one kind (onchip: every V <= 8192), grid (batch * (T - t_begin), n)
+hipError_t mmt_launch_evalpos_records(const EvalPosBatch& b, int n, bool onchip, int batch, int T, int t_begin,
+                                      hipStream_t s);
+// the tables from the records: positions, grid (T, n), then the reliability and PIT cells, grid (n)
+hipError_t mmt_launch_evalpos_tables(const EvalPosBatch& b, int n, int batch, int T, int t_begin, int bins,
+                                     int accumulate, hipStream_t s);
+
 // ------------------------------------------------------------------------------------------
 // Per-head Q/K/V stage 2: block-diagonal [hs/2 -> hs] maps (model.py:39,44,49), nblk = 3*H.
 //   out[r, blk*hs + o] = sum_i W2[blk][o][i] * h1[r, blk*hs/2 + i]

@@ -1,0 +1,276 @@
+"""Evaluation at every position (include/mmt.h: mmt_eval_positions): direction, log score and calibration of the
+heads over all B x T rows an evaluation forward has written, not only the last position of each window.
+
+    position_metrics(logits_list, xb_list, yb_list, values, is_percent, ...)   one call, the device tables
+    PositionMetrics(values, is_percent, ...).add(...) / .result() / .summary_lines(names)
+                                                                               tables accumulated over many batches
+
+Everything runs in the library's kernels; there is no torch formulation behind it. `add` launches and returns: the
+one device-to-host read is in `result`."""
+import ctypes
+
+import numpy as np
+import torch
+
+import mmt_lib as ML
+
+POS_FIELDS = ("rows", "wins", "losses", "certainty", "nll", "top1", "directed", "realised_mass")  # pos[t, k]
+REC_FIELDS = ("logprob", "p_down", "p_flat", "p_up", "pit", "rank", "predicted", "realised")  # rec[b, t, k]
+DIRECTIONS = ("down", "flat", "up")  # rel[d]
+MAX_BINS = 64
+MAX_V = 1 << 20
+
+
+def _check_settings(t_begin, bins, T=None):
+    if isinstance(bins, bool) or not isinstance(bins, int) or not 1 <= bins <= MAX_BINS:
+        raise ValueError(f"position_metrics: bins must be an integer in 1..{MAX_BINS}, got {bins!r}")
+    if isinstance(t_begin, bool) or not isinstance(t_begin, int) or t_begin < 0 or (T is not None and t_begin > T):
+        raise ValueError(f"position_metrics: t_begin must be an integer in 0..T{'' if T is None else f' (T = {T})'}, "
+                         f"got {t_begin!r}")
+
+
+def _check_inputs(logits_list, xb_list, yb_list, values, is_percent, token_range):
+    """The shapes, dtypes, layout and device of one call's inputs; ValueError names the argument. Returns
+    (device, B, T, [V])."""
+    P = len(logits_list)
+    for name, lst in (("xb_list", xb_list), ("yb_list", yb_list), ("values", values), ("is_percent", is_percent)):
+        if not isinstance(lst, (list, tuple)) or len(lst) != P:
+            raise ValueError(f"position_metrics: {name} must be a list of {P} entries, one per logits tensor")
+    if P == 0:
+        return None, 0, 0, []
+    lg0 = logits_list[0]
+    if not isinstance(lg0, torch.Tensor) or lg0.dim() != 3:
+        raise ValueError("position_metrics: logits_list[0] must be an fp32 [B, T, V] tensor")
+    dev, B, T = lg0.device, int(lg0.shape[0]), int(lg0.shape[1])
+    Vs = []
+    for p in range(P):
+        lg = logits_list[p]
+        if not isinstance(lg, torch.Tensor) or lg.dim() != 3 or lg.dtype != torch.float32 or (
+                tuple(lg.shape[:2]) != (B, T)) or lg.shape[2] < 1:
+            raise ValueError(f"position_metrics: logits_list[{p}] must be an fp32 [{B}, {T}, V] tensor")
+        if lg.device.type != "cuda" or lg.device != dev:
+            raise ValueError(f"position_metrics: logits_list[{p}] must be on the GPU of logits_list[0] (the metrics run "
+                             "in HIP kernels; there is no CPU path)")
+        if not lg.is_contiguous():
+            raise ValueError(f"position_metrics: logits_list[{p}] must be contiguous")
+        V = int(lg.shape[2])
+        if V > MAX_V:
+            raise ValueError(f"position_metrics: logits_list[{p}] has V = {V}, above {MAX_V}")
+        Vs.append(V)
+        for name, t in (("xb_list", xb_list[p]), ("yb_list", yb_list[p])):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or tuple(t.shape) != (B, T):
+                raise ValueError(f"position_metrics: {name}[{p}] must be an int64 [{B}, {T}] tensor")
+            if t.device != dev:
+                raise ValueError(f"position_metrics: {name}[{p}] must be on the GPU of the logits")
+            if not t.is_contiguous():
+                raise ValueError(f"position_metrics: {name}[{p}] must be contiguous")
+            if token_range and t.numel() and (int(t.min()) < 0 or int(t.max()) >= V):
+                raise ValueError(f"position_metrics: {name}[{p}] holds tokens outside 0..{V - 1}")
+        v = values[p]
+        if v is not None:
+            if not isinstance(v, torch.Tensor) or v.dtype != torch.float64 or tuple(v.shape) != (V,):
+                raise ValueError(f"position_metrics: values[{p}] must be None or an fp64 [{V}] tensor")
+            if v.device != dev:
+                raise ValueError(f"position_metrics: values[{p}] must be on the GPU of the logits")
+            if not v.is_contiguous():
+                raise ValueError(f"position_metrics: values[{p}] must be contiguous")
+    if B * T >= 2 ** 31:
+        raise ValueError(f"position_metrics: logits_list holds {B} x {T} rows, 2^31 or more")
+    return dev, B, T, Vs
+
+
+class EvalLaunch:
+    """The host arrays of mmt_eval_positions over P problems (raw addresses; values / rec 0 = absent), made once."""
+
+    def __init__(self, V, is_percent):
+        P = self.P = len(V)
+        n = max(1, P)
+        self.V = (ctypes.c_int32 * n)(*[int(v) for v in V])
+        self.is_percent = (ctypes.c_int32 * n)(*[1 if x else 0 for x in is_percent])
+        self.logits = (ctypes.c_void_p * n)()
+        self.xb = (ctypes.c_void_p * n)()
+        self.yb = (ctypes.c_void_p * n)()
+        self.values = (ctypes.c_void_p * n)()
+        self.rec = (ctypes.c_void_p * n)()
+        self.pos = (ctypes.c_void_p * n)()
+        self.rel = (ctypes.c_void_p * n)()
+        self.pit = (ctypes.c_void_p * n)()
+
+    def scratch_bytes(self, L, batch, T, bins):
+        n = L.mmt_eval_positions_scratch_bytes(self.P, int(batch), int(T), int(bins))
+        if n < 0:
+            raise ValueError(f"position_metrics: {batch} x {T} rows with {bins} bins is a shape the entry refuses")
+        return int(n)
+
+    def run(self, L, stream, batch, T, t_begin, bins, accumulate, scratch_ptr, scratch_bytes):
+        rc = L.mmt_eval_positions(stream, self.P, batch, T, t_begin, bins, 1 if accumulate else 0, self.V, self.logits,
+                                  self.xb, self.yb, self.values, self.is_percent, self.rec, self.pos, self.rel,
+                                  self.pit, scratch_ptr, scratch_bytes)
+        if rc != 0:
+            raise ML.MmtError(f"mmt_eval_positions failed (status {rc})")
+
+
+def _table_views(flat, P, T, bins):
+    """The tables of P problems as views of one flat fp64 buffer: per problem pos [T, 8], rel [3, bins, 3], pit
+    [bins], in that order."""
+    each = T * 8 + 10 * bins
+    out = []
+    for p in range(P):
+        o = p * each
+        out.append((flat[o:o + T * 8].view(T, 8), flat[o + T * 8:o + T * 8 + 9 * bins].view(3, bins, 3),
+                    flat[o + T * 8 + 9 * bins:o + each].view(bins)))
+    return out
+
+
+def position_metrics(logits_list, xb_list, yb_list, values, is_percent, t_begin=0, bins=10, records=False):
+    """One mmt_eval_positions call over P modalities: logits_list holds P contiguous fp32 [B, T, V_p] tensors on one
+    GPU, xb_list / yb_list P contiguous int64 [B, T] tensors (the token at position t and the one that followed it),
+    values P entries, each an fp64 [V_p] device tensor or None (a non-numeric vocabulary: no direction), is_percent P
+    bools. Rows with t >= t_begin are scored. Returns a list of P dicts of device tensors: "pos" fp64 [T, 8]
+    (POS_FIELDS), "rel" fp64 [3, bins, 3] (per direction and bin: count, sum of the probability, realised), "pit" fp64
+    [bins], and with records=True "rec" fp64 [B, T, 8] (REC_FIELDS; rows before t_begin hold NaN). ValueError, naming
+    the argument, for shapes or dtypes that do not match, non-contiguous inputs, CPU tensors and tokens outside the
+    vocabulary (this check reads the tokens' extremes back; PositionMetrics.add leaves it out)."""
+    _check_settings(t_begin, bins)
+    dev, B, T, Vs = _check_inputs(logits_list, xb_list, yb_list, values, is_percent, token_range=True)
+    _check_settings(t_begin, bins, T)
+    P = len(Vs)
+    if P == 0:
+        return []
+    flat = torch.zeros(P * (T * 8 + 10 * bins), dtype=torch.float64, device=dev)  # zeros: B == 0 launches nothing
+    views = _table_views(flat, P, T, bins)
+    el = EvalLaunch(Vs, is_percent)
+    recs = [torch.full((B, T, 8), float("nan"), dtype=torch.float64, device=dev) if records else None
+            for _ in range(P)]
+    for p in range(P):
+        el.logits[p], el.xb[p], el.yb[p] = logits_list[p].data_ptr(), xb_list[p].data_ptr(), yb_list[p].data_ptr()
+        el.values[p] = values[p].data_ptr() if values[p] is not None else None
+        el.rec[p] = recs[p].data_ptr() if records and recs[p].numel() else None
+        el.pos[p], el.rel[p], el.pit[p] = (x.data_ptr() for x in views[p])
+    L = ML.lib()
+    nbytes = el.scratch_bytes(L, B, T, bins)
+    scratch = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        el.run(L, ML.stream_ptr(dev), B, T, t_begin, bins, False, scratch.data_ptr(), nbytes)
+    out = []
+    for p in range(P):
+        d = {"pos": views[p][0], "rel": views[p][1], "pit": views[p][2]}
+        if records:
+            d["rec"] = recs[p]
+        out.append(d)
+    return out
+
+
+def _ratio(a, b):
+    return float(a) / float(b) if b else float("nan")
+
+
+def derive(pos, rel, pit, t_begin=0):
+    """The numbers of one modality from its tables (numpy fp64: pos [T, 8], rel [3, bins, 3], pit [bins]). Returns a
+    dict: the tables; rows, directed, wins, losses; accuracy (wins / (wins + losses)) overall, per position [T] (NaN
+    where a position holds no row with a direction) and per quarter of the context length [4]; nll (mean -log p of
+    the token that came); top1 (rate of rank 0); certainty (mean mass on the predicted direction); realised_mass;
+    ece, per direction sum_k n_k / N |mean P_d - realised rate| over the bins; pit_hist (the PIT counts over their
+    sum). A mean over nothing is NaN."""
+    pos, rel, pit = np.asarray(pos, np.float64), np.asarray(rel, np.float64), np.asarray(pit, np.float64)
+    T = pos.shape[0]
+    tot = pos.sum(axis=0) if T else np.zeros(8)
+    rows, wins, losses, directed = int(tot[0]), int(tot[1]), int(tot[2]), int(tot[6])
+    with np.errstate(all="ignore"):
+        acc_t = np.where(pos[:, 1] + pos[:, 2] > 0, pos[:, 1] / (pos[:, 1] + pos[:, 2]), np.nan)
+    quarters = []
+    for k in range(4):
+        lo, hi = max((k * T) // 4, t_begin), ((k + 1) * T) // 4
+        seg = pos[lo:hi] if hi > lo else pos[:0]
+        quarters.append(_ratio(seg[:, 1].sum(), seg[:, 1].sum() + seg[:, 2].sum()))
+    ece = {}
+    for d, name in enumerate(DIRECTIONS):
+        n = rel[d, :, 0].sum()
+        ece[name] = _ratio(np.abs(rel[d, :, 1] - rel[d, :, 2]).sum(), n)
+    return {"pos": pos, "rel": rel, "pit": pit, "t_begin": t_begin, "rows": rows, "directed": directed, "wins": wins,
+            "losses": losses, "accuracy": _ratio(wins, wins + losses), "accuracy_per_position": acc_t,
+            "accuracy_per_quarter": quarters, "nll": _ratio(tot[4], rows), "top1": _ratio(tot[5], rows),
+            "certainty": _ratio(tot[3], directed), "realised_mass": _ratio(tot[7], directed), "ece": ece,
+            "pit_hist": pit / pit.sum() if pit.sum() > 0 else np.full(pit.shape, np.nan)}
+
+
+def _pct(x, digits=1):
+    return "n/a" if x != x else f"{round(x * 100, digits)}%"
+
+
+def summary_text(r):
+    """One modality's line, without its name: correct/total and accuracy over all positions, mean NLL, top-1 rate,
+    ECE of p_up and p_down, accuracy per quarter of the context length."""
+    total = r["wins"] + r["losses"]
+    head = f"{r['wins']}/{total} ({_pct(r['accuracy'])})" if total > 0 else "No directional predictions"
+    nll = "n/a" if r["nll"] != r["nll"] else f"{r['nll']:.4f}"
+    ece = " ".join(f"{k} {'n/a' if r['ece'][k] != r['ece'][k] else format(r['ece'][k], '.4f')}" for k in ("up", "down"))
+    quarters = " ".join(_pct(q) for q in r["accuracy_per_quarter"])
+    return f"{head} | NLL {nll} | top-1 {_pct(r['top1'])} | ECE {ece} | quarters {quarters}"
+
+
+class PositionMetrics:
+    """Tables accumulated on the device over many evaluation batches. values: P entries, each an fp64 [V_p] device
+    tensor or None; is_percent: P bools. `add` checks its inputs on the host (shapes, dtypes, layout, device; not the
+    tokens' range: a row with a token outside the vocabulary is dead on the device), launches with accumulate = 1 and
+    does not sync; the first `add` fixes B, T and the V_p. `result` is one device-to-host read."""
+
+    def __init__(self, values, is_percent, t_begin=0, bins=10):
+        _check_settings(t_begin, bins)
+        if not isinstance(values, (list, tuple)) or not isinstance(is_percent, (list, tuple)) or (
+                len(values) != len(is_percent)):
+            raise ValueError("PositionMetrics: values and is_percent must be lists of one length")
+        self.values, self.is_percent = list(values), [bool(x) for x in is_percent]
+        self.t_begin, self.bins = t_begin, bins
+        self.P = len(self.values)
+        self.batches = 0
+        self._shape = None
+
+    def _setup(self, dev, B, T, Vs):
+        _check_settings(self.t_begin, self.bins, T)
+        self._shape = (dev, B, T, tuple(Vs))
+        self._flat = torch.zeros(self.P * (T * 8 + 10 * self.bins), dtype=torch.float64, device=dev)
+        self._views = _table_views(self._flat, self.P, T, self.bins)
+        self._launch = el = EvalLaunch(Vs, self.is_percent)
+        for p in range(self.P):
+            el.values[p] = self.values[p].data_ptr() if self.values[p] is not None else None
+            el.pos[p], el.rel[p], el.pit[p] = (x.data_ptr() for x in self._views[p])
+        self._lib = ML.lib()
+        self._nbytes = el.scratch_bytes(self._lib, B, T, self.bins)
+        self._scratch = torch.empty(max(self._nbytes, 16), dtype=torch.uint8, device=dev)
+
+    def add(self, logits_list, xb_list, yb_list):
+        if len(logits_list) != self.P:
+            raise ValueError(f"PositionMetrics.add: logits_list must hold {self.P} tensors")
+        dev, B, T, Vs = _check_inputs(logits_list, xb_list, yb_list, self.values, self.is_percent, token_range=False)
+        if self.P == 0:
+            return
+        if self._shape is None:
+            self._setup(dev, B, T, Vs)
+        elif self._shape != (dev, B, T, tuple(Vs)):
+            raise ValueError(f"PositionMetrics.add: logits_list does not match the first batch's device and shapes "
+                             f"(B {self._shape[1]}, T {self._shape[2]}, V {list(self._shape[3])})")
+        el = self._launch
+        for p in range(self.P):
+            el.logits[p], el.xb[p], el.yb[p] = logits_list[p].data_ptr(), xb_list[p].data_ptr(), yb_list[p].data_ptr()
+        with torch.cuda.device(dev):
+            el.run(self._lib, ML.stream_ptr(dev), B, T, self.t_begin, self.bins, True, self._scratch.data_ptr(),
+                   self._nbytes)
+        self.batches += 1
+
+    def result(self):
+        """A list of P dicts (`derive`), from one device-to-host read of all tables. Before any `add`: []."""
+        if self._shape is None:
+            return []
+        T = self._shape[2]
+        host = self._flat.cpu()
+        return [derive(pos.numpy(), rel.numpy(), pit.numpy(), self.t_begin)
+                for pos, rel, pit in _table_views(host, self.P, T, self.bins)]
+
+    def summary_lines(self, name, result=None):
+        """The lines to print, one per modality: `name` is a list of P names (or one string when P == 1)."""
+        names = [name] if isinstance(name, str) else list(name)
+        res = self.result() if result is None else result
+        if len(names) != len(res):
+            raise ValueError(f"PositionMetrics.summary_lines: name must hold {len(res)} names, got {len(names)}")
+        return [f"  - {n:<30}{summary_text(r)}" for n, r in zip(names, res)]

@@ -25,7 +25,10 @@ lines and log lines. What changed underneath:
         training lists are brought up to date at every estimate_loss and by sync_host_state();
   * calculate_evaluation_metrics runs the per-sample argmax / direction / softmax-certainty loop
     (training_utils.py:259-304) as one HIP kernel per modality (mmt_eval_direction) with a single
-    device->host copy, instead of B*V `.item()` syncs.
+    device->host copy, instead of B*V `.item()` syncs;
+  * estimate_loss with the build-only key eval_positions: all also scores every position of the logits it has
+    (mmt_eval.PositionMetrics: direction, log score, calibration) and prints one more block; with the default,
+    last, nothing of that is imported or run.
 """
 import ctypes
 import math
@@ -38,7 +41,8 @@ import numpy as np
 import torch
 
 import mmt_lib as ML
-from config_utils import _get_batch_size, _get_block_size, _get_config, _get_device, _get_eval_iters
+from config_utils import (_get_batch_size, _get_block_size, _get_config, _get_device, _get_eval_iters,
+                          _get_eval_positions, _get_eval_positions_from)
 
 __all__ = ["generate_batch_starting_indices", "get_batch", "estimate_loss", "calculate_evaluation_metrics"]
 
@@ -522,10 +526,37 @@ def calculate_evaluation_metrics(logits_list, xb_list, yb_list, num_modalities, 
 # ------------------------------------------------------------------------------------------
 # estimate_loss (reference training_utils.py:387-520)
 # ------------------------------------------------------------------------------------------
+last_position_metrics = {}  # eval_positions: all. Per state the tables and numbers of the latest estimate_loss
+
+
+def _new_position_metrics(logits_list, yb_list):
+    """eval_positions: all. A PositionMetrics over the modalities calculate_evaluation_metrics scores (a numeric
+    vocabulary, a window long enough), made at the first batch of a state. Returns (metrics, indices, names)."""
+    import mmt_eval
+    idx, values, pct, names = [], [], [], []
+    for i in range(num_modalities):
+        if not (len(logits_list) > i and len(yb_list) > i):
+            continue
+        is_pct = bool(all_modality_params[i][3])
+        numeric, vt = _numeric_vocab(all_vocabularies[i], logits_list[i].device)
+        if not (numeric and yb_list[i].ndim >= 2 and yb_list[i].shape[1] >= (1 if is_pct else 2)):
+            continue
+        idx.append(i)
+        values.append(vt)
+        pct.append(is_pct)
+        names.append(all_modality_params[i][9] if all_modality_params[i][9] else f"Modality {i+1}")
+    pm = mmt_eval.PositionMetrics(values, pct, t_begin=_get_eval_positions_from(), bins=10)
+    return pm, idx, names
+
+
 def estimate_loss(current_step=None, max_steps=None):
     out = {}
+    every_position = _get_eval_positions() == "all"  # a bad key is refused before the model changes mode
+    if every_position:
+        _get_eval_positions_from()
     m.eval()
     for state in ["train", "val"]:
+        pm = None
         now = datetime.now()
         current_time = now.strftime("%H:%M:%S")
         step_info = f"Step {current_step}/{max_steps} | " if current_step is not None else ""
@@ -554,6 +585,11 @@ def estimate_loss(current_step=None, max_steps=None):
                     tot_bad[i] += l[i]
                     tot_cert[i] += c[i]
                     tot_proc[i] += p[i]
+                if every_position:  # the logits are there already: one more call, no sync
+                    if pm is None:
+                        pm, pm_idx, pm_names = _new_position_metrics(logits_list, yb_list)
+                    pm.add([logits_list[i].contiguous() for i in pm_idx], [xb_list[i].contiguous() for i in pm_idx],
+                           [yb_list[i].contiguous() for i in pm_idx])
         out[state] = (loss_sum.item() / n_losses) if n_losses else float("nan")
         disp = "Train Set" if state == "train" else "Val Set"
         print(f"\nDIRECTIONAL METRICS - {disp} (Correct/Total)")
@@ -568,6 +604,14 @@ def estimate_loss(current_step=None, max_steps=None):
                     print(f"  - {name}: No directional predictions")
             else:
                 print(f"  - {name}: No data processed (non-numeric)")
+        pm_res = None
+        if pm is not None:
+            pm_res = pm.result()
+            last_position_metrics[state] = {"indices": pm_idx, "names": pm_names, "results": pm_res,
+                                            "t_begin": pm.t_begin, "batches": pm.batches}
+            print(f"\nPOSITION METRICS - {disp} (positions {pm.t_begin}..{_get_block_size() - 1})")
+            for line in pm.summary_lines(pm_names, pm_res):
+                print(line)
         cfg = _get_config()
         output_file_name = cfg.get("output_file_name", "")
         project_file_path = cfg.get("project_file_path", "")
@@ -588,6 +632,10 @@ def estimate_loss(current_step=None, max_steps=None):
                                     f"Incorrect={tot_bad[i]:,} | Accuracy=N/A\n")
                     else:
                         f.write(f"   DIRECTIONAL PREDICTION {disp} - {name}: Correct=0 | Incorrect=0 | Accuracy=N/A\n")
+                if pm_res is not None:
+                    import mmt_eval
+                    for name, r in zip(pm_names, pm_res):
+                        f.write(f"   POSITION METRICS {disp} - {name}: {mmt_eval.summary_text(r)}\n")
                 if state == "train":
                     f.write("\n")
         if state == "train":
