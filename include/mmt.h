@@ -395,6 +395,77 @@ int mmt_horizon_stats(void* stream, int32_t count, int32_t batch, int32_t sample
                       double* const* ess /* nullable, entries nullable */,
                       int32_t* const* live /* nullable, entries nullable */, void* scratch, int64_t scratch_bytes);
 
+/* Scores of horizon forecasts. mmt_horizon_stats says where the paths of a prompt stand after j steps;
+ * mmt_horizon_score sets that against the series that was realised: per (prompt, step) proper scores of the weighted
+ * sample and of the forecast mmt_horizon_stats made of it, per step tables that accumulate over the calls of a
+ * backtest. No context.
+ *
+ * Paths: count, batch, samples, steps, V, tok, tok_stride, values, is_percent, origin, origin_stride, logw, nq, levels,
+ * nb, barriers as mmt_horizon_stats takes them. The realised series, one row per prompt: real (per problem a device
+ * int64 pointer, token j of prompt b at real[p] + b * real_stride[p] + j) and, required for a value series,
+ * real_origin (prompt b's at real_origin[p][b * real_origin_stride[p]]). The forecast, read and never recomputed:
+ * stats fp64 [batch, steps, 12], qval fp64 [batch, steps, nq], hit fp64 [batch, steps, nb], as a mmt_horizon_stats call
+ * on the same paths, weights, levels and barriers wrote them (qval / hit may be NULL when nq / nb is 0): the pointwise
+ * scores are a function of the forecast the caller holds. bins in 1..64. Outputs per problem: sc fp64 [batch, steps, 8]
+ * (the array and its entries nullable: the records then live in the scratch), pin fp64 [batch, steps, nq], bs fp64
+ * [batch, steps, nb], and the tables agg fp64 [steps, 10], aggq fp64 [steps, nq, 2], aggb fp64 [steps, nb, 3], pit
+ * fp64 [steps, bins] (pin / aggq and bs / aggb may be NULL when nq / nb is 0). scratch:
+ * mmt_horizon_score_scratch_bytes(count, batch, samples, steps) bytes of device memory, 16-byte aligned, its contents
+ * unspecified before and after.
+ * The rule, per problem, prompt b and step j:
+ *   1. the realised row is walked by rule 1 of mmt_horizon_stats (the same device function): x*, hi*, lo*, d* per
+ *      step. A realised row that rule 1 calls dead is dead at every step, and so is a prompt without a row with weight
+ *      (live == 0). A dead (b, j) has NaN in every sc / pin / bs field and enters no table.
+ *   2. weights: rule 2 of mmt_horizon_stats, unchanged: w_s, W (the same sum over the same tree, so the same bits)
+ *      and the rows with weight.
+ *   3. CRPS, the integral of (F - [x* <= t])^2 over t, piecewise: the n rows with weight in the order (x_j, s) of rule
+ *      4; P_m the inclusive fp64 prefix of w through place m over the chunk tree of that rule. For each gap between
+ *      the places m and m + 1, one IEEE operation each: a = x_(m); b = x_(m+1); s = min(b, max(a, x*)); F = P_m / W;
+ *      F2 = F * F; G = 1 - F; G2 = G * G; lo = (s - a) * F2; up = (b - s) * G2; term = lo + up. The terms are summed in
+ *      place order over the tree (thread t owns the c = ceil(samples / 256) | 1 places from t c, a gap belonging to
+ *      its lower place: serial sum from 0, shift scan over the lanes, the four wave totals left to right). The tail,
+ *      x_(1) - x* when x* < x_(1), x* - x_(n) when x* > x_(n), else 0, is added to that sum last. Every term is
+ *      non-negative; the CRPS is 0 when every x equals x* and |x_1 - x*| at one row.
+ *   4. PIT (mid): (L + 0.5 * E) / W with L = sum w [x < x*] and E = sum w [x == x*], both in row order over the tree;
+ *      h = 0.5 * E; n = L + h; PIT = n / W. The comparisons are exact: x* comes from the walk that made x.
+ *   5. sc[b, j, 0..7]: [0] x*  [1] CRPS  [2] PIT  [3] stats[0] - x*, the error of the mean  [4] the entry of
+ *      stats[2..4] that the sign of x* selects  [5] the entry of stats[5..7] that d* selects  [6] hi*  [7] lo*
+ *   6. pin[b, j, k] = (x* - q) * (levels[k] - [x* < q]), q = qval[b, j, k]: one subtraction each, then the product.
+ *   7. bs[b, j, k] = (hit[b, j, k] - o)^2, o = [hi* >= u] for a barrier u > 0 and [lo* <= u] for u < 0.
+ *   8. tables, a function of the records, the forecast and d*: every cell is a serial fp64 sum from 0 over the live
+ *      (b, j) of step j, b ascending, so counts are exact.
+ *      agg[j, .]: [0] scored prompts  [1] sum CRPS  [2] sum |x*| (the CRPS of a "no change" forecast: skill = 1 -
+ *        [1] / [2])  [3] sum |sc[3]|  [4] sum sc[3]^2  [5] sum sc[4]  [6] sign hits: the largest of stats[2..4], the
+ *        lowest index on ties, is the entry the sign of x* selects  [7] sum sc[5]  [8] step-direction hits, the same
+ *        on stats[5..7] and d*  [9] sum stats[1], the mean forecast variance, to set against [4]
+ *      aggq[j, k, .]: [0] sum pin  [1] #{ x* <= q }
+ *      aggb[j, k, .]: [0] sum bs  [1] sum hit  [2] #{ o = 1 }
+ *      pit[j, min(bins - 1, floor(PIT * bins))] (one fp64 product) counts the prompt.
+ *      accumulate == 0 writes the tables; otherwise each cell is added, with one fp64 addition, to what the buffer
+ *      holds.
+ * No float atomics: bit-identical run to run; a prompt launched alone (same samples) gives the sc / pin / bs it gives
+ * in company, and so does a problem. Nothing outside the named buffers is written.
+ * Launches, per chunk of 8 problems: one over ((batch samples + batch) / 256, problems) for rule 1 on the paths and
+ * the realised rows, one over (prompts x steps, problems) for the records (the weights of a prompt and the keys of one
+ * step in LDS, 56 KiB at 4096 rows), one over (steps, problems) for the tables, a thread per cell.
+ * MMT_ERR_INVALID before any launch, nothing written: what mmt_horizon_stats refuses so, with batch * samples + batch
+ * >= 2^31 in place of its bound on batch * samples; bins outside 1..64; real_stride < steps; a null required array or
+ * entry; a value series without origin or real_origin. MMT_ERR_UNSUPPORTED: V > 2^20, samples > 4096, batch * steps >=
+ * 2^31. count, batch or steps of 0 launches nothing and writes nothing. mmt_horizon_score_scratch_bytes returns -1
+ * for arguments the entry refuses. */
+int64_t mmt_horizon_score_scratch_bytes(int32_t count, int32_t batch, int32_t samples, int32_t steps);
+int mmt_horizon_score(void* stream, int32_t count, int32_t batch, int32_t samples, int32_t steps, const int32_t* V,
+                      const int64_t* const* tok, const int64_t* tok_stride, const double* const* values,
+                      const int32_t* is_percent /* nullable */, const int64_t* const* origin,
+                      const int64_t* origin_stride, const int64_t* const* real, const int64_t* real_stride,
+                      const int64_t* const* real_origin, const int64_t* real_origin_stride,
+                      const double* logw /* nullable */, int32_t nq, const double* levels, int32_t nb,
+                      const double* const* barriers, const double* const* stats, const double* const* qval,
+                      const double* const* hit, int32_t bins, int32_t accumulate,
+                      double* const* sc /* nullable, entries nullable */, double* const* pin, double* const* bs,
+                      double* const* agg, double* const* aggq, double* const* aggb, double* const* pit, void* scratch,
+                      int64_t scratch_bytes);
+
 /* Evaluation at every position. mmt_eval_direction scores the last position of every window; the evaluation forward
  * has written the logits of all batch * T rows. mmt_eval_positions scores every row with t >= t_begin: direction,
  * log score and what a calibration check of the head's probabilities needs, then reduces the rows to tables. No

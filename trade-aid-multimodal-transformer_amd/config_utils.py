@@ -21,7 +21,9 @@ _DEFAULTS = {
                             # build-only key: per-tensor gradient statistics (mmt_stats.TensorStats)
                             "grad_stats": "off",
                             # build-only keys: evaluation at every position (mmt_eval.PositionMetrics in estimate_loss)
-                            "eval_positions": "last", "eval_positions_from": 0},
+                            "eval_positions": "last", "eval_positions_from": 0,
+                            # build-only keys: scored rollouts (mmt_eval.RolloutMetrics in estimate_loss); 0 paths: off
+                            "eval_rollout_paths": 0, "eval_rollout_steps": 16, "eval_rollout_seed": 0},
     "model_architecture": {"n_embd": 384, "n_head": 6, "n_layer": 6, "dropout": 0.2,
                            "fixed_values": [-0.5, -0.2, -0.1, 0, 0.1, 0.2, 0.5],
                            # build-only key (the reference ignores unknown keys): "bf16" | "fp8"
@@ -183,4 +185,33 @@ def _get_eval_positions_from():
     v = _get_config().get("eval_positions_from", 0)
     if isinstance(v, bool) or not isinstance(v, int) or v < 0 or v > _get_block_size():
         raise ValueError(f"eval_positions_from must be an integer in 0..block_size, got {v!r}")
+    return v
+
+
+def _get_eval_rollout_paths():
+    """Build-only knob: how many paths estimate_loss rolls from the head of every evaluation window to score the
+    horizon forecast against the window's own tail (mmt_eval.RolloutMetrics). 0 (default, also when the key is
+    absent): off, nothing runs. At most 4096 (the paths of a prompt are sorted on chip)."""
+    v = _get_config().get("eval_rollout_paths", 0)
+    if isinstance(v, bool) or not isinstance(v, int) or v < 0 or v > 4096:
+        raise ValueError(f"eval_rollout_paths must be an integer in 0..4096, got {v!r}")
+    return v
+
+
+def _get_eval_rollout_steps():
+    """Build-only knob: H, the steps of a scored rollout: the last H tokens of a window are the realised series, the
+    first block_size - H the prompt. An integer with 1 <= H < block_size; default 16. Read only with
+    eval_rollout_paths > 0."""
+    v = _get_config().get("eval_rollout_steps", 16)
+    if isinstance(v, bool) or not isinstance(v, int) or v < 1 or v >= _get_block_size():
+        raise ValueError(f"eval_rollout_steps must be an integer with 1 <= H < block_size, got {v!r}")
+    return v
+
+
+def _get_eval_rollout_seed():
+    """Build-only knob: the seed the scored rollouts derive theirs from, an integer >= 0; default 0. Read only with
+    eval_rollout_paths > 0."""
+    v = _get_config().get("eval_rollout_seed", 0)
+    if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+        raise ValueError(f"eval_rollout_seed must be an integer >= 0, got {v!r}")
     return v

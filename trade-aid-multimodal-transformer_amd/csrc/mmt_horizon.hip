@@ -18,124 +18,39 @@
 // No float atomics, no data-dependent order of a sum: bit-identical run to run; a (prompt, step, problem) reads its own
 // rows only.
 //
-// Rule 1 is one IEEE operation per line: floating-point contraction is off for this file, or the compiler fuses
-// g * u - 1 into one multiply-add and x loses its bits against the rule (and against any other implementation).
+// The device functions of every stage are in mmt_horizon_dev.h, which mmt_horizon_score.hip shares. Rule 1 is one IEEE
+// operation per line: floating-point contraction is off for this file (the header turns it off for its own code), or
+// the compiler fuses g * u - 1 into one multiply-add and x loses its bits against the rule.
 #include <cmath>
 
 #include "mmt.h"
 #include "mmt_common.h"
 #include "mmt_kernels.h"
-#include "mmt_sample_dev.h"
+#include "mmt_horizon_dev.h"
 
 #pragma clang fp contract(off)
 
 namespace {
-
-constexpr int HZ_MAX_S = 4096;  // the rows of a (prompt, step) are sorted in LDS (mmt_resample's cap)
-constexpr int HZ_THREADS = SAMPLE_THREADS;
-constexpr int HZ_WAVES = SAMPLE_WAVES;
-constexpr int HZ_NSUM = 11 + MMT_HZ_MAX_B;
-
-// the scratch of problem `index`: x, hi, lo fp64 [steps][rows], d int8 [steps][rows], dead int32 [rows]
-struct HzScratch {
-  char* base;
-  int64_t rows, cells, per;  // cells = steps * rows; per = bytes of one problem
-  __host__ __device__ double* x(int index) const { return reinterpret_cast<double*>(base + index * per); }
-  __host__ __device__ double* hi(int index) const { return x(index) + cells; }
-  __host__ __device__ double* lo(int index) const { return x(index) + 2 * cells; }
-  __host__ __device__ int8_t* d(int index) const { return reinterpret_cast<int8_t*>(x(index) + 3 * cells); }
-  __host__ __device__ int32_t* dead(int index) const {
-    return reinterpret_cast<int32_t*>(base + index * per + 24 * cells + ((cells + 15) & ~(int64_t)15));
-  }
-};
 
 bool hz_plan(int32_t count, int32_t batch, int32_t samples, int32_t steps, HzScratch& sc, int64_t& bytes) {
   if (count < 0 || batch < 0 || steps < 0 || samples < 1 || (int64_t)batch * samples > 0x7fffffff) return false;
   sc.rows = (int64_t)batch * samples;
   sc.cells = sc.rows * steps;
   if (sc.cells > ((int64_t)1 << 44)) return false;  // 25 bytes a cell: far past any device, and no overflow below
-  sc.per = 24 * sc.cells + ((sc.cells + 15) & ~(int64_t)15) + ((4 * sc.rows + 15) & ~(int64_t)15);
+  sc.per = sc.walk_bytes();
   if (count > 0 && sc.per > (int64_t)0x7fffffffffffll / count) return false;
   bytes = sc.per * count;
   return true;
 }
 
-__device__ __forceinline__ int hz_sign(double v) { return v > 0.0 ? 1 : v < 0.0 ? -1 : 0; }
-
 __global__ __launch_bounds__(HZ_THREADS) void horizon_walk_kernel(HorizonBatch batch, HzScratch sc, int steps) {
   const HorizonProblem& q = batch.p[blockIdx.y];
   const int64_t r = (int64_t)blockIdx.x * HZ_THREADS + threadIdx.x;
   if (r >= sc.rows) return;
-  const int V = q.V, pct = q.is_percent;
-  const double* __restrict__ val = q.values;
-  const int64_t* __restrict__ tk = q.tok + r * q.tok_stride;
-  double* xs = sc.x(q.index) + r;
-  double* his = sc.hi(q.index) + r;
-  double* los = sc.lo(q.index) + r;
-  int8_t* ds = sc.d(q.index) + r;
-  bool ok = true;
-  double v0 = 0.0;
-  if (!pct) {
-    const int64_t o = q.origin[r * q.origin_stride];
-    ok = o >= 0 && o < V;
-    if (ok) v0 = val[o];
-  }
-  double prev = v0, g = 1.0, h = 0.0, l = 0.0;
-  for (int j = 0; ok && j < steps; ++j) {
-    const int64_t t = tk[j];
-    if (t < 0 || t >= V) { ok = false; break; }
-    const double v = val[t];
-    double x;
-    int d;
-    if (pct) {
-      const double c = v / 100.0;
-      const double u = 1.0 + c;
-      g = g * u;  // g_0 = 1 * u = u exactly
-      const double e = g - 1.0;
-      x = e * 100.0;
-      d = hz_sign(v);
-    } else {
-      x = v - v0;
-      d = hz_sign(v - prev);
-      prev = v;
-    }
-    if (!(fabs(x) < INFINITY)) { ok = false; break; }
-    h = fmax(h, x);
-    l = fmin(l, x);
-    const int64_t at = (int64_t)j * sc.rows;
-    xs[at] = x;
-    his[at] = h;
-    los[at] = l;
-    ds[at] = (int8_t)d;
-  }
+  const bool ok = hz_walk_row(q.tok + r * q.tok_stride, q.is_percent ? nullptr : q.origin + r * q.origin_stride, q.values,
+                              q.V, q.is_percent, steps, sc.x(q.index) + r, sc.hi(q.index) + r, sc.lo(q.index) + r,
+                              sc.d(q.index) + r, sc.rows);
   sc.dead(q.index)[r] = ok ? 0 : 1;
-}
-
-struct HzShared {
-  double d[2][HZ_NSUM][HZ_WAVES];
-  int i[2][MMT_HZ_MAX_Q][HZ_WAVES];
-};
-
-// the chunk tree for N sums at once: a thread's serial totals in, the block totals out (one barrier)
-template <int N>
-__device__ __forceinline__ void hz_sums(double (&v)[N], int n, HzShared& sh, int& par) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < N; ++k) {  // unrolled: v stays in registers
-    if (k >= n) continue;
-    double inc = v[k];
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const double m = __shfl_up(inc, o, 64);
-      if (lane >= o) inc += m;
-    }
-    if (lane == 63) sh.d[par][k][wave] = inc;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < N; ++k)
-    if (k < n) v[k] = ((sh.d[par][k][0] + sh.d[par][k][1]) + sh.d[par][k][2]) + sh.d[par][k][3];
-  par ^= 1;
 }
 
 __global__ __launch_bounds__(HZ_THREADS) void horizon_reduce_kernel(HorizonBatch batch, HzScratch sc, int S, int steps,
@@ -159,18 +74,7 @@ __global__ __launch_bounds__(HZ_THREADS) void horizon_reduce_kernel(HorizonBatch
   int par = 0;
 
   // rule 2: mmt_resample's rules 1 - 2 over the rows that are not dead
-  double mx = -INFINITY;
-  for (int s = tid; s < S; s += HZ_THREADS) {
-    double a = logw ? logw[r0 + s] : 0.0;
-    if (a != a || dead[s]) a = -INFINITY;
-    mx = fmax(mx, a);
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o, 64));
-  if (lane == 0) sh.d[par][0][wave] = mx;
-  __syncthreads();
-  mx = fmax(fmax(sh.d[par][0][0], sh.d[par][0][1]), fmax(sh.d[par][0][2], sh.d[par][0][3]));
-  par ^= 1;
+  const double mx = hz_weight_max(logw, dead, r0, S, sh, par);
   if (mx == -INFINITY) {  // no live path (uniform branch)
     if (tid < 12) st[tid] = nan;
     if (tid < nq) { q.qval[out * nq + tid] = nan; q.qrow[out * nq + tid] = -1; }
@@ -181,17 +85,7 @@ __global__ __launch_bounds__(HZ_THREADS) void horizon_reduce_kernel(HorizonBatch
     }
     return;
   }
-  for (int s = tid; s < S; s += HZ_THREADS) {
-    double a = logw ? logw[r0 + s] : 0.0;
-    if (a != a || dead[s]) a = -INFINITY;
-    float e = 0.f;
-    if (a != -INFINITY) {
-      const float d = (float)(a - mx);
-      e = d == 0.f ? 1.0f : expf(d);
-    }
-    es[s] = e;
-  }
-  __syncthreads();
+  hz_weight_fill(logw, dead, r0, S, mx, es);
 
   // rules 3 and 5: the sums in row order over the chunk tree
   const int c = ((S + HZ_THREADS - 1) / HZ_THREADS) | 1;
@@ -224,12 +118,7 @@ __global__ __launch_bounds__(HZ_THREADS) void horizon_reduce_kernel(HorizonBatch
     }
   }
   hz_sums(v, 11 + nb, sh, par);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) live += __shfl_xor(live, o, 64);
-  if (lane == 0) sh.i[par][0][wave] = live;
-  __syncthreads();
-  live = sh.i[par][0][0] + sh.i[par][0][1] + sh.i[par][0][2] + sh.i[par][0][3];
-  par ^= 1;
+  live = hz_count(live, sh, par);
   const double W = v[0], mean = v[2] / W;
   double var[1] = {0.0};
   for (int i = i0; i < i1; ++i) {
@@ -241,27 +130,7 @@ __global__ __launch_bounds__(HZ_THREADS) void horizon_reduce_kernel(HorizonBatch
   hz_sums(var, 1, sh, par);
 
   // rule 4: (x, s) ascending; rows without weight and the padding sort last
-  int n2 = 1;
-  while (n2 < S) n2 <<= 1;
-  for (int i = tid; i < n2; i += HZ_THREADS) {
-    key[i] = (i < S && es[i] > 0.f) ? xs[i] : INFINITY;
-    ix[i] = (uint16_t)i;
-  }
-  __syncthreads();
-  for (int k = 2; k <= n2; k <<= 1)
-    for (int jj = k >> 1; jj > 0; jj >>= 1) {
-      for (int t = tid; t < (n2 >> 1); t += HZ_THREADS) {
-        const int lo_i = ((t & ~(jj - 1)) << 1) | (t & (jj - 1)), hi_i = lo_i | jj;
-        const double ka = key[lo_i], kb = key[hi_i];
-        const uint16_t ia = ix[lo_i], ib = ix[hi_i];
-        const bool gt = ka > kb || (ka == kb && ia > ib);
-        if (gt == ((lo_i & k) == 0)) {
-          key[lo_i] = kb; key[hi_i] = ka;
-          ix[lo_i] = ib; ix[hi_i] = ia;
-        }
-      }
-      __syncthreads();
-    }
+  hz_sort(xs, es, S, key, ix);
   if (tid == 0) {
     st[0] = mean;
     st[1] = var[0] / W;
@@ -283,22 +152,7 @@ __global__ __launch_bounds__(HZ_THREADS) void horizon_reduce_kernel(HorizonBatch
 
   // the inclusive prefix of the weights in sorted order, over the same tree on the first `live` places
   const int p0 = min(tid * c, live), p1 = min(tid * c + c, live);
-  double inc = 0.0;
-  for (int i = p0; i < p1; ++i) inc += (double)es[ix[i]];
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const double m = __shfl_up(inc, o, 64);
-    if (lane >= o) inc += m;
-  }
-  double ex = __shfl_up(inc, 1, 64);
-  if (lane == 0) ex = 0.0;
-  if (lane == 63) sh.d[par][0][wave] = inc;
-  __syncthreads();
-  {
-    const double w0 = sh.d[par][0][0], w1 = sh.d[par][0][1], w2 = sh.d[par][0][2];
-    ex += wave == 0 ? 0.0 : wave == 1 ? w0 : wave == 2 ? (w0 + w1) : ((w0 + w1) + w2);
-  }
-  par ^= 1;
+  const double ex = hz_sorted_prefix(es, ix, p0, p1, sh, par);
   for (int k = 0; k < nq; ++k) {
     const double target = batch.level[k] * W;
     int pos = live;

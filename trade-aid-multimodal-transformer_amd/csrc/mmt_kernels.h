@@ -396,6 +396,29 @@ struct HorizonBatch { HorizonProblem p[MMT_MAX_GROUP]; double level[MMT_HZ_MAX_Q
 hipError_t mmt_launch_horizon(const HorizonBatch& b, int n, void* scratch, int64_t rows, int64_t per, int batch,
                               int samples, int steps, const double* logw, hipStream_t s);
 
+// Scores of horizon forecasts (mmt_horizon_score, mmt_horizon_score.hip). The scratch of problem `index` holds what
+// mmt_horizon_stats' holds over batch * samples + batch rows (the realised row of prompt b is row batch * samples + b)
+// and, behind it, the records [batch, steps, 8] of a problem whose caller passed none. The launcher validates
+// nothing: the C entry does.
+struct HorizonScoreProblem {
+  const int64_t* tok; int64_t tok_stride;
+  const int64_t* real; int64_t real_stride;
+  const double* values;
+  const int64_t* origin; int64_t origin_stride;                   // not read for a percent series
+  const int64_t* real_origin; int64_t real_origin_stride;         // not read for a percent series
+  const double* stats; const double* qval; const double* hit;     // the forecast; qval / hit: null with nq / nb == 0
+  double* rec; double* pin; double* bs;                           // rec: the caller's or the scratch's
+  double* agg; double* aggq; double* aggb; double* pit;
+  double barrier[MMT_HZ_MAX_B];
+  int V, is_percent, index;
+};
+struct HorizonScoreBatch { HorizonScoreProblem p[MMT_MAX_GROUP]; double level[MMT_HZ_MAX_Q]; int nq, nb; };
+// walk, grid (ceil((rows + batch) / 256), n), reduce, grid (batch * steps, n), tables, grid (steps, n); rows = batch *
+// samples, samples <= 4096, `per` the bytes of one problem's scratch
+hipError_t mmt_launch_horizon_score(const HorizonScoreBatch& b, int n, void* scratch, int64_t per, int batch,
+                                    int samples, int steps, int bins, int accumulate, const double* logw,
+                                    hipStream_t s);
+
 // Evaluation at every position (mmt_eval_positions, mmt_evalpos.hip). Row r = b * T + t. The launchers validate
 // nothing: the C entry does. `rec` is the caller's record buffer or the problem's place in the scratch, `part` the
 // problem's per-position partial tables [T][10 bins] in the scratch.

@@ -5,6 +5,10 @@ heads over all B x T rows an evaluation forward has written, not only the last p
     PositionMetrics(values, is_percent, ...).add(...) / .result() / .summary_lines(names)
                                                                                tables accumulated over many batches
 
+Scores of horizon forecasts against the realised series (include/mmt.h: mmt_horizon_score), accumulated the same way:
+
+    RolloutMetrics().add(scores) / .result() / .summary_lines(names)            scores: what generate(realised=) returns
+
 Everything runs in the library's kernels; there is no torch formulation behind it. `add` launches and returns: the
 one device-to-host read is in `result`."""
 import ctypes
@@ -274,3 +278,128 @@ class PositionMetrics:
         if len(names) != len(res):
             raise ValueError(f"PositionMetrics.summary_lines: name must hold {len(res)} names, got {len(names)}")
         return [f"  - {n:<30}{summary_text(r)}" for n, r in zip(names, res)]
+
+
+# ------------------------------------------------------------------------------------------
+# Scores of horizon forecasts (mmt_horizon_score) over many evaluation batches
+# ------------------------------------------------------------------------------------------
+ROLLOUT_TABLES = ("agg", "aggq", "aggb", "pit_hist")
+
+
+def _div(a, n):
+    with np.errstate(all="ignore"):
+        return np.where(n > 0, a / np.where(n > 0, n, 1.0), np.nan)
+
+
+def derive_rollout(agg, aggq, aggb, pit, quantiles, barriers=()):
+    """The numbers of one modality per step from its tables (numpy fp64: agg [N, 10], aggq [N, Q, 2], aggb [N, nb, 3],
+    pit [N, bins]; include/mmt.h, rule 8 of mmt_horizon_score). Returns a dict of arrays over the N steps: count;
+    crps (mean) and skill = 1 - sum CRPS / sum |x*| (against a forecast of no change; NaN where nothing moved); mae
+    and rmse of the forecast mean, spread (the root of the mean forecast variance, to set against rmse); coverage [N,
+    Q] (the rate of x* <= q_k, to set against quantiles[k]) and pinball [N, Q]; brier, hit_forecast, hit_observed [N,
+    nb] (the mean Brier score and the two sides of the reliability of a barrier's probability); sign_accuracy and
+    step_accuracy (hits of the most likely sign of the cumulative change / of the step), sign_mass and step_mass (the
+    mean mass on what came); pit_hist [N, bins] (the counts over their sum) and pit_deviation (half the L1 distance of
+    pit_hist from uniform: 0 for a calibrated forecast, towards 1 for a useless one). A mean over nothing is NaN."""
+    agg, aggq = np.asarray(agg, np.float64), np.asarray(aggq, np.float64)
+    aggb, pit = np.asarray(aggb, np.float64), np.asarray(pit, np.float64)
+    n = agg[:, 0]
+    bins = pit.shape[1]
+    hist = _div(pit, pit.sum(axis=1, keepdims=True))
+    return {"agg": agg, "aggq": aggq, "aggb": aggb, "pit": pit, "quantiles": [float(q) for q in quantiles],
+            "barriers": [float(u) for u in barriers], "count": n, "crps": _div(agg[:, 1], n),
+            "skill": 1.0 - _div(agg[:, 1], agg[:, 2]), "mae": _div(agg[:, 3], n), "rmse": np.sqrt(_div(agg[:, 4], n)),
+            "spread": np.sqrt(_div(agg[:, 9], n)), "coverage": _div(aggq[:, :, 1], n[:, None]),
+            "pinball": _div(aggq[:, :, 0], n[:, None]), "brier": _div(aggb[:, :, 0], n[:, None]),
+            "hit_forecast": _div(aggb[:, :, 1], n[:, None]), "hit_observed": _div(aggb[:, :, 2], n[:, None]),
+            "sign_mass": _div(agg[:, 5], n), "sign_accuracy": _div(agg[:, 6], n), "step_mass": _div(agg[:, 7], n),
+            "step_accuracy": _div(agg[:, 8], n), "pit_hist": hist,
+            "pit_deviation": 0.5 * np.abs(hist - 1.0 / bins).sum(axis=1)}
+
+
+def rollout_steps(N):
+    """The steps a summary shows: 1, N / 2 and N (as indices 0, N // 2 - 1, N - 1; fewer where they coincide)."""
+    return sorted({0, max(N // 2 - 1, 0), N - 1}) if N > 0 else []
+
+
+def rollout_summary_text(r, steps=None):
+    """One modality's line, without its name: per shown step the CRPS skill against no change, the coverage of every
+    quantile level and the accuracy of the most likely sign of the cumulative change."""
+    N = len(r["count"])
+    parts = []
+    for j in (rollout_steps(N) if steps is None else steps):
+        if not r["count"][j] > 0:
+            parts.append(f"step {j + 1}: no scored prompt")
+            continue
+        sk = r["skill"][j]
+        cov = " ".join(f"{_pct(q, 2)}:{_pct(float(c))}" for q, c in zip(r["quantiles"], r["coverage"][j]))
+        parts.append(f"step {j + 1}: skill {'n/a' if sk != sk else format(sk, '.3f')} | coverage {cov} | "
+                     f"direction {_pct(float(r['sign_accuracy'][j]))} | PIT dev {r['pit_deviation'][j]:.3f}")
+    return " || ".join(parts) if parts else "no steps"
+
+
+class RolloutMetrics:
+    """The tables of mmt_horizon_score accumulated on the device over many evaluation batches. `add` takes what
+    generate(realised=) returned last, {modality: score dict}, and adds each modality's four tables to its own, which
+    the first `add` allocates (one fp64 addition per cell, on the device, no sync); every later `add` must bring the
+    same modalities and table shapes. quantiles / barriers: the levels and {modality: barriers} the scores were made
+    with, for the report. `result` is one device-to-host read."""
+
+    def __init__(self, quantiles=(0.05, 0.5, 0.95), barriers=None):
+        self.quantiles = [float(q) for q in quantiles]
+        self.barriers = dict(barriers or {})
+        self.batches = 0
+        self._keys = None
+
+    def add(self, scores):
+        if not isinstance(scores, dict) or not scores or any(
+                not isinstance(d, dict) or any(k not in d for k in ROLLOUT_TABLES) for d in scores.values()):
+            raise ValueError("RolloutMetrics.add: scores must be the {modality: dict} generate(realised=) returns")
+        keys = sorted(scores)
+        shapes = [tuple(tuple(scores[i][k].shape) for k in ROLLOUT_TABLES) for i in keys]
+        if any(s[1][1] != len(self.quantiles) for s in shapes):
+            raise ValueError(f"RolloutMetrics.add: the scores hold {shapes[0][1][1]} quantile levels, this object "
+                             f"{len(self.quantiles)}")
+        if self._keys is None:
+            self._keys, self._shapes = keys, shapes
+            sizes = [[int(np.prod(s)) for s in sh] for sh in shapes]
+            dev = scores[keys[0]]["agg"].device
+            self._flat = torch.zeros(sum(sum(s) for s in sizes), dtype=torch.float64, device=dev)
+            self._views, o = [], 0
+            for sh, sz in zip(shapes, sizes):
+                row = []
+                for s, n in zip(sh, sz):
+                    row.append(self._flat[o:o + n].view(s))
+                    o += n
+                self._views.append(row)
+        elif keys != self._keys or shapes != self._shapes:
+            raise ValueError("RolloutMetrics.add: the scores do not match the first batch's modalities and shapes")
+        for row, i in zip(self._views, keys):
+            for dst, k in zip(row, ROLLOUT_TABLES):
+                dst.add_(scores[i][k])
+        self.batches += 1
+
+    def result(self):
+        """{modality: derive_rollout(...)} from one device-to-host read of all tables. Before any `add`: {}."""
+        if self._keys is None:
+            return {}
+        host = self._flat.cpu()
+        out, o = {}, 0
+        for i, sh in zip(self._keys, self._shapes):
+            tabs = []
+            for s in sh:
+                n = int(np.prod(s))
+                tabs.append(host[o:o + n].view(s).numpy())
+                o += n
+            out[i] = derive_rollout(*tabs, self.quantiles, self.barriers.get(i, ()))
+        return out
+
+    def summary_lines(self, names, result=None):
+        """The lines to print, one per modality: `names` is {modality: name} or a list in ascending modality order."""
+        res = self.result() if result is None else result
+        if not isinstance(names, dict):
+            names = list(names)
+            if len(names) != len(res):
+                raise ValueError(f"RolloutMetrics.summary_lines: names must hold {len(res)} names, got {len(names)}")
+            names = dict(zip(sorted(res), names))
+        return [f"  - {names[i]:<30}{rollout_summary_text(res[i])}" for i in sorted(res)]

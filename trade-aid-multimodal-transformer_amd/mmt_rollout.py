@@ -49,6 +49,7 @@ class JointPlan:
         self.points = resample_points(N, resample_every) if evidence == "resample" else []
         self.forecast = None  # check_forecast's result: the forecast settings, None when off
         self.horizon = None  # check_horizon's result: the horizon settings, None when off
+        self.realised = None  # check_realised's result: the realised series to score the horizon against, or None
 
 
 EVIDENCE_MODES = (None, "weights", "resample")
@@ -127,8 +128,31 @@ def check_horizon(horizon, generated, vocab_sizes, forecast=None):
     return out
 
 
+def check_realised(realised, horizon, B, N):
+    """generate's realised= against the plan's horizon (check_horizon's result): None (off), or a dict {i: int64 [B, N]
+    tokens}, i a generated modality with values, the series that followed each prompt. Returns None or the dict, its
+    keys ascending; ValueError for anything else, and without horizon= (the scores are those of the horizon forecast).
+    The tokens' range is not read back: a row with a token outside the vocabulary is dead on the device."""
+    if realised is None:
+        return None
+    if horizon is None:
+        raise ValueError("generate: realised= scores the horizon forecast: pass horizon= (with the values of the "
+                         "modalities to score)")
+    if not isinstance(realised, dict) or not realised:
+        raise ValueError("generate: realised must be a dict {modality: int64 [B, N] tokens}")
+    for i, t in realised.items():
+        if isinstance(i, bool) or not isinstance(i, int) or i not in horizon["modalities"]:
+            raise ValueError(f"generate: realised names modality {i!r}, which is not a generated modality with values "
+                             f"(horizon covers {horizon['modalities']})")
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.long:
+            raise ValueError(f"generate: realised[{i}] must be an int64 tensor")
+        if tuple(t.shape) != (B, N):
+            raise ValueError(f"generate: realised[{i}] must be [{B}, {N}], got {tuple(t.shape)}")
+    return {i: realised[i] for i in sorted(realised)}
+
+
 def plan_joint(modality_to_generate, given, vocab_sizes, prompt_shapes, max_new_tokens, num_samples=None,
-               evidence=None, resample_every=1, ess_threshold=0.5, forecast=None, horizon=None):
+               evidence=None, resample_every=1, ess_threshold=0.5, forecast=None, horizon=None, realised=None):
     """generate's `modality_to_generate` and `given` as per-modality roles, every refusal of the list form that
     needs no device in one place. An int (the int form: one modality sampled, generate as it always ran) returns
     None, and refuses `given`. A sequence of distinct ints, even of one, or "all" is the list form (a joint
@@ -170,6 +194,9 @@ def plan_joint(modality_to_generate, given, vocab_sizes, prompt_shapes, max_new_
         if horizon is not None and horizon is not False:
             raise ValueError(f"generate: horizon= needs the list form of modality_to_generate: pass [{g}] (a "
                              "sequence, even of one, or \"all\")")
+        if realised is not None:
+            raise ValueError(f"generate: realised= needs the list form of modality_to_generate: pass [{g}] (a "
+                             "sequence, even of one, or \"all\") and horizon=")
         return None
     if isinstance(g, str):
         if g != "all":
@@ -224,6 +251,7 @@ def plan_joint(modality_to_generate, given, vocab_sizes, prompt_shapes, max_new_
         if num_samples > MS.HORIZON_MAX_SAMPLES:
             raise ValueError(f"generate: horizon= sorts at most {MS.HORIZON_MAX_SAMPLES} samples per prompt, got "
                              f"num_samples={num_samples}")
+    plan.realised = check_realised(realised, plan.horizon, B, N)
     return plan
 
 
@@ -383,7 +411,8 @@ def rollout(model, idx_list, plan, use_cache, temperature, top_k, top_p, seed, r
     columns. With plan.forecast a step also issues one mmt_forecast_multi over the generated modalities' views, after
     the sampling and scoring and before a resampling, into column j of preallocated [Bp, N, V_i] buffers; one
     mmt_sample.pmf_stats follows the loop. With plan.horizon one mmt_sample.horizon_stats follows the loop too, over
-    the sequence buffers' new columns. Returns seqs, or the tuple (seqs[, {i: logprobs}][, ev][, fc][, hz])."""
+    the sequence buffers' new columns, and with plan.realised one mmt_sample.horizon_score after it, on the same
+    buffers. Returns seqs, or the tuple (seqs[, {i: logprobs}][, ev][, fc][, hz][, sc])."""
     flat = model.flat_params
     dev = flat.device
     M, T, N, n0, gen, Vs = model.num_modalities, model.block_size, plan.N, plan.n0, plan.generated, model.vocab_sizes
@@ -560,9 +589,25 @@ def rollout(model, idx_list, plan, use_cache, temperature, top_k, top_p, seed, r
                                   is_percent=[hz["is_percent"].get(i, False) for i in mods],
                                   origin=[bufs[i][:, n0 - 1] for i in mods], logw=logw if giv else None,
                                   quantiles=hz["quantiles"], barriers=[b + [1.0] * (nbar - len(b)) for b in bars])
+        rz = plan.realised
+        if rz is not None:
+            # the scores of that forecast against the series that followed each prompt: the same buffers, weights,
+            # levels and padded barriers, the origin of the realised row the prompt's last token
+            at = [mods.index(i) for i in rz]
+            res_sc = MS.horizon_score([bufs[i][:, n0:] for i in rz], [rz[i].to(dev).contiguous() for i in rz],
+                                      samples=Sp, values=[hz["values"][i] for i in rz],
+                                      is_percent=[hz["is_percent"].get(i, False) for i in rz],
+                                      origin=[bufs[i][:, n0 - 1] for i in rz],
+                                      realised_origin=[prompts[i][:, -1] for i in rz], logw=logw if giv else None,
+                                      forecast=[res_hz[k] for k in at], quantiles=hz["quantiles"],
+                                      barriers=[bars[k] + [1.0] * (nbar - len(bars[k])) for k in at])
+            for d, k in zip(res_sc, at):
+                d["brier"], d["aggb"] = d["brier"][..., :len(bars[k])], d["aggb"][:, :len(bars[k])]
         for d, b in zip(res_hz, bars):
             d["hit"] = d["hit"][..., :len(b)]
         out.append(dict(zip(mods, res_hz)))
+        if rz is not None:
+            out.append(dict(zip(rz, res_sc)))
     return out[0] if len(out) == 1 else tuple(out)
 
 

@@ -617,6 +617,198 @@ def horizon_stats(tokens_list, *, samples, values, is_percent=False, origin=None
     return [horizon_dict(o) for o in outs]
 
 
+SCORE_FIELDS = ("realised", "crps", "pit", "mean_error", "p_realised_sign", "p_realised_step", "realised_high",
+                "realised_low")  # sc[..., k] of mmt_horizon_score
+SCORE_AGG_FIELDS = ("count", "crps", "abs_realised", "abs_error", "sq_error", "p_realised_sign", "sign_hits",
+                    "p_realised_step", "step_hits", "var")  # agg[..., k]
+SCORE_MAX_BINS = 64
+
+
+def check_bins(bins):
+    """The PIT bins as mmt_horizon_score takes them: an int in 1..64; ValueError otherwise."""
+    if isinstance(bins, bool) or not isinstance(bins, int) or not 1 <= bins <= SCORE_MAX_BINS:
+        raise ValueError(f"horizon score: bins must be an int in 1..{SCORE_MAX_BINS}, got {bins!r}")
+    return bins
+
+
+class HorizonScoreLaunch:
+    """The host arrays of one mmt_horizon_score call over P problems (include/mmt.h), made once: the caller fills the
+    raw addresses `tok` / `values` / `origin` / `real` / `real_origin` (inputs), `stats` / `qval` / `hit` (the
+    forecast of a mmt_horizon_stats call on the same inputs), `sc` (0 = in the scratch) / `pin` / `bs` / `agg` /
+    `aggq` / `aggb` / `pit` (outputs) and the strides, and calls `run`. barriers: P lists of the same length."""
+
+    def __init__(self, V, tok_stride, real_stride, is_percent, quantiles, barriers, bins=10):
+        P = self.P = len(V)
+        n = max(1, P)
+        q = check_quantiles(quantiles)
+        bars = [check_barriers(b) for b in barriers]
+        if len(bars) != P or len({len(b) for b in bars}) > 1:
+            raise ValueError("horizon score: one list of barriers per problem, all of one length")
+        self.nq, self.nb, self.bins = len(q), len(bars[0]) if bars else 0, check_bins(bins)
+        self.V = (ctypes.c_int32 * n)(*[int(v) for v in V])
+        self.tok = (ctypes.c_void_p * n)()
+        self.tok_stride = (ctypes.c_int64 * n)(*[int(x) for x in tok_stride])
+        self.values = (ctypes.c_void_p * n)()
+        self.is_percent = (ctypes.c_int32 * n)(*[1 if x else 0 for x in is_percent])
+        self.origin = (ctypes.c_void_p * n)()
+        self.origin_stride = (ctypes.c_int64 * n)(*([1] * P))
+        self.real = (ctypes.c_void_p * n)()
+        self.real_stride = (ctypes.c_int64 * n)(*[int(x) for x in real_stride])
+        self.real_origin = (ctypes.c_void_p * n)()
+        self.real_origin_stride = (ctypes.c_int64 * n)(*([1] * P))
+        self.levels = (ctypes.c_double * max(1, self.nq))(*q)
+        self._bars = [(ctypes.c_double * max(1, self.nb))(*b) for b in bars]  # kept alive: `barriers` points at them
+        self.barriers = (ctypes.c_void_p * n)(*[ctypes.addressof(b) for b in self._bars])
+        for name in ("stats", "qval", "hit", "sc", "pin", "bs", "agg", "aggq", "aggb", "pit"):
+            setattr(self, name, (ctypes.c_void_p * n)())
+
+    def scratch_bytes(self, L, batch, samples, steps):
+        """mmt_horizon_score_scratch_bytes for this launch's problems; ValueError for a shape the entry refuses."""
+        n = L.mmt_horizon_score_scratch_bytes(self.P, int(batch), int(samples), int(steps))
+        if n < 0:
+            raise ValueError(f"horizon score: {batch} prompts x {samples} samples x {steps} steps is a shape the "
+                             f"entry refuses (at most {HORIZON_MAX_SAMPLES} samples per prompt)")
+        return int(n)
+
+    def run(self, L, stream, batch, samples, steps, logw_ptr, scratch_ptr, scratch_bytes, accumulate=False):
+        """One mmt_horizon_score (logw_ptr: a raw address, 0 = absent). Raises MmtError on a non-zero status."""
+        rc = L.mmt_horizon_score(stream, self.P, batch, samples, steps, self.V, self.tok, self.tok_stride, self.values,
+                                 self.is_percent, self.origin, self.origin_stride, self.real, self.real_stride,
+                                 self.real_origin, self.real_origin_stride, logw_ptr or None, self.nq, self.levels,
+                                 self.nb, self.barriers, self.stats, self.qval, self.hit, self.bins,
+                                 1 if accumulate else 0, self.sc, self.pin, self.bs, self.agg, self.aggq, self.aggb,
+                                 self.pit, scratch_ptr, scratch_bytes)
+        if rc != 0:
+            raise ML.MmtError(f"mmt_horizon_score failed (status {rc})")
+
+
+def horizon_score_outputs(P, batch, steps, nq, nb, bins, dev):
+    """The output tensors of one mmt_horizon_score call, per problem: (sc, pin, bs, agg, aggq, aggb, pit). The tables
+    start at zero: a call with no step or no prompt launches nothing."""
+    f64 = dict(dtype=torch.float64, device=dev)
+    return [(torch.empty(batch, steps, 8, **f64), torch.empty(batch, steps, nq, **f64),
+             torch.empty(batch, steps, nb, **f64), torch.zeros(steps, 10, **f64), torch.zeros(steps, nq, 2, **f64),
+             torch.zeros(steps, nb, 3, **f64), torch.zeros(steps, bins, **f64)) for _ in range(P)]
+
+
+def horizon_score_dict(outs):
+    """One problem's outputs as the dict generate(realised=) and horizon_score return: the SCORE_FIELDS as fp64 [B, N],
+    "pinball" fp64 [B, N, Q], "brier" fp64 [B, N, nb], and the tables "agg" [N, 10] (SCORE_AGG_FIELDS), "aggq" [N, Q,
+    2], "aggb" [N, nb, 3], "pit_hist" [N, bins]."""
+    sc, pin, bs, agg, aggq, aggb, pit = outs
+    d = {name: sc[..., k] for k, name in enumerate(SCORE_FIELDS)}
+    d.update(pinball=pin, brier=bs, agg=agg, aggq=aggq, aggb=aggb, pit_hist=pit)
+    return d
+
+
+def bind_score_forecast(sl, p, stats, qval, hit):
+    """Point problem p of a HorizonScoreLaunch at the forecast tensors of a mmt_horizon_stats call."""
+    sl.stats[p] = stats.data_ptr() if stats.numel() else None
+    sl.qval[p] = qval.data_ptr() if qval.numel() else None
+    sl.hit[p] = hit.data_ptr() if hit.numel() else None
+
+
+def bind_score_outputs(sl, p, outs):
+    (sl.sc[p], sl.pin[p], sl.bs[p], sl.agg[p], sl.aggq[p], sl.aggb[p],
+     sl.pit[p]) = [x.data_ptr() if x.numel() else None for x in outs]
+
+
+def horizon_score(tokens_list, realised_list, *, samples, values, is_percent=False, origin=None, realised_origin=None,
+                  logw=None, forecast, quantiles=(0.05, 0.5, 0.95), barriers=None, bins=10):
+    """Scores of horizon forecasts against the realised series (mmt_horizon_score, include/mmt.h). tokens_list, samples,
+    values, is_percent, origin, logw, quantiles and barriers: what horizon_stats was given. realised_list: P int64 [B,
+    N] tensors, the tokens that followed prompt b (rows may be strided); realised_origin: None or a list of P entries,
+    each None (a percent series) or an int64 [B] tensor (the token before the realised ones). forecast: the list of
+    P dicts horizon_stats returned for these inputs; it is read, never recomputed. bins: the cells of the PIT histogram,
+    1..64. Returns a list of P dicts (horizon_score_dict): per (prompt, step) the realised change, the CRPS and
+    mid-PIT of the weighted paths, the error of the mean, the mass the forecast gave the realised sign and step
+    direction, the realised running high and low, the pinball loss per level and the Brier score per barrier; per
+    step the tables RolloutMetrics accumulates. No sync."""
+    P = len(tokens_list)
+    q = check_quantiles(quantiles)
+    check_bins(bins)
+    S = int(samples)
+    if S < 1:
+        raise ValueError(f"horizon_score: samples must be >= 1, got {samples!r}")
+    if S > HORIZON_MAX_SAMPLES:
+        raise ValueError(f"horizon_score: at most {HORIZON_MAX_SAMPLES} samples per prompt, got {S}")
+    if not isinstance(values, (list, tuple)) or len(values) != P:
+        raise ValueError(f"horizon_score: values must be a list of {P} vocabularies")
+    if not isinstance(realised_list, (list, tuple)) or len(realised_list) != P:
+        raise ValueError(f"horizon_score: realised_list must hold {P} tensors")
+    if not isinstance(forecast, (list, tuple)) or len(forecast) != P:
+        raise ValueError(f"horizon_score: forecast must be the list of {P} dicts horizon_stats returned")
+    pct = _per_problem(is_percent, P, "is_percent")
+    org = _per_problem(origin, P, "origin") if isinstance(origin, (list, tuple)) else [origin] * P
+    rorg = (_per_problem(realised_origin, P, "realised_origin") if isinstance(realised_origin, (list, tuple))
+            else [realised_origin] * P)
+    bars = [[] for _ in range(P)] if barriers is None else [check_barriers(b) for b in barriers]
+    if len(bars) != P:
+        raise ValueError(f"horizon_score: barriers must be a list of {P} lists")
+    if P == 0:
+        return []
+    R, N = tokens_list[0].shape[0], tokens_list[0].shape[1] if tokens_list[0].dim() == 2 else -1
+    dev = tokens_list[0].device
+    if R % S:
+        raise ValueError(f"horizon_score: {R} rows are no multiple of samples={samples}")
+    B = R // S
+    if logw is not None and (logw.dtype != torch.float64 or logw.shape != (R,) or not logw.is_contiguous()
+                             or logw.device != dev):
+        raise ValueError(f"horizon_score: logw must be a contiguous fp64 [{R}] tensor on the GPU")
+    nq, nb = len(q), len(bars[0])
+    fc = []
+    for p, t in enumerate(tokens_list):
+        if t.dim() != 2 or t.dtype != torch.int64 or t.device.type != "cuda" or t.device != dev or (
+                tuple(t.shape) != (R, N)) or (N > 1 and t.stride(1) != 1) or (R > 1 and t.stride(0) < N):
+            raise ValueError("horizon_score: every tokens must be an int64 [rows, N] tensor on the same GPU, the "
+                             "elements of a row contiguous")
+        y = realised_list[p]
+        if not torch.is_tensor(y) or y.dim() != 2 or y.dtype != torch.int64 or y.device != dev or (
+                tuple(y.shape) != (B, N)) or (N > 1 and y.stride(1) != 1) or (B > 1 and y.stride(0) < N):
+            raise ValueError(f"horizon_score: every realised must be an int64 [{B}, {N}] tensor on the same GPU, the "
+                             "elements of a row contiguous")
+        if values[p] is None:
+            raise ValueError(f"horizon_score: problem {p} has no values")
+        if not pct[p]:
+            o, ro = org[p], rorg[p]
+            if o is None or o.dtype != torch.int64 or tuple(o.shape) != (R,) or o.device != dev:
+                raise ValueError(f"horizon_score: a value series needs an int64 [{R}] origin on the GPU (problem {p})")
+            if ro is None or ro.dtype != torch.int64 or tuple(ro.shape) != (B,) or ro.device != dev:
+                raise ValueError(f"horizon_score: a value series needs an int64 [{B}] realised_origin on the GPU "
+                                 f"(problem {p})")
+        f = forecast[p]
+        try:
+            st = torch.stack([f[k] for k in HORIZON_FIELDS], dim=-1).contiguous()
+            qv, ht = f["quantile_values"].contiguous(), f["hit"].contiguous()
+        except (KeyError, TypeError, RuntimeError):
+            raise ValueError(f"horizon_score: forecast[{p}] is not a dict horizon_stats returned") from None
+        if tuple(st.shape) != (B, N, 12) or tuple(qv.shape) != (B, N, nq) or tuple(ht.shape) != (B, N, nb) or any(
+                x.dtype != torch.float64 or x.device != dev for x in (st, qv, ht)):
+            raise ValueError(f"horizon_score: forecast[{p}] does not have the shapes of {B} prompts, {N} steps, "
+                             f"{nq} quantiles and {nb} barriers")
+        fc.append((st, qv, ht))
+    sl = HorizonScoreLaunch([len(torch.as_tensor(v).reshape(-1)) for v in values],
+                            [max(int(t.stride(0)), N) if R > 1 else max(N, 1) for t in tokens_list],
+                            [max(int(y.stride(0)), N) if B > 1 else max(N, 1) for y in realised_list], pct, q, bars,
+                            bins)
+    outs = horizon_score_outputs(P, B, N, nq, nb, bins, dev)
+    keep = []
+    for p, t in enumerate(tokens_list):
+        keep.append(check_values(values[p], sl.V[p]).to(dev))
+        sl.tok[p], sl.values[p], sl.real[p] = t.data_ptr(), keep[-1].data_ptr(), realised_list[p].data_ptr()
+        if not pct[p]:
+            sl.origin[p], sl.origin_stride[p] = org[p].data_ptr(), max(int(org[p].stride(0)), 1)
+            sl.real_origin[p], sl.real_origin_stride[p] = rorg[p].data_ptr(), max(int(rorg[p].stride(0)), 1)
+        bind_score_forecast(sl, p, *fc[p])
+        bind_score_outputs(sl, p, outs[p])
+    L = ML.lib()
+    nbytes = sl.scratch_bytes(L, B, S, N)
+    scratch = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        sl.run(L, ML.stream_ptr(dev), B, S, N, logw.data_ptr() if logw is not None else 0, scratch.data_ptr(), nbytes)
+    return [horizon_score_dict(o) for o in outs]
+
+
 RESAMPLE_MAX_SAMPLES = 4096  # csrc/mmt_evidence.hip RS_MAX_S: the S weights of a prompt stay in LDS
 
 

@@ -498,7 +498,7 @@ class MultimodalTransformer(nn.Module):
     def generate(self, idx_list, max_new_tokens=1, modality_to_generate=0, use_cache=True, sample_fn=None, *,
                  temperature=None, top_k=None, top_p=None, seed=None, return_logprobs=False, logits_hook=None,
                  num_samples=None, given=None, evidence=None, resample_every=1, ess_threshold=0.5, forecast=None,
-                 horizon=None):
+                 horizon=None, realised=None):
         """model.py:404-446: per new token, the logits of the last position of the (block_size
         cropped) context, a sample from the softmax of the target modality's last logits
         (torch.multinomial, as the reference; `sample_fn(probs) -> [B, 1]` overrides it), appended;
@@ -598,11 +598,27 @@ class MultimodalTransformer(nn.Module):
         ancestors, so every step's statistic is that of the surviving histories under the final weights: the
         SMOOTHED estimate (given the whole series), not the filtered one forecast= reports; after heavy resampling
         the early steps rest on few distinct ancestors. num_samples > 4096 is refused before the prefill. Sequences,
-        log-probabilities, `ev` and `fc` are bit-identical to the call without horizon=."""
+        log-probabilities, `ev` and `fc` are bit-identical to the call without horizon=.
+
+        Scored horizons (list form only, needs horizon=): realised={i: int64 [B, N]}, i a generated modality with
+        values, is the series that followed each prompt (a backtest: the prompt is the head of a known window, the
+        realised row its tail). One mmt_horizon_score call (include/mmt.h) follows the mmt_horizon_stats call, on the
+        same buffers, weights, levels and barriers, the origin of both the column before the new ones, and adds a last
+        element `sc` = {i: {...}} after `hz`. Keys, fp64 [Bp, N]: "realised" (the realised cumulative change x*),
+        "crps" (of the weighted paths at x*), "pit" (mid-PIT), "mean_error" (hz mean - x*), "p_realised_sign" and
+        "p_realised_step" (the mass hz gave the sign of x* and the direction of the realised step), "realised_high" /
+        "realised_low"; "pinball" fp64 [Bp, N, Q] (of hz's quantile_values) and "brier" fp64 [Bp, N, nb] (of hz's hit);
+        and the per-step tables "agg" [N, 10], "aggq" [N, Q, 2], "aggb" [N, nb, 3], "pit_hist" [N, 10] that
+        mmt_eval.RolloutMetrics accumulates over calls. A prompt whose realised row holds a token outside the
+        vocabulary, or that has no live path, has NaN scores and enters no table. Refused (ValueError) without
+        horizon=, in the int form, for a key that is not a generated modality with values and for a tensor that is
+        not int64 [B, N]. Sequences, log-probabilities, `ev`, `fc` and `hz` are bit-identical to the call without
+        realised=."""
         if num_samples is not None:
             num_samples = check_num_samples(num_samples)
         plan = plan_joint(modality_to_generate, given, self.vocab_sizes, [tuple(s.shape) for s in idx_list],
-                          max_new_tokens, num_samples, evidence, resample_every, ess_threshold, forecast, horizon)
+                          max_new_tokens, num_samples, evidence, resample_every, ess_threshold, forecast, horizon,
+                          realised)
         if plan is not None:
             if sample_fn is not None:
                 raise ValueError("generate: sample_fn cannot be combined with a joint rollout (a list of modalities "

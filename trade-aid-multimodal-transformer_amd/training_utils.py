@@ -28,7 +28,11 @@ lines and log lines. What changed underneath:
     device->host copy, instead of B*V `.item()` syncs;
   * estimate_loss with the build-only key eval_positions: all also scores every position of the logits it has
     (mmt_eval.PositionMetrics: direction, log score, calibration) and prints one more block; with the default,
-    last, nothing of that is imported or run.
+    last, nothing of that is imported or run;
+  * estimate_loss with the build-only key eval_rollout_paths > 0 also rolls that many paths from the first
+    block_size - eval_rollout_steps tokens of every evaluation window and scores the horizon forecast against the
+    window's own tail (generate(realised=), mmt_eval.RolloutMetrics: CRPS skill, quantile coverage, direction) and
+    prints one more block; with the default, 0, nothing of that is imported or run.
 """
 import ctypes
 import math
@@ -42,7 +46,8 @@ import torch
 
 import mmt_lib as ML
 from config_utils import (_get_batch_size, _get_block_size, _get_config, _get_device, _get_eval_iters,
-                          _get_eval_positions, _get_eval_positions_from)
+                          _get_eval_positions, _get_eval_positions_from, _get_eval_rollout_paths,
+                          _get_eval_rollout_seed, _get_eval_rollout_steps)
 
 __all__ = ["generate_batch_starting_indices", "get_batch", "estimate_loss", "calculate_evaluation_metrics"]
 
@@ -549,14 +554,45 @@ def _new_position_metrics(logits_list, yb_list):
     return pm, idx, names
 
 
+last_rollout_metrics = {}  # eval_rollout_paths > 0. Per state the tables and numbers of the latest estimate_loss
+
+
+def _new_rollout_metrics(xb_list):
+    """eval_rollout_paths > 0. The horizon settings of the scored rollouts over the modalities with a numeric
+    vocabulary, and a RolloutMetrics for them, made at the first batch of a state. Returns (metrics, horizon, names),
+    or (None, None, {}) when no modality is numeric."""
+    import mmt_eval
+    values, pct, names = {}, {}, {}
+    for i in range(min(num_modalities, len(xb_list))):
+        numeric, vt = _numeric_vocab(all_vocabularies[i], xb_list[i].device)
+        if not numeric:
+            continue
+        values[i] = vt.cpu()
+        pct[i] = bool(all_modality_params[i][3])
+        names[i] = all_modality_params[i][9] if all_modality_params[i][9] else f"Modality {i+1}"
+    if not values:
+        return None, None, {}
+    hz = {"values": values, "is_percent": pct}
+    return mmt_eval.RolloutMetrics(), hz, names
+
+
+def _rollout_seed(seed, state, k):
+    """The seed of the scored rollouts of evaluation iteration k: a fixed function of (eval_rollout_seed, state, k)."""
+    return ((seed * 1000003 + (0 if state == "train" else 1)) * 1000003 + k) & (2 ** 63 - 1)
+
+
 def estimate_loss(current_step=None, max_steps=None):
     out = {}
     every_position = _get_eval_positions() == "all"  # a bad key is refused before the model changes mode
     if every_position:
         _get_eval_positions_from()
+    rollout_paths = _get_eval_rollout_paths()
+    if rollout_paths:
+        rollout_steps, rollout_seed = _get_eval_rollout_steps(), _get_eval_rollout_seed()
     m.eval()
     for state in ["train", "val"]:
         pm = None
+        rm, rm_hz, rm_names = None, None, {}
         now = datetime.now()
         current_time = now.strftime("%H:%M:%S")
         step_info = f"Step {current_step}/{max_steps} | " if current_step is not None else ""
@@ -590,6 +626,20 @@ def estimate_loss(current_step=None, max_steps=None):
                         pm, pm_idx, pm_names = _new_position_metrics(logits_list, yb_list)
                     pm.add([logits_list[i].contiguous() for i in pm_idx], [xb_list[i].contiguous() for i in pm_idx],
                            [yb_list[i].contiguous() for i in pm_idx])
+                if rollout_paths:
+                    # a backtest on the window itself: roll the paths from its head, score the horizon forecast
+                    # against its tail. After everything that reads this iteration's logits; an explicit seed, so
+                    # neither Python's nor torch's generators move.
+                    if rm is None and rm_hz is None:
+                        rm, rm_hz, rm_names = _new_rollout_metrics(xb_list)
+                        rm_hz = rm_hz or False
+                    if rm is not None:
+                        cut = xb_list[0].shape[1] - rollout_steps
+                        res = m.generate([x[:, :cut] for x in xb_list], max_new_tokens=rollout_steps,
+                                         modality_to_generate="all", num_samples=rollout_paths,
+                                         seed=_rollout_seed(rollout_seed, state, k), horizon=rm_hz,
+                                         realised={i: xb_list[i][:, cut:].long() for i in rm_names})
+                        rm.add(res[-1])
         out[state] = (loss_sum.item() / n_losses) if n_losses else float("nan")
         disp = "Train Set" if state == "train" else "Val Set"
         print(f"\nDIRECTIONAL METRICS - {disp} (Correct/Total)")
@@ -611,6 +661,15 @@ def estimate_loss(current_step=None, max_steps=None):
                                             "t_begin": pm.t_begin, "batches": pm.batches}
             print(f"\nPOSITION METRICS - {disp} (positions {pm.t_begin}..{_get_block_size() - 1})")
             for line in pm.summary_lines(pm_names, pm_res):
+                print(line)
+        rm_res = None
+        if rm is not None:
+            rm_res = rm.result()
+            last_rollout_metrics[state] = {"indices": sorted(rm_names), "names": rm_names, "results": rm_res,
+                                           "paths": rollout_paths, "steps": rollout_steps, "batches": rm.batches}
+            print(f"\nROLLOUT METRICS - {disp} ({rollout_paths} paths, {rollout_steps} steps from position "
+                  f"{_get_block_size() - rollout_steps})")
+            for line in rm.summary_lines(rm_names, rm_res):
                 print(line)
         cfg = _get_config()
         output_file_name = cfg.get("output_file_name", "")
@@ -636,6 +695,11 @@ def estimate_loss(current_step=None, max_steps=None):
                     import mmt_eval
                     for name, r in zip(pm_names, pm_res):
                         f.write(f"   POSITION METRICS {disp} - {name}: {mmt_eval.summary_text(r)}\n")
+                if rm_res is not None:
+                    import mmt_eval
+                    for i in sorted(rm_res):
+                        f.write(f"   ROLLOUT METRICS {disp} - {rm_names[i]}: "
+                                f"{mmt_eval.rollout_summary_text(rm_res[i])}\n")
                 if state == "train":
                     f.write("\n")
         if state == "train":
