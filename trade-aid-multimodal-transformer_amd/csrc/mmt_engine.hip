@@ -124,52 +124,95 @@ struct FanPlan {
 
 }  // namespace
 
-// the FFN's ReLU' as bits written by ffn0 (16x fewer bytes than the bf16 hidden the ffn2 data
-// gradient reads back). MMT_RELU_BITS=1 or mmt_set_relu_bits(1) before mmt_create turns it on (latched
-// per context: the bit rows are allocated only then); off by default: on the final round-5 build the
-// bf16 aux measured faster (same box, profiles/r5am_relu_bits_final_ab.txt: C1 8.502 -> 8.477 ms,
-// target 19.770 -> 19.505 ms), where the first version had been 0.1-0.7 % faster than the aux
-static int g_relu_bits = mmt_env_int("MMT_RELU_BITS", 0);
-extern "C" int mmt_set_relu_bits(int on) {
-  const int old = g_relu_bits;
-  g_relu_bits = on;
-  return old;
-}
-// the FFN backward's dropout-masked bf16 residual-gradient copy (+ FFN output-bias gradient) in the
-// epilogue of the last cross-attention K/V dX launch into that gradient (1, default, env
-// MMT_DROP_COPY_FUSE) or a separate drop_copy pass (0)
-static int g_drop_copy_fuse = mmt_env_int("MMT_DROP_COPY_FUSE", 1);
-extern "C" int mmt_set_drop_copy_fuse(int on) {
-  const int old = g_drop_copy_fuse;
-  g_drop_copy_fuse = on;
-  return old;
-}
+// Every MMT_* environment variable the engine reads, with its default and its meaning (DESIGN.md §3 has the same
+// table). Read once, when the process first calls into the engine or a setter: nothing changes them after the
+// library is loaded. The five knobs with a setter (include/mmt.h) only start from their variable.
+namespace {
+struct Knobs {
+  // MMT_RELU_BITS / mmt_set_relu_bits: the FFN's ReLU' as bits written by ffn0 (16x fewer bytes than the bf16 hidden
+  // the ffn2 data gradient reads back). Latched per context by mmt_create (the bit rows are allocated only then);
+  // off by default: on the final round-5 build the bf16 aux measured faster (same box,
+  // profiles/r5am_relu_bits_final_ab.txt: C1 8.502 -> 8.477 ms, target 19.770 -> 19.505 ms), where the first
+  // version had been 0.1-0.7 % faster than the aux
+  int relu_bits = mmt_env_int("MMT_RELU_BITS", 0);
+  // MMT_DROP_COPY_FUSE / mmt_set_drop_copy_fuse: the FFN backward's dropout-masked bf16 residual-gradient copy (+ FFN
+  // output-bias gradient) in the epilogue of the last cross-attention K/V dX launch into that gradient (1), or a
+  // separate drop_copy pass for every modality (0)
+  int drop_copy_fuse = mmt_env_int("MMT_DROP_COPY_FUSE", 1);
+  // MMT_ATTN_QKV2 / mmt_set_attn_qkv2: hs 32, the Q/K/V stage-2 backward in the one-pass attention backward's
+  // epilogue (1) or the separate qkv2 backward over the bf16 dQ / dK / dV (0); read at every step
+  int attn_qkv2 = mmt_env_int("MMT_ATTN_QKV2", 1);
+  // MMT_FFN_FUSED / mmt_set_ffn_fused: the FFN forward as one launch at C = 256 (include/mmt.h); read at every forward
+  int ffn_fused = mmt_env_int("MMT_FFN_FUSED", 1);
+  // MMT_ATTN_QKV_ONCHIP / mmt_set_attn_qkv_onchip: hs 32 self-attention at T <= 256 in training forwards: Q / K / V
+  // made on chip from h1 and W2 (AttnProblem::oc_*) by the forward (bit 0) and by the one-pass backward (bit 1);
+  // with both bits the stage-1 GEMM drops its stage-2 epilogue and the Q/K/V rows are never written. Latched by
+  // mmt_forward
+  int attn_qkv_onchip = mmt_env_int("MMT_ATTN_QKV_ONCHIP", 3) & 3;
 
-// hs 32: the Q/K/V stage-2 backward in the one-pass attention backward's epilogue (1, default, env
-// MMT_ATTN_QKV2) or the separate qkv2 backward over the bf16 dQ / dK / dV (0); read at every step
-static int g_attn_qkv2 = mmt_env_int("MMT_ATTN_QKV2", 1);
-extern "C" int mmt_set_attn_qkv2(int on) {
-  const int old = g_attn_qkv2;
-  g_attn_qkv2 = on;
+  // MMT_LN_FUSE: 0 = no LayerNorm in a GEMM epilogue, backward (gemm_ln_bwd) or forward (MMT_LN_FUSE_FWD)
+  int ln_fuse = mmt_env_int("MMT_LN_FUSE", 1);
+  // MMT_LN_FUSE_FWD: the next LayerNorm's forward in the ffn2 residual GEMM's epilogue; bf16 at C == 256 (whole rows
+  // per 256x256 tile). 2: also C = 512 (128 x 512 tile), measured slower on the 2-stage ring (target 20.09 ->
+  // 20.43 ms, profiles/r3u_ab.txt)
+  int ln_fuse_fwd = mmt_env_int("MMT_LN_FUSE_FWD", 1);
+  // MMT_LN2_FUSE: ln2 in the fused out-projection's epilogue (0: the separate ln_fwd pass; fp8 keeps the pass, which
+  // also writes the MX-fp8 copy)
+  int ln2_fuse = mmt_env_int("MMT_LN2_FUSE", 1);
+  // MMT_MLP2: the out-projection pair as one launch (Runner::mlp2). Forward fused by default: C1 8.80 -> 8.70 ms/step
+  // (standalone 45.9 -> 43.0 us at C1, 119.6 -> 112.8 us at the target)
+  int mlp2 = mmt_env_int("MMT_MLP2", 1);
+  // MMT_MLP2_BWD: its backward pair: 2 = fused at C = 256 only, 1 = every width, 0 = never. Standalone the fused
+  // backward measured 33.5 / 80.6 us against 29.3 / 61.6 us for the pair (C1 / target, tools/mlp2_bench.py; one
+  // block per CU at 136 KiB of LDS with both B operands read transposed cannot hide what the two 2-3 blocks-per-CU
+  // GEMMs overlap, profiles/r5h_*), but in the C1 step beside the side stream it wins: 7.975 / 7.982 -> 7.949 /
+  // 7.960 ms (round 6, profiles/r6x_c1_env_ab.txt); at C = 512 it stays two GEMMs
+  int mlp2_bwd = mmt_env_int("MMT_MLP2_BWD", 2);
+  // MMT_QKV2_FUSE: the per-head Q/K/V stage 2 (model.py:39, 44, 49) in the stage-1 GEMM's epilogue at hs 32 / 64
+  // (SURVEY.md K4); 0 keeps the separate kernel
+  int qkv2_fuse = mmt_env_int("MMT_QKV2_FUSE", 1);
+  // MMT_MASK_AHEAD: when the attention dropout keep bits are made. 0: all later layers' while layer 0 computes;
+  // 1: layer l + 1's while layer l computes (one fork and one join per layer), so the masks overlap each layer's
+  // attention forward instead of layer 0's GEMMs (C3 attention forward 394 -> 955 us live); 2: layer l + 1's bits
+  // forked after layer l's self-attention forward, so they overlap that layer's GEMMs, which take the tile hint
+  // until the next join, rather than its attention. Unset (-1): 1 from 12 layers on, where the later layers' pile
+  // beside layer 0 grows past what one layer's GEMMs hide: C4 (24 layers) 312.4 -> 308.6 ms, C3 (12) 141.1 ->
+  // 140.5-140.9, target (6) 19.07 -> 19.04, C1 (6) 7.87 -> 7.90 (profiles/r6ab_mask_ab.txt, r6ae_c4_mask_ab.txt)
+  int mask_ahead = mmt_env_int("MMT_MASK_AHEAD", -1);
+  // MMT_MASK_T2: main-stream GEMMs beside the keep-bit launches take the 128 x 256 tile (0: the ping-pong kernel
+  // throughout)
+  int mask_t2 = mmt_env_int("MMT_MASK_T2", 1);
+  // MMT_DW_ATTN_SMALL=1: the FFN weight gradients (the side-stream launches still running when the self-attention
+  // backward starts) on the 128 x 128 tile, whose 64 KiB of LDS leave room on their CUs for one of the attention
+  // backward's 80 KiB workgroups
+  int dw_attn_small = mmt_env_int("MMT_DW_ATTN_SMALL", 0);
+  // MMT_FLUSH_HOLD=1: one side-stream fork per backward stage (every stage but the last layer's, whose weight
+  // gradients would otherwise only start after its data-gradient chain, at the end of the step)
+  int flush_hold = mmt_env_int("MMT_FLUSH_HOLD", 0);
+  // MMT_SIDE_STREAM=0: everything on the caller's stream, no side stream is made
+  int side_stream = mmt_env_int("MMT_SIDE_STREAM", 1);
+  // MMT_SIDE_PRIORITY (optional): HIP stream priority of the side stream (lower = higher priority, clamped to the
+  // device's range); unset = default priority
+  const char* side_priority = getenv("MMT_SIDE_PRIORITY");
+  // MMT_PROBE_EVENTS: event pairs mmt_probe_set makes for the recorded launches (recording stops when they run out)
+  int probe_events = mmt_env_int("MMT_PROBE_EVENTS", 4096);
+};
+Knobs& knobs() {
+  static Knobs k;
+  return k;
+}
+int swap_knob(int& k, int v) {
+  const int old = k;
+  k = v;
   return old;
 }
+}  // namespace
 
-// hs 32 self-attention at T <= 256 in training forwards: Q / K / V made on chip from h1 and W2 (AttnProblem::oc_*)
-// by the forward (bit 0) and by the one-pass backward (bit 1); with both bits the stage-1 GEMM drops its stage-2
-// epilogue and the Q/K/V rows are never written (env MMT_ATTN_QKV_ONCHIP). Latched by mmt_forward.
-// the FFN forward as one launch at C = 256 (include/mmt.h: mmt_set_ffn_fused)
-static int g_ffn_fused = mmt_env_int("MMT_FFN_FUSED", 1);
-extern "C" int mmt_set_ffn_fused(int on) {
-  const int old = g_ffn_fused;
-  g_ffn_fused = on;
-  return old;
-}
-static int g_attn_qkv_onchip = mmt_env_int("MMT_ATTN_QKV_ONCHIP", 3) & 3;
-extern "C" int mmt_set_attn_qkv_onchip(int bits) {
-  const int old = g_attn_qkv_onchip;
-  g_attn_qkv_onchip = bits & 3;
-  return old;
-}
+extern "C" int mmt_set_relu_bits(int on) { return swap_knob(knobs().relu_bits, on); }
+extern "C" int mmt_set_drop_copy_fuse(int on) { return swap_knob(knobs().drop_copy_fuse, on); }
+extern "C" int mmt_set_attn_qkv2(int on) { return swap_knob(knobs().attn_qkv2, on); }
+extern "C" int mmt_set_ffn_fused(int on) { return swap_knob(knobs().ffn_fused, on); }
+extern "C" int mmt_set_attn_qkv_onchip(int bits) { return swap_knob(knobs().attn_qkv_onchip, bits & 3); }
 
 struct mmt_ctx {
   mmt_config cfg;
@@ -675,9 +718,9 @@ int probe_match(const mmt_ctx* c, const char* what) {
 
 // algorithmic cost of one grouped GEMM launch: 2MNK flops; every operand read once and every
 // output written once (bf16 activations / packed bf16 weights, fp32 bias / residual / outputs)
-void gemm_cost(const GemmBatch& b, int epi, double* fl, double* by) {
-  for (int g = 0; g < b.count; ++g) {
-    const GemmProblem& P = b.p[g];
+void gemm_cost(const GemmProblem* p, int n, int epi, double* fl, double* by) {
+  for (int g = 0; g < n; ++g) {
+    const GemmProblem& P = p[g];
     const double M = P.M, N = P.N, K = P.K;
     *fl += 2.0 * M * N * K;
     double x = (M * K + N * K) * 2.0;
@@ -703,6 +746,7 @@ void gemm_cost(const GemmBatch& b, int epi, double* fl, double* by) {
     *by += x;
   }
 }
+void gemm_cost(const GemmBatch& b, int epi, double* fl, double* by) { gemm_cost(b.p, b.count, epi, fl, by); }
 
 // weight gradient dW[M,N] += dY[K,M]^T X[K,N]: both operands read once, the fp32 gradient written once
 void wgrad_cost(const GemmBatch& b, double* fl, double* by) {
@@ -762,6 +806,93 @@ GemmProblem gp_f8(const uint8_t* X8, int ldx, const uint8_t* Xs, int ldxs, const
 // :116 CA projection, :171 FFN output); one hash key per (seed, layer, modality, site)
 enum DropSite { DS_SA_PROB = 0, DS_SA_PROJ = 1, DS_FFN = 2, DS_CA_PROB = 3, DS_CA_PROJ = 4 };
 
+// descriptor builders -------------------------------------------------------------------------
+// a batch of n problems, problem u made by fn(u); built where it is launched, so no field of an earlier launch lives on
+// (gemms / lns: the two most common kinds)
+template <class Bt, class Fn>
+Bt batch_of(int n, Fn&& fn) {
+  Bt b{};
+  b.count = n;
+  for (int u = 0; u < n; ++u) b.p[u] = fn(u);
+  return b;
+}
+template <class Fn> GemmBatch gemms(int n, Fn&& fn) { return batch_of<GemmBatch>(n, fn); }
+template <class Fn> LnBatch lns(int n, Fn&& fn) { return batch_of<LnBatch>(n, fn); }
+
+// a forward Linear's problem (Runner::linear / linear8) and where its rows go
+struct Lin : GemmProblem {
+  Lin(const GemmProblem& g) : GemmProblem(g) {}
+  Lin& out16(bf16_t* y, int ld) { o16 = y; ldo16 = ld; return *this; }                       // bf16 rows
+  Lin& out32(float* y, int ld, const float* res = nullptr) {                                   // fp32 rows (+ residual)
+    o32 = y; ldc = ld; resid = res; ldres = res ? ld : 0;
+    return *this;
+  }
+};
+
+LnProblem ln_fwd_problem(const float* x, const float* gamma, const float* beta, bf16_t* y, float* mean, float* rstd) {
+  LnProblem q{};
+  q.x = x; q.gamma = gamma; q.beta = beta; q.y = y; q.mean = mean; q.rstd = rstd;
+  return q;
+}
+// dx += the LayerNorm's input gradient; no bf16 copy (set_dres16_consumer / the caller add dx16, dsum and its mask)
+LnProblem ln_bwd_problem(const float* x, const float* gamma, float* mean, float* rstd, const float* dy, float* dx,
+                         float* dgamma, float* dbeta) {
+  LnProblem q{};
+  q.x = x; q.gamma = gamma; q.mean = mean; q.rstd = rstd;
+  q.dy = dy; q.dx = dx; q.dgamma = dgamma; q.dbeta = dbeta;
+  return q;
+}
+// the three LayerNorms of a layer: where each keeps its parameters (LM) and its saved rows (ActLM)
+struct LnSite {
+  int64_t LM::*w, LM::*b;
+  size_t ActLM::*y, ActLM::*mean, ActLM::*rstd, ActLM::*y8, ActLM::*s8;
+};
+const LnSite LN1{&LM::ln1w, &LM::ln1b, &ActLM::a, &ActLM::mean1, &ActLM::rstd1, &ActLM::a8, &ActLM::as8};
+const LnSite LN2{&LM::ln2w, &LM::ln2b, &ActLM::c, &ActLM::mean2, &ActLM::rstd2, &ActLM::c8, &ActLM::cs8};
+const LnSite LNC{&LM::lncw, &LM::lncb, &ActLM::d, &ActLM::meanc, &ActLM::rstdc, &ActLM::d8, &ActLM::ds8};
+// the LayerNorm n in the epilogue of the residual GEMM that writes its input rows (GemmProblem::lnf_*)
+void fuse_next_ln(GemmProblem& g, const LnProblem& n) {
+  g.lnf_gamma = n.gamma; g.lnf_beta = n.beta; g.lnf_y = n.y; g.lnf_mean = n.mean; g.lnf_rstd = n.rstd;
+}
+
+// the operand fields AttnProblem, DecodeAttnProblem and FanoutAttnProblem share. Self-attention: K | Q | V
+// interleaved in rows of 3C (kqv), the query row given apart (decode reads it from compact or tail rows)
+template <class P>
+void self_attn_io(P& q, const bf16_t* qrow, int q_ld, const bf16_t* kqv, bf16_t* o, int C, int hs) {
+  q.q = qrow; q.q_ld = q_ld; q.k[0] = kqv; q.v[0] = kqv + 2 * C; q.kv_ld = 3 * C; q.kv_hstride = hs;
+  q.o = o; q.o_ld = C; q.nstreams = 1;
+}
+// cross-attention over nkv KV streams, stream j's K | V interleaved per head in the rows of 2C that kv(j) returns
+template <class P, class Kv>
+void cross_attn_io(P& q, const bf16_t* qrow, Kv&& kv, int nkv, bf16_t* o, int C, int hs) {
+  q.q = qrow; q.q_ld = C;
+  for (int j = 0; j < nkv; ++j) { q.k[j] = kv(j); q.v[j] = q.k[j] + hs; }
+  q.kv_ld = 2 * C; q.kv_hstride = 2 * hs; q.o = o; q.o_ld = C; q.nstreams = nkv;
+}
+
+inline std::vector<int> cross_set(const LM* x, int M) {
+  std::vector<int> cx;
+  for (int i = 0; i < M; ++i) if (x[i].cross) cx.push_back(i);
+  return cx;
+}
+// the cross K/V projections of a layer: for every cross modality i of cx and every other modality j (i's KV stream
+// jj), add(i, j, jj) appends one problem to the caller's group and send() launches and empties it: at MMT_MAX_GROUP
+// problems, at the end, and (per_query) after each i's last stream
+template <class Add, class Send>
+void for_each_cross_kv(const std::vector<int>& cx, int M, bool per_query, Add&& add, Send&& send) {
+  int n = 0;
+  for (int i : cx) {
+    int jj = 0;
+    for (int j = 0; j < M; ++j) {
+      if (j == i) continue;
+      add(i, j, jj++);
+      if (++n == MMT_MAX_GROUP) { send(); n = 0; }
+    }
+    if (per_query && n) { send(); n = 0; }
+  }
+  if (n) send();
+}
+
 struct Runner {
   mmt_ctx* c;
   hipStream_t s;
@@ -773,6 +904,11 @@ struct Runner {
   bool drop = false;  // dropout active for this forward / its backward
   uint64_t seed = 0;
 
+  template <class T> T* W(size_t off) { return at<T>(ws, off); }
+  bf16_t* b16(size_t off) { return at<bf16_t>(ws, off); }
+  float* f32(size_t off) { return at<float>(ws, off); }
+  const float* P(int64_t off) { return params + off; }
+
   // element kept iff mmt_keep(mmt_hash(key, row, col >> 1), col, thr) ; kept values scaled by 1 / (1 - p)
   template <class Pm>
   void set_drop(Pm& p, int l, int i, int site) const {
@@ -781,6 +917,40 @@ struct Runner {
     p.drop_key = mmt_hash((uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)((l * MAXM + i) * 8 + site));
     p.drop_thr = (uint32_t)std::min(65535.0, std::max(1.0, std::floor(pr * 65536.0)));  // 16-bit halves (mmt_keep)
     p.drop_scale = (float)(1.0 / (1.0 - pr));
+  }
+
+  // Y = X W^T (+ bias; bias < 0: none) on bf16 rows X [R, W.cols] against the packed bf16 weight
+  Lin linear(const bf16_t* X, int ldx, const Mat& W, int64_t bias) {
+    GemmProblem g = gp_fwd(X, ldx, wpk, W, R);
+    if (bias >= 0) g.bias = P(bias);
+    return g;
+  }
+  // the same on the MX-fp8 copies of X and W (precision fp8)
+  Lin linear8(const uint8_t* X8, int ldx, const uint8_t* Xs, int ldxs, const uint8_t* w8, const Mat& W, int64_t bias) {
+    GemmProblem g = gp_f8(X8, ldx, Xs, ldxs, w8, W, R);
+    if (bias >= 0) g.bias = P(bias);
+    return g;
+  }
+  // the training forward's and backward's self-attention problem of (layer l, modality i): the fields both share
+  AttnProblem self_attn(const ActLM& a, int l, int i) {
+    AttnProblem q{};
+    bf16_t* kqv = b16(a.qkv);
+    self_attn_io(q, kqv + c->C, 3 * c->C, kqv, b16(a.o), c->C, c->hs);
+    q.lse[0] = f32(a.lse);
+    set_drop(q, l, i, DS_SA_PROB);
+    if (drop) q.dmask[0] = W<uint32_t>(a.dm);
+    return q;
+  }
+  // ... and the cross-attention problem of a cross modality i over the other M - 1 modalities' K/V
+  AttnProblem cross_attn(const ActLM& a, int l, int i) {
+    AttnProblem q{};
+    const int nkv = c->M - 1;
+    cross_attn_io(q, b16(a.qc), [&](int j) { return b16(a.kv[j]); }, nkv, b16(a.oc), c->C, c->hs);
+    for (int j = 0; j < nkv; ++j) { q.oj[j] = b16(a.ocj[j]); q.lse[j] = f32(a.lsej[j]); }
+    set_drop(q, l, i, DS_CA_PROB);
+    if (drop)
+      for (int j = 0; j < nkv; ++j) q.dmask[j] = W<uint32_t>(a.dmj[j]);
+    return q;
   }
 
   bool ok(hipError_t e, const char* what) {
@@ -828,24 +998,51 @@ struct Runner {
     e.bytes = bytes;
     hipEventRecord(e.b, st);
   }
+  // Every labelled launch goes through here: the error latch (after a failure nothing more is launched), the probe
+  // events around go() on the stream it launches to, and, only when a pattern matched, cost(&flops, &bytes)
+  template <class Go, class Cost>
+  void launch(const char* what, hipStream_t st, Go&& go, Cost&& cost) {
+    if (rc != MMT_OK) return;
+    const int id = probe_begin(what, st);
+    ok(go(), what);
+    if (id < 0) return;
+    double fl = 0, by = 0;
+    cost(&fl, &by);
+    probe_end(id, st, fl, by);
+  }
+  // GemmBatch::tile_hint for the main-stream GEMMs launched while it is set (run_forward: beside the
+  // side stream's keep-bit launches)
+  int gemm_hint = 0;
+  static void set_hint(GemmBatch& b, int hint) { b.tile_hint = hint; }
+  static void set_hint(AttnBatch&, int) {}
+  // go(the batch as launched): b itself, or a copy that carries the tile hint and (arm, deterministic mode) the
+  // partial-sum scratch
+  template <class Bt, class Go>
+  hipError_t prepared(const Bt& b, int hint, bool arm, Go&& go) {
+    if (!hint && !(arm && det)) return go(b);
+    Bt h = b;
+    if (hint) set_hint(h, hint);
+    if (arm) det_arm(h);
+    return go(h);
+  }
+  void gemm(const GemmBatch& b, bool akc, bool bkc, int epi, int splits, const char* what) {
+    auto go = [&](const GemmBatch& h) { return mmt_launch_gemm(h, akc, bkc, epi, splits, s); };
+    launch(what, s, [&] { return prepared(b, gemm_hint, true, go); }, [&](double* fl, double* by) { gemm_cost(b, epi, fl, by); });
+  }
   // MX-fp8 forward GEMM (precision fp8): A / B e4m3fn + E8M0 (mmt_launch_gemm_f8)
   void gemm8(const GemmBatch& b, int epi, const char* what) {
-    if (rc != MMT_OK) return;
-    const int id = probe_begin(what, s);
-    if (gemm_hint) {
-      GemmBatch h = b;
-      h.tile_hint = gemm_hint;
-      ok(mmt_launch_gemm_f8(h, epi, s), what);
-    } else {
-      ok(mmt_launch_gemm_f8(b, epi, s), what);
-    }
-    if (id >= 0) {
-      double fl = 0, by = 0;
-      gemm_cost(b, epi, &fl, &by);
-      // 1-byte operands plus one E8M0 exponent byte per 32 K elements of every row of A and B
-      for (int g = 0; g < b.count; ++g) by -= ((double)b.p[g].M + b.p[g].N) * b.p[g].K * (1.0 - 1.0 / 32.0);
-      probe_end(id, s, fl, by);
-    }
+    auto go = [&](const GemmBatch& h) { return mmt_launch_gemm_f8(h, epi, s); };
+    launch(what, s, [&] { return prepared(b, gemm_hint, false, go); },
+           [&](double* fl, double* by) {
+             gemm_cost(b, epi, fl, by);
+             // 1-byte operands plus one E8M0 exponent byte per 32 K elements of every row of A and B
+             for (int g = 0; g < b.count; ++g) *by -= ((double)b.p[g].M + b.p[g].N) * b.p[g].K * (1.0 - 1.0 / 32.0);
+           });
+  }
+  // a forward Linear launch (both operands K-contiguous, no split): the MX-fp8 kernel when f8
+  void fgemm(const GemmBatch& b, int epi, const char* what, bool f8 = false) {
+    if (f8) gemm8(b, epi, what);
+    else gemm(b, true, true, epi, 1, what);
   }
   // backward-data GEMM dy = A B (EPI_STORE_F32 into lb's dy) followed by the LayerNorm backward lb
   // (model.py:189-190, 210, 330 under autograd): ONE launch with the LayerNorm fused into the GEMM's
@@ -853,8 +1050,7 @@ struct Runner {
   // the two passes. The fused launch never materialises dy (the fp32 round trip of the two-pass form)
   void gemm_ln_bwd(const GemmBatch& dx, const LnBatch& lb, int R, int C, const char* gname, const char* lname) {
     if (rc != MMT_OK) return;
-    static const bool fuse = mmt_env_int("MMT_LN_FUSE", 1) != 0;
-    if (fuse && lb.count == dx.count) {
+    if (knobs().ln_fuse != 0 && lb.count == dx.count) {
       GemmBatch f = dx;
       for (int g = 0; g < f.count; ++g) {
         GemmProblem& P = f.p[g];
@@ -869,13 +1065,8 @@ struct Runner {
       }
       if (mmt_gemm_ln_bwd_ok(f)) {
         det_arm(f);
-        const int id = probe_begin(gname, s);
-        ok(mmt_launch_gemm_ln_bwd(f, s), gname);
-        if (id >= 0) {
-          double fl = 0, by = 0;
-          gemm_cost(f, EPI_LN_BWD_F32, &fl, &by);
-          probe_end(id, s, fl, by);
-        }
+        launch(gname, s, [&] { return mmt_launch_gemm_ln_bwd(f, s); },
+               [&](double* fl, double* by) { gemm_cost(f, EPI_LN_BWD_F32, fl, by); });
         return;
       }
     }
@@ -884,22 +1075,12 @@ struct Runner {
     det_arm(ld);
     ok(mmt_launch_ln_bwd(ld, R, C, s), lname);
   }
-  // the attention out-projection Linear(C, C/2) -> tanh -> Linear(C/2, C) + dropout + residual as one fused
-  // launch (mmt_launch_mlp2: h stays in LDS between the products); false (nothing launched) when the
-  // shape is outside the fused kernel or MMT_MLP2=0, and the caller runs the two GEMMs
-  // bwd: the backward-data pair (mmt_launch_mlp2_bwd: dh = (dY W2) tanh', dx = dh W0)
-  bool mlp2(const GemmProblem* g1s, const GemmProblem* g2s, int n, const char* what, bool bwd = false) {
-    // forward fused by default: C1 8.80 -> 8.70 ms/step (standalone 45.9 -> 43.0 us at C1, 119.6 -> 112.8 us
-    // at the target). The backward pair: fused at C = 256 only by default (MMT_MLP2_BWD: 2 = that, 1 =
-    // every width, 0 = never). Standalone the fused backward measured 33.5 / 80.6 us against 29.3 / 61.6 us
-    // for the pair (C1 / target, tools/mlp2_bench.py; one block per CU at 136 KiB of LDS with both B
-    // operands read transposed cannot hide what the two 2-3 blocks-per-CU GEMMs overlap, profiles/r5h_*),
-    // but in the C1 step beside the side stream it wins: 7.975 / 7.982 -> 7.949 / 7.960 ms (round 6,
-    // profiles/r6x_c1_env_ab.txt); at C = 512 it stays two GEMMs
-    static const bool on = mmt_env_int("MMT_MLP2", 1) != 0;
-    static const int bwd_mode = mmt_env_int("MMT_MLP2_BWD", 2);
-    const bool on_bwd = bwd_mode == 1 || (bwd_mode == 2 && n >= 1 && g1s[0].N == 128);
-    if (rc != MMT_OK || !on || (bwd && !on_bwd) || n < 1) return false;
+  // n problem pairs (g1s[i] feeds g2s[i] through a hidden tile that stays on chip) as Mlp2Batch chunks of
+  // MMT_MLP2_GROUP under ONE label: nothing is launched and false returned unless fits() takes every chunk.
+  // Cost: the two GEMMs' (epilogues epi1, epi2), less the hidden rows the second product does not read back
+  template <class Fits, class Go>
+  bool pair_launch(const GemmProblem* g1s, const GemmProblem* g2s, int n, const char* what, int epi1, int epi2, bool arm,
+                   Fits&& fits, Go&& go) {
     Mlp2Batch chunk[(MMT_MAX_GROUP + MMT_MLP2_GROUP - 1) / MMT_MLP2_GROUP] = {};
     const int nch = (n + MMT_MLP2_GROUP - 1) / MMT_MLP2_GROUP;
     for (int i = 0; i < n; ++i) {
@@ -909,85 +1090,59 @@ struct Runner {
       ++b.count;
     }
     for (int k = 0; k < nch; ++k)
-      if (!(bwd ? mmt_mlp2_bwd_ok(chunk[k]) : mmt_mlp2_ok(chunk[k]))) return false;
-    if (bwd)
+      if (!fits(chunk[k])) return false;
+    if (arm)
       for (int k = 0; k < nch; ++k) det_arm(chunk[k]);  // (each chunk's ordered sum runs before the next chunk's launch)
-    const int id = probe_begin(what, s);
-    for (int k = 0; k < nch; ++k) ok(bwd ? mmt_launch_mlp2_bwd(chunk[k], s) : mmt_launch_mlp2(chunk[k], s), what);
-    if (id >= 0) {
-      double fl = 0, by = 0;
-      GemmBatch g1{}, g2{};
-      g1.count = g2.count = n;
-      for (int g = 0; g < n; ++g) { g1.p[g] = g1s[g]; g2.p[g] = g2s[g]; }
-      gemm_cost(g1, bwd ? EPI_DTANH_BF16 : EPI_BIAS_TANH_BF16, &fl, &by);
-      gemm_cost(g2, bwd ? EPI_STORE_BF16 : EPI_BIAS_RESID_F32, &fl, &by);
-      for (int g = 0; g < n; ++g) by -= (double)g2s[g].M * g2s[g].K * 2.0;  // h / dh is not read back
-      probe_end(id, s, fl, by);
-    }
+    launch(what, s,
+           [&] {
+             hipError_t first = hipSuccess;
+             for (int k = 0; k < nch; ++k) {
+               const hipError_t e = go(chunk[k], s);
+               if (first == hipSuccess) first = e;
+             }
+             return first;
+           },
+           [&](double* fl, double* by) {
+             gemm_cost(g1s, n, epi1, fl, by);
+             gemm_cost(g2s, n, epi2, fl, by);
+             for (int g = 0; g < n; ++g) *by -= (double)g2s[g].M * g2s[g].K * 2.0;  // h / dh is not read back
+           });
     return true;
+  }
+  // the attention out-projection Linear(C, C/2) -> tanh -> Linear(C/2, C) + dropout + residual as one fused
+  // launch (mmt_launch_mlp2: h stays in LDS between the products); false (nothing launched) when the
+  // shape is outside the fused kernel or MMT_MLP2=0, and the caller runs the two GEMMs
+  // bwd: the backward-data pair (mmt_launch_mlp2_bwd: dh = (dY W2) tanh', dx = dh W0), by MMT_MLP2_BWD
+  bool mlp2(const GemmProblem* g1s, const GemmProblem* g2s, int n, const char* what, bool bwd = false) {
+    const int bwd_mode = knobs().mlp2_bwd;
+    const bool on_bwd = bwd_mode == 1 || (bwd_mode == 2 && n >= 1 && g1s[0].N == 128);
+    if (rc != MMT_OK || knobs().mlp2 == 0 || (bwd && !on_bwd) || n < 1) return false;
+    if (bwd) return pair_launch(g1s, g2s, n, what, EPI_DTANH_BF16, EPI_STORE_BF16, true, mmt_mlp2_bwd_ok, mmt_launch_mlp2_bwd);
+    return pair_launch(g1s, g2s, n, what, EPI_BIAS_TANH_BF16, EPI_BIAS_RESID_F32, false, mmt_mlp2_ok, mmt_launch_mlp2);
   }
   // the FFN forward Linear(C, 4C) -> ReLU -> Linear(4C, C) + dropout + residual (+ the next LayerNorm) as one
   // launch (mmt_launch_ffn: the hidden activation is stored for the backward but never read back); g1s the
   // ffn0 problems, g2s the ffn2 problems. false (nothing launched) when the shape is outside the kernel
   bool ffn(const GemmProblem* g1s, const GemmProblem* g2s, int n, const char* what) {
     if (rc != MMT_OK || n < 1) return false;
-    Mlp2Batch chunk[(MMT_MAX_GROUP + MMT_MLP2_GROUP - 1) / MMT_MLP2_GROUP] = {};
-    const int nch = (n + MMT_MLP2_GROUP - 1) / MMT_MLP2_GROUP;
-    for (int i = 0; i < n; ++i) {
-      Mlp2Batch& b = chunk[i / MMT_MLP2_GROUP];
-      b.g1[b.count] = g1s[i];
-      b.g2[b.count] = g2s[i];
-      ++b.count;
-    }
-    for (int k = 0; k < nch; ++k)
-      if (!mmt_ffn_ok(chunk[k])) return false;
-    const int id = probe_begin(what, s);
-    for (int k = 0; k < nch; ++k) ok(mmt_launch_ffn(chunk[k], s), what);
-    if (id >= 0) {
-      double fl = 0, by = 0;
-      GemmBatch g1{}, g2{};
-      g1.count = g2.count = n;
-      for (int g = 0; g < n; ++g) { g1.p[g] = g1s[g]; g2.p[g] = g2s[g]; }
-      gemm_cost(g1, EPI_BIAS_RELU_BF16, &fl, &by);
-      gemm_cost(g2, EPI_BIAS_RESID_F32, &fl, &by);
-      for (int g = 0; g < n; ++g) by -= (double)g2s[g].M * g2s[g].K * 2.0;  // h is not read back
-      probe_end(id, s, fl, by);
-    }
-    return true;
+    return pair_launch(g1s, g2s, n, what, EPI_BIAS_RELU_BF16, EPI_BIAS_RESID_F32, false, mmt_ffn_ok, mmt_launch_ffn);
   }
   // forward residual GEMM with the next LayerNorm's forward fused (mmt_launch_gemm_resid_ln)
   bool gemm_resid_ln(const GemmBatch& b, const char* what) {
     if (rc != MMT_OK || !mmt_gemm_resid_ln_ok(b)) return false;
-    const int id = probe_begin(what, s);
-    ok(mmt_launch_gemm_resid_ln(b, s), what);
-    if (id >= 0) {
-      double fl = 0, by = 0;
-      gemm_cost(b, EPI_BIAS_RESID_F32, &fl, &by);
-      for (int g = 0; g < b.count; ++g)
-        if (b.p[g].lnf_y) by += (double)b.p[g].M * b.p[g].N * 2.0 + b.p[g].M * 8.0;
-      probe_end(id, s, fl, by);
-    }
+    launch(what, s, [&] { return mmt_launch_gemm_resid_ln(b, s); },
+           [&](double* fl, double* by) {
+             gemm_cost(b, EPI_BIAS_RESID_F32, fl, by);
+             for (int g = 0; g < b.count; ++g)
+               if (b.p[g].lnf_y) *by += (double)b.p[g].M * b.p[g].N * 2.0 + b.p[g].M * 8.0;
+           });
     return true;
   }
-  // GemmBatch::tile_hint for the main-stream GEMMs launched while it is set (run_forward: beside the
-  // side stream's keep-bit launches)
-  int gemm_hint = 0;
-  void gemm(const GemmBatch& b, bool akc, bool bkc, int epi, int splits, const char* what) {
-    if (rc != MMT_OK) return;
-    const int id = probe_begin(what, s);
-    if (gemm_hint || det) {
-      GemmBatch h = b;
-      if (gemm_hint) h.tile_hint = gemm_hint;
-      det_arm(h);
-      ok(mmt_launch_gemm(h, akc, bkc, epi, splits, s), what);
-    } else {
-      ok(mmt_launch_gemm(b, akc, bkc, epi, splits, s), what);
-    }
-    if (id >= 0) {
-      double fl = 0, by = 0;
-      gemm_cost(b, epi, &fl, &by);
-      probe_end(id, s, fl, by);
-    }
+  void attn(const AttnBatch& ab, bool bwd, float scale, const char* what) {
+    const auto kernel = bwd ? mmt_launch_attn_bwd : mmt_launch_attn_fwd;
+    auto go = [&](const AttnBatch& h) { return kernel(h, B, c->T, c->H, c->hs, scale, s); };
+    launch(what, s, [&] { return prepared(ab, 0, bwd, go); },
+           [&](double* fl, double* by) { attn_cost(ab, B, c->T, c->H, c->hs, bwd, drop, fl, by); });
   }
   // fork the side stream off the main one (everything enqueued on `s` so far happens first)
   hipStream_t side_stream() const { return c->side_off ? nullptr : c->side; }
@@ -1036,13 +1191,8 @@ struct Runner {
     pend.clear();
   }
   void wgrad(const GemmBatch& b, const char* what, hipStream_t st) {
-    const int id = probe_begin(what, st);
-    ok(mmt_launch_gemm_wgrad(b, W<float>(c->plan.slab), (int64_t)c->plan.slab_bytes, st), what);
-    if (id >= 0) {
-      double fl = 0, by = 0;
-      wgrad_cost(b, &fl, &by);
-      probe_end(id, st, fl, by);
-    }
+    launch(what, st, [&] { return mmt_launch_gemm_wgrad(b, W<float>(c->plan.slab), (int64_t)c->plan.slab_bytes, st); },
+           [&](double* fl, double* by) { wgrad_cost(b, fl, by); });
   }
   // weight-gradient GEMMs share one split-K slab region: they run in launch order on ONE stream
   // (the side stream when there is one), so no two of them ever write the slabs at once (a
@@ -1057,51 +1207,52 @@ struct Runner {
     // another (profiles/r6ak_wgrad_blocks_ab.txt, r6al_wgrad96_ab.txt). MMT_WGRAD_BLOCKS overrides both
     pend.back().first.dw_blocks = c->hs >= 64 ? 96 : 0;
   }
-  void attn(const AttnBatch& ab, bool bwd, float scale, const char* what) {
-    if (rc != MMT_OK) return;
-    const int id = probe_begin(what, s);
-    if (bwd && det) {
-      AttnBatch ad = ab;
-      det_arm(ad);
-      ok(mmt_launch_attn_bwd(ad, B, c->T, c->H, c->hs, scale, s), what);
-    } else if (bwd) ok(mmt_launch_attn_bwd(ab, B, c->T, c->H, c->hs, scale, s), what);
-    else ok(mmt_launch_attn_fwd(ab, B, c->T, c->H, c->hs, scale, s), what);
-    if (id >= 0) {
-      double fl = 0, by = 0;
-      attn_cost(ab, B, c->T, c->H, c->hs, bwd, drop, &fl, &by);
-      probe_end(id, s, fl, by);
-    }
-  }
-  template <class T> T* W(size_t off) { return at<T>(ws, off); }
-  const float* P(int64_t off) { return params + off; }
 };
 
 // -------------------------------------------------------------------------------------------
 // forward
 // -------------------------------------------------------------------------------------------
+// post block (model.py:296-330), shared by the forward and the decode step: the final LayerNorm of the modalities
+// lnf_done does not mark (the ffn2 epilogue did theirs), Linear(C, V/2) + tanh, Linear(V/2, V) into logits. rows(i)
+// says where modality i's rows live; lf arrives empty but for the words its launch zeroes; labels: lnf, head0, head2
+struct PostRows { bf16_t* y; float* mean; float* rstd; bf16_t* hh; };
+template <class Rows>
+void run_post(mmt_ctx* c, Runner& r, int R, const std::vector<const float*>& xin, const char* lnf_done, Rows&& rows,
+              float* const* logits, LnBatch lf, const char* const (&labels)[3]) {
+  const int M = c->M, C = c->C;
+  for (int i = 0; i < M; ++i) {
+    if (lnf_done && lnf_done[i]) continue;
+    const PostRows w = rows(i);
+    lf.p[lf.count++] = ln_fwd_problem(xin[i], r.P(c->post[i].lnw), r.P(c->post[i].lnb), w.y, w.mean, w.rstd);
+  }
+  if (lf.count) {
+    r.ok(mmt_launch_ln_fwd(lf, R, C, r.s), labels[0]);
+  } else if (lf.nzero_f) {  // every post-block LayerNorm was fused: zero the accumulators here
+    r.ok(hipMemsetAsync(lf.zero_f, 0, sizeof(float) * lf.nzero_f, r.s), "memset losses");
+    r.ok(hipMemsetAsync(lf.zero_i, 0, sizeof(int) * lf.nzero_i, r.s), "memset flag");
+  }
+  r.fgemm(gemms(M, [&](int i) {
+            return r.linear(rows(i).y, C, c->post[i].H0, c->post[i].b0).out16(rows(i).hh, c->ldvh[i]);
+          }), EPI_BIAS_TANH_BF16, labels[1]);
+  r.fgemm(gemms(M, [&](int i) {
+            return r.linear(rows(i).hh, c->ldvh[i], c->post[i].H2, c->post[i].b2).out32(logits[i], c->V[i]);
+          }), EPI_STORE_F32, labels[2]);
+}
+
 int run_forward(mmt_ctx* c, Runner& r, const int64_t* const* idx, const int64_t* const* tgt, float* const* logits,
                 float* losses) {
   const int M = c->M, C = c->C, H = c->H, hs = c->hs, R = r.R, B = r.B, T = c->T;
   const int ldh1 = r8(3 * H * c->hh), ldp = r8(C / 2);
   const float scale = 1.0f / std::sqrt((float)hs);
+  const Knobs& kn = knobs();
   Plan& p = c->plan;
-  bf16_t* wpk = r.W<bf16_t>(p.pack);
+  bf16_t* wpk = r.b16(p.pack);
   r.wpk = wpk;
   // keep bits of layer ll's self- and cross-attention dropout, one side-stream launch each (the
   // mask kernel reads nothing the main stream writes: a fork orders it after the previous step)
   hipStream_t ss = r.s;
-  // MMT_MASK_AHEAD=1: layer l + 1's keep bits are made while layer l computes (one fork and one join per
-  // layer) instead of all later layers' while layer 0 computes. The masks then overlap each layer's attention
-  // forward instead of layer 0's GEMMs (C3 attention forward 394 -> 955 us live). Default: from 12 layers on,
-  // where the later layers' pile beside layer 0 grows past what one layer's GEMMs hide: C4 (24 layers) 312.4 ->
-  // 308.6 ms, C3 (12) 141.1 -> 140.5-140.9, target (6) 19.07 -> 19.04, C1 (6) 7.87 -> 7.90
-  // (profiles/r6ab_mask_ab.txt, r6ae_c4_mask_ab.txt); MMT_MASK_AHEAD=0 / 1 forces it
-  static const int mask_ahead_env = mmt_env_int("MMT_MASK_AHEAD", -1);
-  // (2: layer l + 1's bits forked after layer l's self-attention forward, so they overlap that layer's
-  // GEMMs, which take the tile hint until the next join, rather than its attention)
-  const int ahead_mode = mask_ahead_env >= 0 ? mask_ahead_env : (c->L >= 12 ? 1 : 0);
+  const int ahead_mode = kn.mask_ahead >= 0 ? kn.mask_ahead : (c->L >= 12 ? 1 : 0);  // (Knobs: MMT_MASK_AHEAD)
   const bool mask_ahead = ahead_mode != 0;
-  static const int mask_t2 = mmt_env_int("MMT_MASK_T2", 1);
   auto gen_masks = [&](int ll) {
     if (ll <= 1 || mask_ahead) ss = r.side();  // layer 0: one fork; layers 1..L-1: one fork for all
     const LM* xl = &c->lm[(size_t)ll * M];
@@ -1141,27 +1292,33 @@ int run_forward(mmt_ctx* c, Runner& r, const int64_t* const* idx, const int64_t*
         }
     }
   }
-  auto ln8 = [&](LnProblem& q, size_t y8, size_t s8) {
-    if (!f8) return;
-    q.y8 = r.W<uint8_t>(y8); q.s8 = r.W<uint8_t>(s8); q.ld8 = C; q.lds8 = ldsC;
+  // a Linear of the layers on the rows at x16: on their MX-fp8 copy (x8, exponents s8 with row stride lds) when fp8
+  auto lin = [&](size_t x16, size_t x8, size_t s8, int K, int lds, const Mat& W, int64_t bias) {
+    return f8 ? r.linear8(r.W<uint8_t>(x8), K, r.W<uint8_t>(s8), lds, w8, W, bias) : r.linear(r.b16(x16), K, W, bias);
   };
+  // the LayerNorms, as their own launch reads them (x: the input rows) or as a residual GEMM's epilogue takes them
+  // (fuse_next_ln; x unused). fp8: the launch also writes the MX-fp8 copy of y
+  auto ln = [&](const LnSite& n, int l, int i, const float* xi) {
+    const LM& x = c->lm[(size_t)l * M + i];
+    const ActLM& a = p.act[(size_t)l * M + i];
+    LnProblem q = ln_fwd_problem(xi, r.P(x.*n.w), r.P(x.*n.b), r.b16(a.*n.y), r.f32(a.*n.mean), r.f32(a.*n.rstd));
+    if (f8) { q.y8 = r.W<uint8_t>(a.*n.y8); q.s8 = r.W<uint8_t>(a.*n.s8); q.ld8 = C; q.lds8 = ldsC; }
+    return q;
+  };
+  auto post_rows = [&](int i) { return PostRows{r.b16(p.lnf16[i]), r.f32(p.meanf[i]), r.f32(p.rstdf[i]), r.b16(p.hh[i])}; };
   {
     EmbBatch eb{};
     eb.count = M;
     for (int i = 0; i < M; ++i) {
       eb.p[i].idx = idx[i]; eb.p[i].tok = r.P(c->post[i].tok); eb.p[i].pos = r.P(c->pos_off);
-      eb.p[i].x = r.W<float>(p.xemb[i]); eb.p[i].V = c->V[i];
+      eb.p[i].x = r.f32(p.xemb[i]); eb.p[i].V = c->V[i];
     }
     r.ok(mmt_launch_embed_fwd(eb, B, T, C, r.s), "embed_fwd");
   }
   std::vector<const float*> xin(M);
-  for (int i = 0; i < M; ++i) xin[i] = r.W<float>(p.xemb[i]);
-  // LayerNorm forwards already done by the previous residual GEMM's epilogue (lnf_fused: the post
-  // block's); fused only in bf16 at C == 256 (whole rows per 256x256 tile), MMT_LN_FUSE=0 or
-  // MMT_LN_FUSE_FWD=0 disables
-  static const int ln_fuse = mmt_env_int("MMT_LN_FUSE", 1) != 0 ? mmt_env_int("MMT_LN_FUSE_FWD", 1) : 0;
-  // C = 512 (128 x 512 tile) only with MMT_LN_FUSE_FWD=2: measured slower on the 2-stage ring
-  // (target 20.09 -> 20.43 ms, profiles/r3u_ab.txt)
+  for (int i = 0; i < M; ++i) xin[i] = r.f32(p.xemb[i]);
+  // LayerNorm forwards done by the previous residual GEMM's epilogue (Knobs: MMT_LN_FUSE, MMT_LN_FUSE_FWD)
+  const int ln_fuse = kn.ln_fuse != 0 ? kn.ln_fuse_fwd : 0;
   const bool fuse_fwd = ln_fuse && !f8 && (C == 256 || (C == 512 && ln_fuse == 2));
   std::vector<char> ln1_done(M, 0), lnf_done(M, 0);
   for (int l = 0; l < c->L && r.rc == MMT_OK; ++l) {
@@ -1170,46 +1327,29 @@ int run_forward(mmt_ctx* c, Runner& r, const int64_t* const* idx, const int64_t*
     // attention dropout keep bits: layer 0's made on the side stream while the first LayerNorm and
     // Q/K/V GEMMs run, all later layers' while layer 0 computes (two forks, two joins per forward)
     if (r.drop && l == 0) gen_masks(0);
-    LnBatch lb{}; lb.count = 0;
-    for (int i = 0; i < M; ++i) {
-      if (ln1_done[i]) continue;
-      LnProblem& q = lb.p[lb.count++];
-      q.x = xin[i]; q.gamma = r.P(x[i].ln1w); q.beta = r.P(x[i].ln1b);
-      q.y = r.W<bf16_t>(a[i].a); q.mean = r.W<float>(a[i].mean1); q.rstd = r.W<float>(a[i].rstd1);
-      ln8(q, a[i].a8, a[i].as8);
+    {
+      LnBatch lb{};
+      for (int i = 0; i < M; ++i)
+        if (!ln1_done[i]) lb.p[lb.count++] = ln(LN1, l, i, xin[i]);
+      if (lb.count) r.ok(mmt_launch_ln_fwd(lb, R, C, r.s), "ln1_fwd");
+      std::fill(ln1_done.begin(), ln1_done.end(), 0);
     }
-    if (lb.count) r.ok(mmt_launch_ln_fwd(lb, R, C, r.s), "ln1_fwd");
-    std::fill(ln1_done.begin(), ln1_done.end(), 0);
-    lb.count = M;
-    GemmBatch g{}; g.count = M;
-    // per-head stage 2 (model.py:39, 44, 49) fused into the stage-1 GEMM's epilogue at hs 32 / 64
-    // (qkv2_fused), else its own launch; MMT_QKV2_FUSE=0 keeps the separate kernel
-    static const bool qkv2_fuse = mmt_env_int("MMT_QKV2_FUSE", 1) != 0;
-    for (int i = 0; i < M; ++i) {
-      g.p[i] = f8 ? gp_f8(r.W<uint8_t>(a[i].a8), C, r.W<uint8_t>(a[i].as8), ldsC, w8, x[i].W1, R)
-                  : gp_fwd(r.W<bf16_t>(a[i].a), C, wpk, x[i].W1, R);
-      g.p[i].bias = r.P(x[i].b1); g.p[i].o16 = r.W<bf16_t>(a[i].h1); g.p[i].ldo16 = ldh1;
-    }
+    // Q/K/V stage 1; the per-head stage 2 in its epilogue at hs 32 / 64 (Knobs: MMT_QKV2_FUSE), else its own launch
+    GemmBatch qkv1 = gemms(M, [&](int i) {
+      return lin(a[i].a, a[i].a8, a[i].as8, C, ldsC, x[i].W1, x[i].b1).out16(r.b16(a[i].h1), ldh1);
+    });
     // (the 128 x 128 bf16 tile only: not on the fp8 kernel, not where the GEMM takes the 256 x 256 tile)
-    const bool fuse_qkv2 = qkv2_fuse && (c->hh == 16 || c->hh == 32) && !f8 && !mmt_gemm_wgrad_big(g);
-    AttnBatch ab{}; ab.count = M;
-    for (int i = 0; i < M; ++i) {
-      AttnProblem& q = ab.p[i];
-      bf16_t* qkv = r.W<bf16_t>(a[i].qkv);
-      q.q = qkv + C; q.q_ld = 3 * C; q.k[0] = qkv; q.v[0] = qkv + 2 * C; q.kv_ld = 3 * C; q.kv_hstride = hs;
-      q.o = r.W<bf16_t>(a[i].o); q.o_ld = C; q.lse[0] = r.W<float>(a[i].lse); q.nstreams = 1;
-      r.set_drop(q, l, i, DS_SA_PROB);
-      if (r.drop) q.dmask[0] = r.W<uint32_t>(a[i].dm);
-    }
+    const bool fuse_qkv2 = kn.qkv2_fuse != 0 && (c->hh == 16 || c->hh == 32) && !f8 && !mmt_gemm_wgrad_big(qkv1);
+    AttnBatch ab = batch_of<AttnBatch>(M, [&](int i) { return r.self_attn(a[i], l, i); });
     // Q / K / V on chip (mmt_set_attn_qkv_onchip; training forwards only): exactly where this GEMM would make
     // them in its epilogue and the backward will take the one-pass hs-32 kernel with the stage-2 backward in it.
     // Bit 0: the attention forward makes them from h1 and W2; bit 1: the backward will; both: stage 2 leaves this
     // GEMM and the rows are never written. The same for every layer, kept in c->onchip for the backward.
     int oc = 0;
-    if (c->onchip_req && fuse_qkv2 && g_attn_qkv2 && mmt_attn_bwd_fuses_qkv2(ab, T, hs) && !(ldh1 & 7)) {
+    if (c->onchip_req && fuse_qkv2 && kn.attn_qkv2 && mmt_attn_bwd_fuses_qkv2(ab, T, hs) && !(ldh1 & 7)) {
       oc = c->onchip_req;
       for (int i = 0; i < M; ++i)
-        if (((uintptr_t)r.W<bf16_t>(a[i].h1) | (uintptr_t)r.P(x[i].w2)) & 15) oc = 0;
+        if (((uintptr_t)r.b16(a[i].h1) | (uintptr_t)r.P(x[i].w2)) & 15) oc = 0;
     }
     if (l == 0) c->onchip = oc;
     else if (oc != c->onchip) {
@@ -1217,21 +1357,19 @@ int run_forward(mmt_ctx* c, Runner& r, const int64_t* const* idx, const int64_t*
       break;
     }
     for (int i = 0; i < M; ++i) {
+      GemmProblem& g = qkv1.p[i];
       if (fuse_qkv2 && oc != 3) {
-        g.p[i].qkv2_w2 = r.P(x[i].w2); g.p[i].qkv2_out = r.W<bf16_t>(a[i].qkv);
-        g.p[i].qkv2_ld = 3 * C; g.p[i].qkv2_hh = c->hh;
+        g.qkv2_w2 = r.P(x[i].w2); g.qkv2_out = r.b16(a[i].qkv); g.qkv2_ld = 3 * C; g.qkv2_hh = c->hh;
       }
       // both bits: no stage 2 and no Q/K/V store, but h1 bit for bit as the fused launch rounds it
-      if (oc == 3) g.p[i].qkv2_h1_only = 1;
-      if (oc & 1) { ab.p[i].oc_h1 = r.W<bf16_t>(a[i].h1); ab.p[i].oc_ld = ldh1; ab.p[i].oc_w2 = r.P(x[i].w2); }
+      if (oc == 3) g.qkv2_h1_only = 1;
+      if (oc & 1) { ab.p[i].oc_h1 = r.b16(a[i].h1); ab.p[i].oc_ld = ldh1; ab.p[i].oc_w2 = r.P(x[i].w2); }
     }
-    if (f8) r.gemm8(g, EPI_BIAS_TANH_BF16, "qkv1");
-    else r.gemm(g, true, true, EPI_BIAS_TANH_BF16, 1, "qkv1");
-    for (int i = 0; i < M; ++i) { g.p[i].qkv2_out = nullptr; g.p[i].qkv2_h1_only = 0; }  // g is reused by the next GEMMs
+    r.fgemm(qkv1, EPI_BIAS_TANH_BF16, "qkv1", f8);
     if (!fuse_qkv2) {
       Qkv2Batch qb{}; qb.count = M;
       for (int i = 0; i < M; ++i) {
-        qb.p[i].h1 = r.W<bf16_t>(a[i].h1); qb.p[i].w2 = r.P(x[i].w2); qb.p[i].out = r.W<bf16_t>(a[i].qkv);
+        qb.p[i].h1 = r.b16(a[i].h1); qb.p[i].w2 = r.P(x[i].w2); qb.p[i].out = r.b16(a[i].qkv);
       }
       r.ok(mmt_launch_qkv2_fwd(qb, R, 3 * H, hs, ldh1, 3 * C, r.s), "qkv2_fwd");
     }
@@ -1244,217 +1382,129 @@ int run_forward(mmt_ctx* c, Runner& r, const int64_t* const* idx, const int64_t*
         for (int ll = 1; ll < c->L; ++ll) gen_masks(ll);
         // until layer 1's join the later layers' keep bits fill the CUs the side stream can reach: a
         // ping-pong GEMM block needs a CU with none of them on it (all its VGPRs and 128 KiB of LDS), the
-        // 128 x 256 tile fits beside them (MMT_MASK_T2=0: the ping-pong kernel throughout)
-        if (mask_t2) r.gemm_hint = 1;
+        // 128 x 256 tile fits beside them (Knobs: MMT_MASK_T2)
+        if (kn.mask_t2) r.gemm_hint = 1;
       }
     }
     r.attn(ab, false, scale, "attn_fwd");
     if (r.drop && ahead_mode == 2 && l + 1 < c->L) {
       gen_masks(l + 1);
-      if (mask_t2) r.gemm_hint = 1;
+      if (kn.mask_t2) r.gemm_hint = 1;
     }
-    // ln2 in the fused out-projection's epilogue (MMT_LN2_FUSE=0: the separate ln_fwd pass; fp8 keeps
-    // it, the pass also writes the MX-fp8 copy)
-    static const bool ln2_env = mmt_env_int("MMT_LN2_FUSE", 1) != 0;
-    const bool ln2_fuse = ln2_env && !f8;
+    // out-projection: Linear(C, C/2) -> tanh -> Linear(C/2, C) -> dropout -> + residual (model.py:82-92,
+    // 224), fused into one launch where the shape allows (C = 256 / 512), else two GEMMs. The fused launch owns
+    // whole rows: ln2 runs in its epilogue (Knobs: MMT_LN2_FUSE; not fp8, whose ln2 pass also writes the MX copy)
+    const bool ln2_fuse = kn.ln2_fuse != 0 && !f8;
     bool ln2_done = false;
     {
-      // out-projection: Linear(C, C/2) -> tanh -> Linear(C/2, C) -> dropout -> + residual (model.py:82-92,
-      // 224), fused into one launch where the shape allows (C = 256 / 512), else two GEMMs
-      GemmProblem pg1[MAXM], pg2[MAXM];
-      for (int i = 0; i < M; ++i) {
-        GemmProblem& g1 = pg1[i];
-        g1 = gp_fwd(r.W<bf16_t>(a[i].o), C, wpk, x[i].P0, R);
-        g1.bias = r.P(x[i].bp0); g1.o16 = r.W<bf16_t>(a[i].p1); g1.ldo16 = ldp;
-        GemmProblem& g2 = pg2[i];
-        g2 = gp_fwd(r.W<bf16_t>(a[i].p1), ldp, wpk, x[i].P2, R);
-        g2.bias = r.P(x[i].bp2); g2.resid = xin[i]; g2.ldres = C;
-        g2.o32 = r.W<float>(a[i].x1); g2.ldc = C;
-        r.set_drop(g2, l, i, DS_SA_PROJ);
-        if (ln2_fuse) {  // the fused launch owns whole rows: ln2 runs in its epilogue (no MX-fp8 copy)
-          g2.lnf_gamma = r.P(x[i].ln2w); g2.lnf_beta = r.P(x[i].ln2b); g2.lnf_y = r.W<bf16_t>(a[i].c);
-          g2.lnf_mean = r.W<float>(a[i].mean2); g2.lnf_rstd = r.W<float>(a[i].rstd2);
-        }
-      }
-      const bool fused = r.mlp2(pg1, pg2, M, "proj");  // (nothing launched when it returns false)
+      GemmBatch p0 = gemms(M, [&](int i) {
+        return r.linear(r.b16(a[i].o), C, x[i].P0, x[i].bp0).out16(r.b16(a[i].p1), ldp);
+      });
+      GemmBatch p2 = gemms(M, [&](int i) {
+        Lin g = r.linear(r.b16(a[i].p1), ldp, x[i].P2, x[i].bp2).out32(r.f32(a[i].x1), C, xin[i]);
+        r.set_drop(g, l, i, DS_SA_PROJ);
+        if (ln2_fuse) fuse_next_ln(g, ln(LN2, l, i, nullptr));
+        return g;
+      });
+      const bool fused = r.mlp2(p0.p, p2.p, M, "proj");  // (nothing launched when it returns false)
       ln2_done = fused && ln2_fuse;
       if (!fused) {
-        for (int i = 0; i < M; ++i) g.p[i] = pg1[i];
-        r.gemm(g, true, true, EPI_BIAS_TANH_BF16, 1, "proj0");
-        for (int i = 0; i < M; ++i) { g.p[i] = pg2[i]; g.p[i].lnf_y = nullptr; }
-        r.gemm(g, true, true, EPI_BIAS_RESID_F32, 1, "proj2");
+        r.fgemm(p0, EPI_BIAS_TANH_BF16, "proj0");
+        for (int i = 0; i < M; ++i) p2.p[i].lnf_y = nullptr;  // the plain GEMM runs no LayerNorm
+        r.fgemm(p2, EPI_BIAS_RESID_F32, "proj2");
       }
     }
-    if (!ln2_done) {
-      for (int i = 0; i < M; ++i) {
-        lb.p[i].x = r.W<float>(a[i].x1); lb.p[i].gamma = r.P(x[i].ln2w); lb.p[i].beta = r.P(x[i].ln2b);
-        lb.p[i].y = r.W<bf16_t>(a[i].c); lb.p[i].mean = r.W<float>(a[i].mean2); lb.p[i].rstd = r.W<float>(a[i].rstd2);
-        ln8(lb.p[i], a[i].c8, a[i].cs8);
-      }
-      r.ok(mmt_launch_ln_fwd(lb, R, C, r.s), "ln2_fwd");
-    }
-    for (int i = 0; i < M; ++i) {
-      g.p[i] = f8 ? gp_f8(r.W<uint8_t>(a[i].c8), C, r.W<uint8_t>(a[i].cs8), ldsC, w8, x[i].F0, R)
-                  : gp_fwd(r.W<bf16_t>(a[i].c), C, wpk, x[i].F0, R);
-      g.p[i].bias = r.P(x[i].bf0); g.p[i].o16 = r.W<bf16_t>(a[i].f); g.p[i].ldo16 = 4 * C;
-      if (r.c->relu_bits) { g.p[i].mask8 = r.W<uint8_t>(a[i].fm); g.p[i].ldm8 = 4 * C / 8; }
-      if (f8) { g.p[i].o8 = r.W<uint8_t>(a[i].f8); g.p[i].ld8 = 4 * C; g.p[i].s8 = r.W<uint8_t>(a[i].fs8); g.p[i].lds8 = ldsF; }
-    }
-    const GemmBatch gf0 = g;  // the ffn0 problems: launched below, alone or inside the one-launch FFN
-    auto run_ffn0 = [&] {
-      if (f8) r.gemm8(gf0, EPI_BIAS_RELU_BF16, "ffn0");
-      else r.gemm(gf0, true, true, EPI_BIAS_RELU_BF16, 1, "ffn0");
-    };
-    for (int i = 0; i < M; ++i) g.p[i].mask8 = nullptr;  // g is reused
-    for (int i = 0; i < M; ++i) {
-      g.p[i] = f8 ? gp_f8(r.W<uint8_t>(a[i].f8), 4 * C, r.W<uint8_t>(a[i].fs8), ldsF, w8, x[i].F2, R)
-                  : gp_fwd(r.W<bf16_t>(a[i].f), 4 * C, wpk, x[i].F2, R);
-      g.p[i].bias = r.P(x[i].bf2); g.p[i].resid = r.W<float>(a[i].x1); g.p[i].ldres = C;
-      g.p[i].o32 = r.W<float>(a[i].x2); g.p[i].ldc = C;
-      if (c->any_cross) { g.p[i].o16 = r.W<bf16_t>(a[i].x2h); g.p[i].ldo16 = C; }
-      r.set_drop(g.p[i], l, i, DS_FFN);
-    }
-    bool lnc_done = false;
-    if (fuse_fwd) {
-      // the LayerNorm that reads each problem's x2 next: lnc (cross-attention query side), else the
+    if (!ln2_done)
+      r.ok(mmt_launch_ln_fwd(lns(M, [&](int i) { return ln(LN2, l, i, r.f32(a[i].x1)); }), R, C, r.s), "ln2_fwd");
+    // FFN (model.py:162-175, 225)
+    GemmBatch f0 = gemms(M, [&](int i) {
+      Lin g = lin(a[i].c, a[i].c8, a[i].cs8, C, ldsC, x[i].F0, x[i].bf0).out16(r.b16(a[i].f), 4 * C);
+      if (c->relu_bits) { g.mask8 = r.W<uint8_t>(a[i].fm); g.ldm8 = 4 * C / 8; }
+      if (f8) { g.o8 = r.W<uint8_t>(a[i].f8); g.ld8 = 4 * C; g.s8 = r.W<uint8_t>(a[i].fs8); g.lds8 = ldsF; }
+      return g;
+    });
+    GemmBatch f2 = gemms(M, [&](int i) {
+      Lin g = lin(a[i].f, a[i].f8, a[i].fs8, 4 * C, ldsF, x[i].F2, x[i].bf2).out32(r.f32(a[i].x2), C, r.f32(a[i].x1));
+      if (c->any_cross) g.out16(r.b16(a[i].x2h), C);
+      r.set_drop(g, l, i, DS_FFN);
+      // the LayerNorm that reads this problem's x2 next: lnc (cross-attention query side), else the
       // next layer's ln1, else (last layer) the post block's
-      for (int i = 0; i < M; ++i) {
-        GemmProblem& q = g.p[i];
-        if (c->any_cross && x[i].cross) {
-          q.lnf_gamma = r.P(x[i].lncw); q.lnf_beta = r.P(x[i].lncb); q.lnf_y = r.W<bf16_t>(a[i].d);
-          q.lnf_mean = r.W<float>(a[i].meanc); q.lnf_rstd = r.W<float>(a[i].rstdc);
-        } else if (l + 1 < c->L) {
-          const LM& xn = c->lm[(size_t)(l + 1) * M + i];
-          const ActLM& an = p.act[(size_t)(l + 1) * M + i];
-          q.lnf_gamma = r.P(xn.ln1w); q.lnf_beta = r.P(xn.ln1b); q.lnf_y = r.W<bf16_t>(an.a);
-          q.lnf_mean = r.W<float>(an.mean1); q.lnf_rstd = r.W<float>(an.rstd1);
-        } else {
-          q.lnf_gamma = r.P(c->post[i].lnw); q.lnf_beta = r.P(c->post[i].lnb); q.lnf_y = r.W<bf16_t>(p.lnf16[i]);
-          q.lnf_mean = r.W<float>(p.meanf[i]); q.lnf_rstd = r.W<float>(p.rstdf[i]);
-        }
+      if (fuse_fwd) {
+        const PostRows w = post_rows(i);
+        fuse_next_ln(g, x[i].cross ? ln(LNC, l, i, nullptr) : l + 1 < c->L ? ln(LN1, l + 1, i, nullptr)
+                        : ln_fwd_problem(nullptr, r.P(c->post[i].lnw), r.P(c->post[i].lnb), w.y, w.mean, w.rstd));
       }
-    }
+      return g;
+    });
     // both products as one launch (mmt_set_ffn_fused; C = 256, bf16, no ReLU bits: ffn_fwd_kernel, the bits of
     // the pair below); false (nothing launched) for every other shape or a field it does not implement
-    const bool ffn_one = !f8 && !c->relu_bits && C == 256 && g_ffn_fused != 0 && r.ffn(gf0.p, g.p, M, "ffn");
-    if (!ffn_one) run_ffn0();
-    if (fuse_fwd) {
-      if (ffn_one || r.gemm_resid_ln(g, "ffn2")) {
-        for (int i = 0; i < M; ++i) {
-          if (c->any_cross && x[i].cross) lnc_done = true;
-          else if (l + 1 < c->L) ln1_done[i] = 1;
-          else lnf_done[i] = 1;
-        }
-      } else {
-        for (int i = 0; i < M; ++i) g.p[i].lnf_y = nullptr;
-        r.gemm(g, true, true, EPI_BIAS_RESID_F32, 1, "ffn2");
+    const bool ffn_one = !f8 && !c->relu_bits && C == 256 && kn.ffn_fused != 0 && r.ffn(f0.p, f2.p, M, "ffn");
+    if (!ffn_one) r.fgemm(f0, EPI_BIAS_RELU_BF16, "ffn0", f8);
+    bool lnc_done = false;
+    if (fuse_fwd && (ffn_one || r.gemm_resid_ln(f2, "ffn2"))) {
+      for (int i = 0; i < M; ++i) {
+        if (x[i].cross) lnc_done = true;
+        else if (l + 1 < c->L) ln1_done[i] = 1;
+        else lnf_done[i] = 1;
       }
     } else if (!ffn_one) {
-      if (f8) r.gemm8(g, EPI_BIAS_RESID_F32, "ffn2");
-      else r.gemm(g, true, true, EPI_BIAS_RESID_F32, 1, "ffn2");
+      for (int i = 0; i < M; ++i) f2.p[i].lnf_y = nullptr;  // the plain GEMM runs no LayerNorm
+      r.fgemm(f2, EPI_BIAS_RESID_F32, "ffn2", f8);
     }
-    for (int i = 0; i < M; ++i) g.p[i].lnf_y = nullptr;  // g is reused: no stale LayerNorm outputs
     std::vector<const float*> xout(M);
-    for (int i = 0; i < M; ++i) xout[i] = r.W<float>(a[i].x2);
+    for (int i = 0; i < M; ++i) xout[i] = r.f32(a[i].x2);
     if (c->any_cross) {
-      std::vector<int> cx;
-      for (int i = 0; i < M; ++i) if (x[i].cross) cx.push_back(i);
-      LnBatch lc{}; lc.count = (int)cx.size();
-      GemmBatch gq{}; gq.count = (int)cx.size();
-      for (size_t u = 0; u < cx.size(); ++u) {
-        const int i = cx[u];
-        lc.p[u].x = r.W<float>(a[i].x2); lc.p[u].gamma = r.P(x[i].lncw); lc.p[u].beta = r.P(x[i].lncb);
-        lc.p[u].y = r.W<bf16_t>(a[i].d); lc.p[u].mean = r.W<float>(a[i].meanc); lc.p[u].rstd = r.W<float>(a[i].rstdc);
-        ln8(lc.p[u], a[i].d8, a[i].ds8);
-        gq.p[u] = f8 ? gp_f8(r.W<uint8_t>(a[i].d8), C, r.W<uint8_t>(a[i].ds8), ldsC, w8, x[i].Wq, R)
-                     : gp_fwd(r.W<bf16_t>(a[i].d), C, wpk, x[i].Wq, R);
-        gq.p[u].o16 = r.W<bf16_t>(a[i].qc); gq.p[u].ldo16 = C;
-      }
-      if (!lnc_done) r.ok(mmt_launch_ln_fwd(lc, R, C, r.s), "lnc_fwd");
-      if (f8) r.gemm8(gq, EPI_STORE_BF16, "ca_q");
-      else r.gemm(gq, true, true, EPI_STORE_BF16, 1, "ca_q");
+      const std::vector<int> cx = cross_set(x, M);
+      const int nc = (int)cx.size();
+      if (!lnc_done)
+        r.ok(mmt_launch_ln_fwd(lns(nc, [&](int u) { return ln(LNC, l, cx[u], r.f32(a[cx[u]].x2)); }), R, C, r.s),
+             "lnc_fwd");
+      r.fgemm(gemms(nc, [&](int u) {
+                const int i = cx[u];
+                return lin(a[i].d, a[i].d8, a[i].ds8, C, ldsC, x[i].Wq, -1).out16(r.b16(a[i].qc), C);
+              }), EPI_STORE_BF16, "ca_q", f8);
       // KV projections of the other modalities' post-FFN states, grouped up to 8 per launch
-      GemmBatch gk{}; gk.count = 0;
-      for (int i : cx) {
-        int jj = 0;
-        for (int j = 0; j < M; ++j) {
-          if (j == i) continue;
-          gk.p[gk.count] = gp_fwd(r.W<bf16_t>(a[j].x2h), C, wpk, x[i].Wkv[jj], R);
-          gk.p[gk.count].o16 = r.W<bf16_t>(a[i].kv[jj]); gk.p[gk.count].ldo16 = 2 * C;
-          ++gk.count; ++jj;
-          if (gk.count == MMT_MAX_GROUP) { r.gemm(gk, true, true, EPI_STORE_BF16, 1, "ca_kv"); gk.count = 0; }
-        }
-      }
-      if (gk.count) r.gemm(gk, true, true, EPI_STORE_BF16, 1, "ca_kv");
-      AttnBatch cb{}; cb.count = (int)cx.size();
-      for (size_t u = 0; u < cx.size(); ++u) {
+      GemmBatch gk{};
+      for_each_cross_kv(cx, M, false,
+                        [&](int i, int j, int jj) {
+                          gk.p[gk.count++] = r.linear(r.b16(a[j].x2h), C, x[i].Wkv[jj], -1).out16(r.b16(a[i].kv[jj]), 2 * C);
+                        },
+                        [&] { r.fgemm(gk, EPI_STORE_BF16, "ca_kv"); gk = GemmBatch{}; });
+      r.attn(batch_of<AttnBatch>(nc, [&](int u) { return r.cross_attn(a[cx[u]], l, cx[u]); }), false, scale, "ca_attn_fwd");
+      GemmBatch c0 = gemms(nc, [&](int u) {
         const int i = cx[u];
-        AttnProblem& q = cb.p[u];
-        q.q = r.W<bf16_t>(a[i].qc); q.q_ld = C;
-        for (int j = 0; j < M - 1; ++j) {
-          bf16_t* kv = r.W<bf16_t>(a[i].kv[j]);
-          q.k[j] = kv; q.v[j] = kv + hs; q.oj[j] = r.W<bf16_t>(a[i].ocj[j]); q.lse[j] = r.W<float>(a[i].lsej[j]);
-        }
-        q.kv_ld = 2 * C; q.kv_hstride = 2 * hs; q.o = r.W<bf16_t>(a[i].oc); q.o_ld = C; q.nstreams = M - 1;
-        r.set_drop(q, l, i, DS_CA_PROB);
-        if (r.drop)
-          for (int j = 0; j < M - 1; ++j) q.dmask[j] = r.W<uint32_t>(a[i].dmj[j]);
-      }
-      r.attn(cb, false, scale, "ca_attn_fwd");
-      GemmBatch g0{}; g0.count = (int)cx.size();
-      GemmBatch g2{}; g2.count = (int)cx.size();
-      for (size_t u = 0; u < cx.size(); ++u) {
+        return r.linear(r.b16(a[i].oc), C, x[i].C0, x[i].bc0).out16(r.b16(a[i].pc), ldp);
+      });
+      GemmBatch c2 = gemms(nc, [&](int u) {
         const int i = cx[u];
-        g0.p[u] = gp_fwd(r.W<bf16_t>(a[i].oc), C, wpk, x[i].C0, R);
-        g0.p[u].bias = r.P(x[i].bc0); g0.p[u].o16 = r.W<bf16_t>(a[i].pc); g0.p[u].ldo16 = ldp;
-        g2.p[u] = gp_fwd(r.W<bf16_t>(a[i].pc), ldp, wpk, x[i].C2, R);
-        g2.p[u].bias = r.P(x[i].bc2); g2.p[u].resid = r.W<float>(a[i].x2); g2.p[u].ldres = C;
-        g2.p[u].o32 = r.W<float>(a[i].x3); g2.p[u].ldc = C;
-        r.set_drop(g2.p[u], l, i, DS_CA_PROJ);
-        xout[i] = r.W<float>(a[i].x3);
-      }
-      if (!r.mlp2(g0.p, g2.p, g0.count, "ca_proj")) {
-        r.gemm(g0, true, true, EPI_BIAS_TANH_BF16, 1, "ca_proj0");
-        r.gemm(g2, true, true, EPI_BIAS_RESID_F32, 1, "ca_proj2");
+        Lin g = r.linear(r.b16(a[i].pc), ldp, x[i].C2, x[i].bc2).out32(r.f32(a[i].x3), C, r.f32(a[i].x2));
+        r.set_drop(g, l, i, DS_CA_PROJ);
+        return g;
+      });
+      for (int i : cx) xout[i] = r.f32(a[i].x3);
+      if (!r.mlp2(c0.p, c2.p, nc, "ca_proj")) {
+        r.fgemm(c0, EPI_BIAS_TANH_BF16, "ca_proj0");
+        r.fgemm(c2, EPI_BIAS_RESID_F32, "ca_proj2");
       }
     }
     xin = xout;
   }
   if (r.rc != MMT_OK) return r.rc;
   // post block + CE
-  LnBatch lf{}; lf.count = 0;
-  GemmBatch h0{}; h0.count = M;
-  GemmBatch h2{}; h2.count = M;
-  for (int i = 0; i < M; ++i) {
-    if (!lnf_done[i]) {
-      LnProblem& q = lf.p[lf.count++];
-      q.x = xin[i]; q.gamma = r.P(c->post[i].lnw); q.beta = r.P(c->post[i].lnb);
-      q.y = r.W<bf16_t>(p.lnf16[i]); q.mean = r.W<float>(p.meanf[i]); q.rstd = r.W<float>(p.rstdf[i]);
-    }
-    h0.p[i] = gp_fwd(r.W<bf16_t>(p.lnf16[i]), C, wpk, c->post[i].H0, R);
-    h0.p[i].bias = r.P(c->post[i].b0); h0.p[i].o16 = r.W<bf16_t>(p.hh[i]); h0.p[i].ldo16 = c->ldvh[i];
-    h2.p[i] = gp_fwd(r.W<bf16_t>(p.hh[i]), c->ldvh[i], wpk, c->post[i].H2, R);
-    h2.p[i].bias = r.P(c->post[i].b2); h2.p[i].o32 = logits[i]; h2.p[i].ldc = c->V[i];
-  }
+  LnBatch lf{};
   if (tgt) {  // the loss accumulators and this forward's flag word, zeroed by the LN launch
     lf.zero_f = losses; lf.nzero_f = M;
     lf.zero_i = r.W<int>(p.flag); lf.nzero_i = 1;
   }
-  if (lf.count) {
-    r.ok(mmt_launch_ln_fwd(lf, R, C, r.s), "lnf_fwd");
-  } else if (tgt) {  // every post-block LayerNorm was fused: zero the accumulators here
-    r.ok(hipMemsetAsync(losses, 0, sizeof(float) * M, r.s), "memset losses");
-    r.ok(hipMemsetAsync(r.W<int>(p.flag), 0, sizeof(int), r.s), "memset flag");
-  }
-  r.gemm(h0, true, true, EPI_BIAS_TANH_BF16, 1, "head0");
-  r.gemm(h2, true, true, EPI_STORE_F32, 1, "head2");
+  static const char* const post_labels[3] = {"lnf_fwd", "head0", "head2"};
+  run_post(c, r, R, xin, lnf_done.data(), post_rows, logits, lf, post_labels);
   if (tgt && r.rc == MMT_OK) {
     CeBatch cb{}; cb.count = M;
     for (int i = 0; i < M; ++i) {
-      cb.p[i].logits = logits[i]; cb.p[i].tgt = tgt[i]; cb.p[i].dlogits = r.W<bf16_t>(p.dlog[i]);
+      cb.p[i].logits = logits[i]; cb.p[i].tgt = tgt[i]; cb.p[i].dlogits = r.b16(p.dlog[i]);
       cb.p[i].loss = losses + i; cb.p[i].V = c->V[i]; cb.p[i].ld_d = c->ldv[i];
       cb.p[i].flag = r.W<int>(p.flag); cb.p[i].bit = 1 << i;
-      cb.p[i].part = r.W<float>(p.celoss[i]);
+      cb.p[i].part = r.f32(p.celoss[i]);
     }
     r.ok(mmt_launch_ce_fwd(cb, R, r.s), "ce_fwd");
   }
@@ -1484,12 +1534,12 @@ struct DecWhere {
 
 int run_decode(mmt_ctx* c, Runner& r, const DecWhere& w, int t, const int64_t* const* idx, float* const* logits) {
   const int M = c->M, C = c->C, H = c->H, hs = c->hs, B = r.B, T = c->T;
-  const int R = w.rows;  // compact rows
+  const int R = w.rows;  // compact rows (== r.R)
   const int ldh1 = r8(3 * H * c->hh), ldp = r8(C / 2);
   const float scale = 1.0f / std::sqrt((float)hs);
   Plan& p = c->plan;
-  const bf16_t* wpk = r.W<bf16_t>(p.pack);
-  r.wpk = wpk;
+  r.wpk = r.b16(p.pack);
+  auto D = [&](size_t off) { return w.at<bf16_t>(off); };  // compact bf16 rows
   auto scatter_rows = [&](bf16_t* cache, int ld, const bf16_t* rows, const char* what) {
     // compact row b -> cache row b*T + t
     r.ok(hipMemcpy2DAsync(cache + (size_t)t * ld, (size_t)T * ld * 2, rows, (size_t)ld * 2, (size_t)ld * 2, B,
@@ -1500,6 +1550,10 @@ int run_decode(mmt_ctx* c, Runner& r, const DecWhere& w, int t, const int64_t* c
     // compact row r -> tail row r*max_new + (t - n0)
     r.ok(hipMemcpy2DAsync(tail + (size_t)(t - w.n0) * ld, (size_t)tail_rows * ld * 2, rows, (size_t)ld * 2,
                           (size_t)ld * 2, R, hipMemcpyDeviceToDevice, r.s), what);
+  };
+  // every LayerNorm of the step writes the same compact rows: y as given, the statistics (unused) in d.mean / d.rstd
+  auto ln = [&](int i, const float* xi, int64_t gamma, int64_t beta, size_t y) {
+    return ln_fwd_problem(xi, r.P(gamma), r.P(beta), D(y), w.at<float>(w.dec[i].mean), w.at<float>(w.dec[i].rstd));
   };
   {
     EmbBatch eb{};
@@ -1515,171 +1569,115 @@ int run_decode(mmt_ctx* c, Runner& r, const DecWhere& w, int t, const int64_t* c
   for (int l = 0; l < c->L && r.rc == MMT_OK; ++l) {
     const LM* x = &c->lm[(size_t)l * M];
     const ActLM* a = &p.act[(size_t)l * M];
+    const Plan::Dec* d = w.dec;
     auto X = [&](int i, int k) { return w.at<float>(w.dec_x[((size_t)l * M + i) * 3 + k]); };
-    LnBatch lb{}; lb.count = M;
-    for (int i = 0; i < M; ++i) {
-      const Plan::Dec& d = w.dec[i];
-      lb.p[i].x = xin[i]; lb.p[i].gamma = r.P(x[i].ln1w); lb.p[i].beta = r.P(x[i].ln1b);
-      lb.p[i].y = w.at<bf16_t>(d.a16); lb.p[i].mean = w.at<float>(d.mean); lb.p[i].rstd = w.at<float>(d.rstd);
-    }
-    r.ok(mmt_launch_ln_fwd(lb, R, C, r.s), "dec_ln1");
-    GemmBatch g{}; g.count = M;
-    for (int i = 0; i < M; ++i) {
-      g.p[i] = gp_fwd(w.at<bf16_t>(w.dec[i].a16), C, wpk, x[i].W1, R);
-      g.p[i].bias = r.P(x[i].b1); g.p[i].o16 = w.at<bf16_t>(w.dec[i].h1); g.p[i].ldo16 = ldh1;
-    }
-    r.gemm(g, true, true, EPI_BIAS_TANH_BF16, 1, "dec_qkv1");
+    r.ok(mmt_launch_ln_fwd(lns(M, [&](int i) { return ln(i, xin[i], x[i].ln1w, x[i].ln1b, d[i].a16); }), R, C, r.s),
+         "dec_ln1");
+    r.fgemm(gemms(M, [&](int i) { return r.linear(D(d[i].a16), C, x[i].W1, x[i].b1).out16(D(d[i].h1), ldh1); }),
+            EPI_BIAS_TANH_BF16, "dec_qkv1");
     Qkv2Batch qb{}; qb.count = M;
     for (int i = 0; i < M; ++i) {
-      qb.p[i].h1 = w.at<bf16_t>(w.dec[i].h1); qb.p[i].w2 = r.P(x[i].w2); qb.p[i].out = w.at<bf16_t>(w.dec[i].qkv);
+      qb.p[i].h1 = D(d[i].h1); qb.p[i].w2 = r.P(x[i].w2); qb.p[i].out = D(d[i].qkv);
       // fan-out: stage 2 writes row t - n0 of the self-attention tail itself (leading dimension max_new * 3C; the
       // kernel forms (int64) row * ld and writes the 3C columns only), so no append copy and no compact K|Q|V row
-      if (w.fan) qb.p[i].out = w.at<bf16_t>(w.fan->sa_tail[(size_t)l * M + i]) + (size_t)(t - w.n0) * 3 * C;
+      if (w.fan) qb.p[i].out = D(w.fan->sa_tail[(size_t)l * M + i]) + (size_t)(t - w.n0) * 3 * C;
     }
     r.ok(mmt_launch_qkv2_fwd(qb, R, 3 * H, hs, ldh1, w.fan ? tail_rows * 3 * C : 3 * C, r.s), "dec_qkv2");
     if (w.fan) {
-      FanoutAttnBatch fb{}; fb.count = M;
-      for (int i = 0; i < M; ++i) {
-        const bf16_t* cache = r.W<bf16_t>(a[i].qkv);
-        bf16_t* tail = w.at<bf16_t>(w.fan->sa_tail[(size_t)l * M + i]);
-        FanoutAttnProblem& q = fb.p[i];
-        q.q = tail + (size_t)(t - w.n0) * 3 * C + C; q.q_ld = tail_rows * 3 * C;  // the query: the tail row just written
-        q.k[0] = cache; q.v[0] = cache + 2 * C; q.kv_ld = 3 * C; q.kv_hstride = hs;
+      const FanoutAttnBatch fb = batch_of<FanoutAttnBatch>(M, [&](int i) {
+        FanoutAttnProblem q{};
+        bf16_t* tail = D(w.fan->sa_tail[(size_t)l * M + i]);
+        // the query: the tail row just written
+        self_attn_io(q, tail + (size_t)(t - w.n0) * 3 * C + C, tail_rows * 3 * C, r.b16(a[i].qkv), D(d[i].o16), C, hs);
         q.tk[0] = tail; q.tv[0] = tail + 2 * C; q.tail_ld = 3 * C;
-        q.o = w.at<bf16_t>(w.dec[i].o16); q.o_ld = C; q.nstreams = 1;
-      }
+        return q;
+      });
       r.ok(mmt_launch_attn_decode_fanout(fb, B, w.S, w.n0, t, T, H, hs, tail_rows, scale, r.s), "fan_attn");
+    } else {
+      const DecodeAttnBatch ab = batch_of<DecodeAttnBatch>(M, [&](int i) {
+        DecodeAttnProblem q{};
+        scatter_rows(r.b16(a[i].qkv), 3 * C, D(d[i].qkv), "dec_kv_append");
+        self_attn_io(q, D(d[i].qkv) + C, 3 * C, r.b16(a[i].qkv), D(d[i].o16), C, hs);
+        return q;
+      });
+      r.ok(mmt_launch_attn_decode(ab, B, t, T, H, hs, scale, r.s), "dec_attn");
     }
-    DecodeAttnBatch ab{}; ab.count = w.fan ? 0 : M;
-    for (int i = 0; i < ab.count; ++i) {
-      bf16_t* cache = r.W<bf16_t>(a[i].qkv);
-      scatter_rows(cache, 3 * C, w.at<bf16_t>(w.dec[i].qkv), "dec_kv_append");
-      DecodeAttnProblem& q = ab.p[i];
-      q.q = w.at<bf16_t>(w.dec[i].qkv) + C; q.q_ld = 3 * C;
-      q.k[0] = cache; q.v[0] = cache + 2 * C; q.kv_ld = 3 * C; q.kv_hstride = hs;
-      q.o = w.at<bf16_t>(w.dec[i].o16); q.o_ld = C; q.nstreams = 1;
-    }
-    r.ok(mmt_launch_attn_decode(ab, B, t, T, H, hs, scale, r.s), "dec_attn");
-    for (int i = 0; i < M; ++i) {
-      g.p[i] = gp_fwd(w.at<bf16_t>(w.dec[i].o16), C, wpk, x[i].P0, R);
-      g.p[i].bias = r.P(x[i].bp0); g.p[i].o16 = w.at<bf16_t>(w.dec[i].p1); g.p[i].ldo16 = ldp;
-    }
-    r.gemm(g, true, true, EPI_BIAS_TANH_BF16, 1, "dec_proj0");
-    for (int i = 0; i < M; ++i) {
-      g.p[i] = gp_fwd(w.at<bf16_t>(w.dec[i].p1), ldp, wpk, x[i].P2, R);
-      g.p[i].bias = r.P(x[i].bp2); g.p[i].resid = xin[i]; g.p[i].ldres = C;
-      g.p[i].o32 = X(i, 0); g.p[i].ldc = C;
-    }
-    r.gemm(g, true, true, EPI_BIAS_RESID_F32, 1, "dec_proj2");
-    for (int i = 0; i < M; ++i) {
-      const Plan::Dec& d = w.dec[i];
-      lb.p[i].x = X(i, 0); lb.p[i].gamma = r.P(x[i].ln2w); lb.p[i].beta = r.P(x[i].ln2b);
-      lb.p[i].y = w.at<bf16_t>(d.a16); lb.p[i].mean = w.at<float>(d.mean); lb.p[i].rstd = w.at<float>(d.rstd);
-    }
-    r.ok(mmt_launch_ln_fwd(lb, R, C, r.s), "dec_ln2");
-    for (int i = 0; i < M; ++i) {
-      g.p[i] = gp_fwd(w.at<bf16_t>(w.dec[i].a16), C, wpk, x[i].F0, R);
-      g.p[i].bias = r.P(x[i].bf0); g.p[i].o16 = w.at<bf16_t>(w.dec[i].f); g.p[i].ldo16 = 4 * C;
-    }
-    r.gemm(g, true, true, EPI_BIAS_RELU_BF16, 1, "dec_ffn0");
-    for (int i = 0; i < M; ++i) {
-      g.p[i] = gp_fwd(w.at<bf16_t>(w.dec[i].f), 4 * C, wpk, x[i].F2, R);
-      g.p[i].bias = r.P(x[i].bf2); g.p[i].resid = X(i, 0); g.p[i].ldres = C;
-      g.p[i].o32 = X(i, 1); g.p[i].ldc = C;
-      if (c->any_cross) { g.p[i].o16 = w.at<bf16_t>(w.dec[i].x2h); g.p[i].ldo16 = C; }
-    }
-    r.gemm(g, true, true, EPI_BIAS_RESID_F32, 1, "dec_ffn2");
+    r.fgemm(gemms(M, [&](int i) { return r.linear(D(d[i].o16), C, x[i].P0, x[i].bp0).out16(D(d[i].p1), ldp); }),
+            EPI_BIAS_TANH_BF16, "dec_proj0");
+    r.fgemm(gemms(M, [&](int i) { return r.linear(D(d[i].p1), ldp, x[i].P2, x[i].bp2).out32(X(i, 0), C, xin[i]); }),
+            EPI_BIAS_RESID_F32, "dec_proj2");
+    r.ok(mmt_launch_ln_fwd(lns(M, [&](int i) { return ln(i, X(i, 0), x[i].ln2w, x[i].ln2b, d[i].a16); }), R, C, r.s),
+         "dec_ln2");
+    r.fgemm(gemms(M, [&](int i) { return r.linear(D(d[i].a16), C, x[i].F0, x[i].bf0).out16(D(d[i].f), 4 * C); }),
+            EPI_BIAS_RELU_BF16, "dec_ffn0");
+    r.fgemm(gemms(M, [&](int i) {
+              Lin g = r.linear(D(d[i].f), 4 * C, x[i].F2, x[i].bf2).out32(X(i, 1), C, X(i, 0));
+              if (c->any_cross) g.out16(D(d[i].x2h), C);
+              return g;
+            }), EPI_BIAS_RESID_F32, "dec_ffn2");
     std::vector<const float*> xout(M);
     for (int i = 0; i < M; ++i) xout[i] = X(i, 1);
     if (c->any_cross) {
-      std::vector<int> cx;
-      for (int i = 0; i < M; ++i) if (x[i].cross) cx.push_back(i);
-      LnBatch lc{}; lc.count = (int)cx.size();
-      GemmBatch gq{}; gq.count = (int)cx.size();
-      for (size_t u = 0; u < cx.size(); ++u) {
-        const int i = cx[u];
-        const Plan::Dec& d = w.dec[i];
-        lc.p[u].x = X(i, 1); lc.p[u].gamma = r.P(x[i].lncw); lc.p[u].beta = r.P(x[i].lncb);
-        lc.p[u].y = w.at<bf16_t>(d.d16); lc.p[u].mean = w.at<float>(d.mean); lc.p[u].rstd = w.at<float>(d.rstd);
-        gq.p[u] = gp_fwd(w.at<bf16_t>(d.d16), C, wpk, x[i].Wq, R);
-        gq.p[u].o16 = w.at<bf16_t>(d.qc); gq.p[u].ldo16 = C;
-      }
-      r.ok(mmt_launch_ln_fwd(lc, R, C, r.s), "dec_lnc");
-      r.gemm(gq, true, true, EPI_STORE_BF16, 1, "dec_ca_q");
-      GemmBatch gk{}; gk.count = 0;
-      for (int i : cx) {
-        int jj = 0;
-        for (int j = 0; j < M; ++j) {
-          if (j == i) continue;
-          gk.p[gk.count] = gp_fwd(w.at<bf16_t>(w.dec[j].x2h), C, wpk, x[i].Wkv[jj], R);
-          gk.p[gk.count].o16 = w.at<bf16_t>(w.dec[i].kv[jj]); gk.p[gk.count].ldo16 = 2 * C;
-          ++gk.count; ++jj;
-          if (gk.count == MMT_MAX_GROUP) { r.gemm(gk, true, true, EPI_STORE_BF16, 1, "dec_ca_kv"); gk.count = 0; }
-        }
-      }
-      if (gk.count) r.gemm(gk, true, true, EPI_STORE_BF16, 1, "dec_ca_kv");
+      const std::vector<int> cx = cross_set(x, M);
+      const int nc = (int)cx.size();
+      r.ok(mmt_launch_ln_fwd(lns(nc, [&](int u) {
+                               const int i = cx[u];
+                               return ln(i, X(i, 1), x[i].lncw, x[i].lncb, d[i].d16);
+                             }), R, C, r.s), "dec_lnc");
+      r.fgemm(gemms(nc, [&](int u) {
+                const int i = cx[u];
+                return r.linear(D(d[i].d16), C, x[i].Wq, -1).out16(D(d[i].qc), C);
+              }), EPI_STORE_BF16, "dec_ca_q");
+      GemmBatch gk{};
+      for_each_cross_kv(cx, M, false,
+                        [&](int i, int j, int jj) {
+                          gk.p[gk.count++] = r.linear(D(d[j].x2h), C, x[i].Wkv[jj], -1).out16(D(d[i].kv[jj]), 2 * C);
+                        },
+                        [&] { r.fgemm(gk, EPI_STORE_BF16, "dec_ca_kv"); gk = GemmBatch{}; });
       if (w.fan) {
-        FanoutAttnBatch fb{}; fb.count = (int)cx.size();
-        for (size_t u = 0; u < cx.size(); ++u) {
+        const FanoutAttnBatch fb = batch_of<FanoutAttnBatch>(nc, [&](int u) {
           const int i = cx[u];
-          FanoutAttnProblem& q = fb.p[u];
-          q.q = w.at<bf16_t>(w.dec[i].qc); q.q_ld = C;
+          FanoutAttnProblem q{};
+          cross_attn_io(q, D(d[i].qc), [&](int j) { return r.b16(a[i].kv[j]); }, M - 1, D(d[i].oc), C, hs);
           for (int j = 0; j < M - 1; ++j) {
-            const bf16_t* kv = r.W<bf16_t>(a[i].kv[j]);
-            bf16_t* tail = w.at<bf16_t>(w.fan->ca_tail[((size_t)l * M + i) * MAXM + j]);
-            tail_append(tail, 2 * C, w.at<bf16_t>(w.dec[i].kv[j]), "fan_cakv_append");
-            q.k[j] = kv; q.v[j] = kv + hs; q.tk[j] = tail; q.tv[j] = tail + hs;
+            bf16_t* tail = D(w.fan->ca_tail[((size_t)l * M + i) * MAXM + j]);
+            tail_append(tail, 2 * C, D(d[i].kv[j]), "fan_cakv_append");
+            q.tk[j] = tail; q.tv[j] = tail + hs;
           }
-          q.kv_ld = 2 * C; q.kv_hstride = 2 * hs; q.tail_ld = 2 * C;
-          q.o = w.at<bf16_t>(w.dec[i].oc); q.o_ld = C; q.nstreams = M - 1;
-        }
+          q.tail_ld = 2 * C;
+          return q;
+        });
         r.ok(mmt_launch_attn_decode_fanout(fb, B, w.S, w.n0, t, T, H, hs, tail_rows, scale, r.s), "fan_ca_attn");
+      } else {
+        const DecodeAttnBatch cb = batch_of<DecodeAttnBatch>(nc, [&](int u) {
+          const int i = cx[u];
+          DecodeAttnProblem q{};
+          for (int j = 0; j < M - 1; ++j) scatter_rows(r.b16(a[i].kv[j]), 2 * C, D(d[i].kv[j]), "dec_cakv_append");
+          cross_attn_io(q, D(d[i].qc), [&](int j) { return r.b16(a[i].kv[j]); }, M - 1, D(d[i].oc), C, hs);
+          return q;
+        });
+        r.ok(mmt_launch_attn_decode(cb, B, t, T, H, hs, scale, r.s), "dec_ca_attn");
       }
-      DecodeAttnBatch cb{}; cb.count = w.fan ? 0 : (int)cx.size();
-      for (size_t u = 0; u < (size_t)cb.count; ++u) {
-        const int i = cx[u];
-        DecodeAttnProblem& q = cb.p[u];
-        q.q = w.at<bf16_t>(w.dec[i].qc); q.q_ld = C;
-        for (int j = 0; j < M - 1; ++j) {
-          bf16_t* kv = r.W<bf16_t>(a[i].kv[j]);
-          scatter_rows(kv, 2 * C, w.at<bf16_t>(w.dec[i].kv[j]), "dec_cakv_append");
-          q.k[j] = kv; q.v[j] = kv + hs;
-        }
-        q.kv_ld = 2 * C; q.kv_hstride = 2 * hs; q.o = w.at<bf16_t>(w.dec[i].oc); q.o_ld = C; q.nstreams = M - 1;
-      }
-      r.ok(mmt_launch_attn_decode(cb, B, t, T, H, hs, scale, r.s), "dec_ca_attn");
-      GemmBatch g0{}; g0.count = (int)cx.size();
-      GemmBatch g2{}; g2.count = (int)cx.size();
-      for (size_t u = 0; u < cx.size(); ++u) {
-        const int i = cx[u];
-        g0.p[u] = gp_fwd(w.at<bf16_t>(w.dec[i].oc), C, wpk, x[i].C0, R);
-        g0.p[u].bias = r.P(x[i].bc0); g0.p[u].o16 = w.at<bf16_t>(w.dec[i].pc); g0.p[u].ldo16 = ldp;
-        g2.p[u] = gp_fwd(w.at<bf16_t>(w.dec[i].pc), ldp, wpk, x[i].C2, R);
-        g2.p[u].bias = r.P(x[i].bc2); g2.p[u].resid = X(i, 1); g2.p[u].ldres = C;
-        g2.p[u].o32 = X(i, 2); g2.p[u].ldc = C;
-        xout[i] = X(i, 2);
-      }
-      r.gemm(g0, true, true, EPI_BIAS_TANH_BF16, 1, "dec_ca_proj0");
-      r.gemm(g2, true, true, EPI_BIAS_RESID_F32, 1, "dec_ca_proj2");
+      r.fgemm(gemms(nc, [&](int u) {
+                const int i = cx[u];
+                return r.linear(D(d[i].oc), C, x[i].C0, x[i].bc0).out16(D(d[i].pc), ldp);
+              }), EPI_BIAS_TANH_BF16, "dec_ca_proj0");
+      r.fgemm(gemms(nc, [&](int u) {
+                const int i = cx[u];
+                return r.linear(D(d[i].pc), ldp, x[i].C2, x[i].bc2).out32(X(i, 2), C, X(i, 1));
+              }), EPI_BIAS_RESID_F32, "dec_ca_proj2");
+      for (int i : cx) xout[i] = X(i, 2);
     }
     xin = xout;
   }
   if (r.rc != MMT_OK) return r.rc;
-  LnBatch lf{}; lf.count = M;
-  GemmBatch h0{}; h0.count = M;
-  GemmBatch h2{}; h2.count = M;
-  for (int i = 0; i < M; ++i) {
-    const Plan::Dec& d = w.dec[i];
-    lf.p[i].x = xin[i]; lf.p[i].gamma = r.P(c->post[i].lnw); lf.p[i].beta = r.P(c->post[i].lnb);
-    lf.p[i].y = w.at<bf16_t>(d.lnf16); lf.p[i].mean = w.at<float>(d.mean); lf.p[i].rstd = w.at<float>(d.rstd);
-    h0.p[i] = gp_fwd(w.at<bf16_t>(d.lnf16), C, wpk, c->post[i].H0, R);
-    h0.p[i].bias = r.P(c->post[i].b0); h0.p[i].o16 = w.at<bf16_t>(d.hh); h0.p[i].ldo16 = c->ldvh[i];
-    h2.p[i] = gp_fwd(w.at<bf16_t>(d.hh), c->ldvh[i], wpk, c->post[i].H2, R);
-    h2.p[i].bias = r.P(c->post[i].b2); h2.p[i].o32 = logits[i]; h2.p[i].ldc = c->V[i];
-  }
-  r.ok(mmt_launch_ln_fwd(lf, R, C, r.s), "dec_lnf");
-  r.gemm(h0, true, true, EPI_BIAS_TANH_BF16, 1, "dec_head0");
-  r.gemm(h2, true, true, EPI_STORE_F32, 1, "dec_head2");
+  static const char* const post_labels[3] = {"dec_lnf", "dec_head0", "dec_head2"};
+  run_post(c, r, R, xin, nullptr,
+           [&](int i) {
+             const Plan::Dec& d = w.dec[i];
+             return PostRows{D(d.lnf16), w.at<float>(d.mean), w.at<float>(d.rstd), D(d.hh)};
+           },
+           logits, LnBatch{}, post_labels);
   return r.rc;
 }
 
@@ -1717,12 +1715,35 @@ void set_dres16_consumer(mmt_ctx* c, Runner& r, LnProblem& lp, int i, int lprev,
 }
 
 int run_backward_stage(mmt_ctx* c, Runner& r, int stage, const float* loss_grads, float* grads) {
-  const int M = c->M, C = c->C, H = c->H, hs = c->hs, R = r.R, B = r.B, T = c->T, L = c->L;
+  const int M = c->M, C = c->C, H = c->H, hs = c->hs, R = r.R, T = c->T, L = c->L;
   const int ldh1 = r8(3 * H * c->hh), ldp = r8(C / 2);
   const float scale = 1.0f / std::sqrt((float)hs);
+  const Knobs& kn = knobs();
   Plan& p = c->plan;
-  const bf16_t* wpk = r.W<bf16_t>(p.pack);
+  const bf16_t* wpk = r.b16(p.pack);
   const int par = stage & 1;  // copy of the side-stream-read scratch this stage writes (Plan)
+  // one Linear's two gradients from the rows g = dY (ld ldy): dW += dY^T X, and dX = dY W (the caller adds where it goes)
+  auto dw_of = [&](const bf16_t* g, int ldy, size_t x16, int ldx, const Mat& W) {
+    return gp_dw(g, ldy, r.b16(x16), ldx, grads, W, R);
+  };
+  auto dx_of = [&](const bf16_t* g, int ldy, const Mat& W) { return gp_dx(g, ldy, wpk, W, R); };
+  // ... dX as fp32 rows in dln (the input of the LayerNorm backward that follows), or as bf16 rows through the
+  // activation's derivative (aux: the saved activation) with the previous Linear's bias gradient as column sums
+  auto dx_ln = [&](const bf16_t* g, int ldy, const Mat& W, int i) {
+    GemmProblem d = dx_of(g, ldy, W);
+    d.o32 = r.f32(p.dln[i]); d.ldc = C;
+    return d;
+  };
+  auto dx_act = [&](const bf16_t* g, int ldy, const Mat& W, size_t aux, size_t out, int ld, int64_t dbias) {
+    GemmProblem d = dx_of(g, ldy, W);
+    d.aux = r.b16(aux); d.ldaux = ld; d.o16 = r.b16(out); d.ldo16 = ld; d.dbias = grads + dbias;
+    return d;
+  };
+  auto dx_16 = [&](const bf16_t* g, int ldy, const Mat& W, size_t out, int ld) {
+    GemmProblem d = dx_of(g, ldy, W);
+    d.o16 = r.b16(out); d.ldo16 = ld;
+    return d;
+  };
   if (stage == 0) {
     c->d16 = 0;
     // the active prefix only; in-place accumulation (mmt_set_grad_accumulate) adds to what is there
@@ -1744,47 +1765,34 @@ int run_backward_stage(mmt_ctx* c, Runner& r, int stage, const float* loss_grads
       }
     }
     const float invR = 1.0f / (float)R;
-    GemmBatch dw{}; dw.count = M;
-    GemmBatch dx{}; dx.count = M;
+    auto scaled = [&](GemmProblem g, int i) { g.alpha_ptr = loss_grads + i; g.alpha = invR; return g; };
+    r.dwgemm(gemms(M, [&](int i) {
+               return scaled(dw_of(r.b16(p.dlog[i]), c->ldv[i], p.hh[i], c->ldvh[i], c->post[i].H2), i);
+             }), "head2_dw");
     ColsumBatch cs{}; cs.count = M;
-    for (int i = 0; i < M; ++i) {
-      const PostM& q = c->post[i];
-      const bf16_t* dl = r.W<bf16_t>(p.dlog[i]);
-      dw.p[i] = gp_dw(dl, c->ldv[i], r.W<bf16_t>(p.hh[i]), c->ldvh[i], grads, q.H2, R);
-      dw.p[i].alpha_ptr = loss_grads + i; dw.p[i].alpha = invR;
-      colsum_add(r, cs, i, dl, c->ldv[i], grads + q.b2, c->V[i], loss_grads + i, invR);
-      dx.p[i] = gp_dx(dl, c->ldv[i], wpk, q.H2, R);
-      dx.p[i].alpha_ptr = loss_grads + i; dx.p[i].alpha = invR;
-      dx.p[i].aux = r.W<bf16_t>(p.hh[i]); dx.p[i].ldaux = c->ldvh[i];
-      dx.p[i].o16 = r.W<bf16_t>(p.gbig[par][i]); dx.p[i].ldo16 = c->ldvh[i];
-    }
-    r.dwgemm(dw, "head2_dw");
+    for (int i = 0; i < M; ++i)
+      colsum_add(r, cs, i, r.b16(p.dlog[i]), c->ldv[i], grads + c->post[i].b2, c->V[i], loss_grads + i, invR);
     r.det_arm(cs);
     r.ok(mmt_launch_colsum(cs, R, r.s), "head2_db");
-    for (int i = 0; i < M; ++i) dx.p[i].dbias = grads + c->post[i].b0;  // head0 bias grad fused
-    r.gemm(dx, true, false, EPI_DTANH_BF16, 1, "head2_dx");
-    for (int i = 0; i < M; ++i) {
-      const PostM& q = c->post[i];
-      const bf16_t* g = r.W<bf16_t>(p.gbig[par][i]);
-      dw.p[i] = gp_dw(g, c->ldvh[i], r.W<bf16_t>(p.lnf16[i]), C, grads, q.H0, R);
-      dx.p[i] = gp_dx(g, c->ldvh[i], wpk, q.H0, R);
-      dx.p[i].o32 = r.W<float>(p.dln[i]); dx.p[i].ldc = C;
-    }
-    r.dwgemm(dw, "head0_dw");
+    r.gemm(gemms(M, [&](int i) {  // (head0 bias grad fused)
+             const PostM& q = c->post[i];
+             return scaled(dx_act(r.b16(p.dlog[i]), c->ldv[i], q.H2, p.hh[i], p.gbig[par][i], c->ldvh[i], q.b0), i);
+           }), true, false, EPI_DTANH_BF16, 1, "head2_dx");
+    r.dwgemm(gemms(M, [&](int i) { return dw_of(r.b16(p.gbig[par][i]), c->ldvh[i], p.lnf16[i], C, c->post[i].H0); }),
+             "head0_dw");
     r.flush();
-    LnBatch lb{}; lb.count = M;
     d16_advance(c);
-    std::vector<const float*> xfin(M);
-    for (int i = 0; i < M; ++i) {
+    const LnBatch lb = lns(M, [&](int i) {
       const ActLM& a = p.act[(size_t)(L - 1) * M + i];
-      xfin[i] = (L == 0) ? r.W<float>(p.xemb[i]) : (c->lm[(size_t)(L - 1) * M + i].cross ? r.W<float>(a.x3) : r.W<float>(a.x2));
-      r.ok(hipMemsetAsync(r.W<float>(p.dres[i]), 0, sizeof(float) * (size_t)R * C, r.s), "memset dres");
-      lb.p[i].x = xfin[i]; lb.p[i].gamma = r.P(c->post[i].lnw); lb.p[i].mean = r.W<float>(p.meanf[i]);
-      lb.p[i].rstd = r.W<float>(p.rstdf[i]); lb.p[i].dy = r.W<float>(p.dln[i]); lb.p[i].dx = r.W<float>(p.dres[i]);
-      set_dres16_consumer(c, r, lb.p[i], i, L - 1, grads);
-      lb.p[i].dgamma = grads + c->post[i].lnw; lb.p[i].dbeta = grads + c->post[i].lnb;
-    }
-    r.gemm_ln_bwd(dx, lb, R, C, "head0_dx", "lnf_bwd");
+      const float* xfin = (L == 0) ? r.f32(p.xemb[i]) : (c->lm[(size_t)(L - 1) * M + i].cross ? r.f32(a.x3) : r.f32(a.x2));
+      r.ok(hipMemsetAsync(r.f32(p.dres[i]), 0, sizeof(float) * (size_t)R * C, r.s), "memset dres");
+      LnProblem q = ln_bwd_problem(xfin, r.P(c->post[i].lnw), r.f32(p.meanf[i]), r.f32(p.rstdf[i]), r.f32(p.dln[i]),
+                                   r.f32(p.dres[i]), grads + c->post[i].lnw, grads + c->post[i].lnb);
+      set_dres16_consumer(c, r, q, i, L - 1, grads);
+      return q;
+    });
+    r.gemm_ln_bwd(gemms(M, [&](int i) { return dx_ln(r.b16(p.gbig[par][i]), c->ldvh[i], c->post[i].H0, i); }), lb,
+                  R, C, "head0_dx", "lnf_bwd");
     return r.rc;
   }
   // layer stage
@@ -1793,92 +1801,69 @@ int run_backward_stage(mmt_ctx* c, Runner& r, int stage, const float* loss_grads
   const ActLM* a = &p.act[(size_t)l * M];
   std::vector<const float*> xin(M);
   for (int i = 0; i < M; ++i) {
-    if (l == 0) xin[i] = r.W<float>(p.xemb[i]);
+    if (l == 0) xin[i] = r.f32(p.xemb[i]);
     else {
       const ActLM& pa = p.act[(size_t)(l - 1) * M + i];
-      xin[i] = c->lm[(size_t)(l - 1) * M + i].cross ? r.W<float>(pa.x3) : r.W<float>(pa.x2);
+      xin[i] = c->lm[(size_t)(l - 1) * M + i].cross ? r.f32(pa.x3) : r.f32(pa.x2);
     }
   }
-  if (c->any_cross) {
-    // MMT_DROP_COPY_FUSE=0 / mmt_set_drop_copy_fuse(0): the separate drop_copy pass for every modality
-    const bool fuse_copy = g_drop_copy_fuse != 0;
-    std::vector<int> cx;
-    for (int i = 0; i < M; ++i) if (x[i].cross) cx.push_back(i);
-    const int nc = (int)cx.size();
-    GemmBatch dw{}; dw.count = nc;
-    GemmBatch dx{}; dx.count = nc;
-    for (int u = 0; u < nc; ++u) {
-      const int i = cx[u];
-      // dres16[i] already carries this projection's dropout mask; its bias grad came with it
-      const bf16_t* g = d16_cur(c, r, i);
-      dw.p[u] = gp_dw(g, C, r.W<bf16_t>(a[i].pc), ldp, grads, x[i].C2, R);
-      dx.p[u] = gp_dx(g, C, wpk, x[i].C2, R);
-      dx.p[u].aux = r.W<bf16_t>(a[i].pc); dx.p[u].ldaux = ldp; dx.p[u].o16 = r.W<bf16_t>(p.gpc[par][i]); dx.p[u].ldo16 = ldp;
-      dx.p[u].dbias = grads + x[i].bc0;
-    }
-    r.dwgemm(dw, "ca_proj2_dw");
-    GemmProblem pdx0[MAXM];
-    for (int u = 0; u < nc; ++u) {
-      const int i = cx[u];
-      pdx0[u] = gp_dx(r.W<bf16_t>(p.gpc[par][i]), ldp, wpk, x[i].C0, R);
-      pdx0[u].o16 = r.W<bf16_t>(p.gdo[i]); pdx0[u].ldo16 = C;
-    }
-    const bool fused = r.mlp2(dx.p, pdx0, nc, "ca_proj_dx", true);
-    if (!fused) r.gemm(dx, true, false, EPI_DTANH_BF16, 1, "ca_proj2_dx");
-    for (int u = 0; u < nc; ++u) {
-      const int i = cx[u];
-      const bf16_t* g = r.W<bf16_t>(p.gpc[par][i]);
-      dw.p[u] = gp_dw(g, ldp, r.W<bf16_t>(a[i].oc), C, grads, x[i].C0, R);
-      dx.p[u] = pdx0[u];
-    }
-    r.dwgemm(dw, "ca_proj0_dw");
-    if (!fused) r.gemm(dx, true, false, EPI_STORE_BF16, 1, "ca_proj0_dx");
+  // the backward of this layer's LayerNorm n on modality i (input rows xi): dy in dln, dx added to dres
+  auto ln_bwd = [&](const LnSite& n, int i, const float* xi) {
+    return ln_bwd_problem(xi, r.P(x[i].*n.w), r.f32(a[i].*n.mean), r.f32(a[i].*n.rstd), r.f32(p.dln[i]), r.f32(p.dres[i]),
+                          grads + x[i].*n.w, grads + x[i].*n.b);
+  };
+  // the backward of an out-projection pair (self- or cross-attention's: weights P0 / P2 or C0 / C2) of the n
+  // modalities at_(u), hidden rows a.*hid and input rows a.*in: the dres16 copy carries the projection's dropout mask (its output-bias grad came with it);
+  // both data gradients in one launch where the fused kernel takes the shape (C = 256 / 512), else two GEMMs
+  auto proj_bwd = [&](int n, auto&& at_, auto&& mats, size_t ActLM::*hid, size_t ActLM::*in, size_t (*gp)[MAXM],
+                      const char* const (&lab)[5]) {
+    GemmBatch dx2 = gemms(n, [&](int u) {
+      const int i = at_(u);
+      return dx_act(d16_cur(c, r, i), C, *mats(i).w2, a[i].*hid, gp[par][i], ldp, mats(i).b0);
+    });
+    r.dwgemm(gemms(n, [&](int u) { const int i = at_(u); return dw_of(d16_cur(c, r, i), C, a[i].*hid, ldp, *mats(i).w2); }),
+             lab[0]);
+    GemmBatch dx0 = gemms(n, [&](int u) { const int i = at_(u); return dx_16(r.b16(gp[par][i]), ldp, *mats(i).w0, p.gdo[i], C); });
+    const bool fused = r.mlp2(dx2.p, dx0.p, n, lab[1], true);
+    if (!fused) r.gemm(dx2, true, false, EPI_DTANH_BF16, 1, lab[2]);
+    r.dwgemm(gemms(n, [&](int u) { const int i = at_(u); return dw_of(r.b16(gp[par][i]), ldp, a[i].*in, C, *mats(i).w0); }),
+             lab[3]);
+    if (!fused) r.gemm(dx0, true, false, EPI_STORE_BF16, 1, lab[4]);
     r.flush();
-    AttnBatch ab{}; ab.count = nc;
-    for (int u = 0; u < nc; ++u) {
-      const int i = cx[u];
-      AttnProblem& q = ab.p[u];
-      q.q = r.W<bf16_t>(a[i].qc); q.q_ld = C;
-      for (int j = 0; j < M - 1; ++j) {
-        bf16_t* kv = r.W<bf16_t>(a[i].kv[j]);
-        q.k[j] = kv; q.v[j] = kv + hs; q.oj[j] = r.W<bf16_t>(a[i].ocj[j]); q.lse[j] = r.W<float>(a[i].lsej[j]);
-        q.dvec[j] = r.W<float>(p.dvec[i][j]);
-        bf16_t* dkv = r.W<bf16_t>(p.dkv[par][i][j]);
-        q.dk[j] = dkv; q.dv[j] = dkv + hs;
-      }
-      q.kv_ld = 2 * C; q.kv_hstride = 2 * hs; q.o = r.W<bf16_t>(a[i].oc); q.o_ld = C; q.nstreams = M - 1;
-      q.dout = r.W<bf16_t>(p.gdo[i]); q.dout_ld = C; q.dq = r.W<bf16_t>(p.gq[par][i]); q.dq_ld = C;
-      // fp32 rows for the one-pass hs-32 backward's dQ sum over the KV streams: dln is free here (the
-      // cross-query dX GEMM after the attention writes it)
-      q.dq32 = r.W<float>(p.dln[i]); q.dq32_ld = C;
-      q.dkv_ld = 2 * C; q.dkv_hstride = 2 * hs;
-      r.set_drop(q, l, i, DS_CA_PROB);
-      if (r.drop)
-        for (int j = 0; j < M - 1; ++j) q.dmask[j] = r.W<uint32_t>(a[i].dmj[j]);
-    }
-    r.attn(ab, true, scale, "ca_attn_bwd");
-    for (int u = 0; u < nc; ++u) {
-      const int i = cx[u];
-      const bf16_t* g = r.W<bf16_t>(p.gq[par][i]);
-      dw.p[u] = gp_dw(g, C, r.W<bf16_t>(a[i].d), C, grads, x[i].Wq, R);
-      dx.p[u] = gp_dx(g, C, wpk, x[i].Wq, R);
-      dx.p[u].o32 = r.W<float>(p.dln[i]); dx.p[u].ldc = C;
-    }
-    r.dwgemm(dw, "ca_q_dw");
-    LnBatch lc{}; lc.count = nc;
-    for (int u = 0; u < nc; ++u) {
-      const int i = cx[u];
-      lc.p[u].x = r.W<float>(a[i].x2); lc.p[u].gamma = r.P(x[i].lncw); lc.p[u].mean = r.W<float>(a[i].meanc);
-      lc.p[u].rstd = r.W<float>(a[i].rstdc); lc.p[u].dy = r.W<float>(p.dln[i]); lc.p[u].dx = r.W<float>(p.dres[i]);
-      lc.p[u].dgamma = grads + x[i].lncw; lc.p[u].dbeta = grads + x[i].lncb;
-    }
-    r.gemm_ln_bwd(dx, lc, R, C, "ca_q_dx", "lnc_bwd");
+  };
+  struct ProjMats { const Mat* w0; const Mat* w2; int64_t b0; };
+  if (c->any_cross) {
+    const std::vector<int> cx = cross_set(x, M);
+    const int nc = (int)cx.size();
+    static const char* const ca_labels[5] = {"ca_proj2_dw", "ca_proj_dx", "ca_proj2_dx", "ca_proj0_dw", "ca_proj0_dx"};
+    proj_bwd(nc, [&](int u) { return cx[u]; }, [&](int i) { return ProjMats{&x[i].C0, &x[i].C2, x[i].bc0}; }, &ActLM::pc,
+             &ActLM::oc, p.gpc, ca_labels);
+    r.attn(batch_of<AttnBatch>(nc, [&](int u) {
+             const int i = cx[u];
+             AttnProblem q = r.cross_attn(a[i], l, i);
+             for (int j = 0; j < M - 1; ++j) {
+               q.dvec[j] = r.f32(p.dvec[i][j]);
+               bf16_t* dkv = r.b16(p.dkv[par][i][j]);
+               q.dk[j] = dkv; q.dv[j] = dkv + hs;
+             }
+             q.dout = r.b16(p.gdo[i]); q.dout_ld = C; q.dq = r.b16(p.gq[par][i]); q.dq_ld = C;
+             // fp32 rows for the one-pass hs-32 backward's dQ sum over the KV streams: dln is free here (the
+             // cross-query dX GEMM after the attention writes it)
+             q.dq32 = r.f32(p.dln[i]); q.dq32_ld = C;
+             q.dkv_ld = 2 * C; q.dkv_hstride = 2 * hs;
+             return q;
+           }), true, scale, "ca_attn_bwd");
+    r.dwgemm(gemms(nc, [&](int u) { const int i = cx[u]; return dw_of(r.b16(p.gq[par][i]), C, a[i].d, C, x[i].Wq); }),
+             "ca_q_dw");
+    r.gemm_ln_bwd(gemms(nc, [&](int u) { const int i = cx[u]; return dx_ln(r.b16(p.gq[par][i]), C, x[i].Wq, i); }),
+                  lns(nc, [&](int u) { return ln_bwd(LNC, cx[u], r.f32(a[cx[u]].x2)); }), R, C, "ca_q_dx", "lnc_bwd");
     // KV projections: dWkv += dkv^T x2_j ; dres[j] += dkv Wkv (one launch per query modality:
     // different query modalities accumulate into the same dres[j]). The LAST query modality that
     // accumulates into dres[j] also writes its bf16 copy for the FFN backward in that epilogue (FFN
     // dropout mask, FFN output-bias gradient as column sums): a separate drop_copy pass re-read the
     // fp32 rows (6 x 38 us per step at the target). Only a modality no launch accumulates into (one
-    // cross modality: its own dres) keeps the copy pass.
+    // cross modality: its own dres) keeps the copy pass (Knobs: MMT_DROP_COPY_FUSE = 0: every modality does).
+    const bool fuse_copy = kn.drop_copy_fuse != 0;
     d16_advance(c);
     std::vector<int> last_writer(M, -1);
     for (int i : cx)
@@ -1888,128 +1873,78 @@ int run_backward_stage(mmt_ctx* c, Runner& r, int stage, const float* loss_grads
     // backward reads the copy): launches run in cx order and last_writer[j] is the last i of cx that
     // writes dres[j]; copied[j] checks that invariant as the launches are built
     std::vector<char> copied(M, 0);
-    for (int i : cx) {
-      GemmBatch kw{}; kw.count = 0;
-      GemmBatch kx{}; kx.count = 0;
-      int jj = 0;
-      for (int j = 0; j < M; ++j) {
-        if (j == i) continue;
-        if (copied[j]) return fail(c, MMT_ERR_STATE, "cross K/V dX: dres written after its fused bf16 copy");
-        const bf16_t* g = r.W<bf16_t>(p.dkv[par][i][jj]);
-        kw.p[kw.count++] = gp_dw(g, 2 * C, r.W<bf16_t>(a[j].x2h), C, grads, x[i].Wkv[jj], R);
-        GemmProblem d = gp_dx(g, 2 * C, wpk, x[i].Wkv[jj], R);
-        d.o32 = r.W<float>(p.dres[j]); d.ldc = C;
-        if (last_writer[j] == i && fuse_copy) {
-          copied[j] = 1;
-          d.o16 = d16_cur(c, r, j); d.ldo16 = C; d.dbias = grads + x[j].bf2;
-          r.set_drop(d, l, j, DS_FFN);
-        }
-        kx.p[kx.count++] = d;
-        ++jj;
-        if (kw.count == MMT_MAX_GROUP) {
-          r.dwgemm(kw, "ca_kv_dw"); r.gemm(kx, true, false, EPI_ACC_F32, 1, "ca_kv_dx");
-          kw.count = 0; kx.count = 0;
-        }
-      }
-      if (kw.count) { r.dwgemm(kw, "ca_kv_dw"); r.gemm(kx, true, false, EPI_ACC_F32, 1, "ca_kv_dx"); }
-    }
+    GemmBatch kw{}, kx{};
+    for_each_cross_kv(cx, M, true,
+                      [&](int i, int j, int jj) {
+                        if (copied[j] && r.rc == MMT_OK)
+                          r.rc = fail(c, MMT_ERR_STATE, "cross K/V dX: dres written after its fused bf16 copy");
+                        const bf16_t* g = r.b16(p.dkv[par][i][jj]);
+                        kw.p[kw.count++] = dw_of(g, 2 * C, a[j].x2h, C, x[i].Wkv[jj]);
+                        GemmProblem d = dx_of(g, 2 * C, x[i].Wkv[jj]);
+                        d.o32 = r.f32(p.dres[j]); d.ldc = C;
+                        if (last_writer[j] == i && fuse_copy) {
+                          copied[j] = 1;
+                          d.o16 = d16_cur(c, r, j); d.ldo16 = C; d.dbias = grads + x[j].bf2;
+                          r.set_drop(d, l, j, DS_FFN);
+                        }
+                        kx.p[kx.count++] = d;
+                      },
+                      [&] {
+                        r.dwgemm(kw, "ca_kv_dw");
+                        r.gemm(kx, true, false, EPI_ACC_F32, 1, "ca_kv_dx");
+                        kw = GemmBatch{}; kx = GemmBatch{};
+                      });
+    if (r.rc != MMT_OK) return r.rc;
     r.flush();
     // bf16 copy for the FFN backward of the modalities no fused epilogue covered
     DropCopyBatch db{}; db.count = 0;
     for (int i = 0; i < M; ++i) {
       if (fuse_copy && last_writer[i] >= 0) continue;
       DropCopyProblem& q = db.p[db.count++];
-      q.src = r.W<float>(p.dres[i]); q.dst = d16_cur(c, r, i); q.dsum = grads + x[i].bf2;
+      q.src = r.f32(p.dres[i]); q.dst = d16_cur(c, r, i); q.dsum = grads + x[i].bf2;
       r.set_drop(q, l, i, DS_FFN);
     }
     r.det_arm(db);
     if (db.count) r.ok(mmt_launch_drop_copy(db, R, C, r.s), "dres16");
   }
   if (r.rc != MMT_OK) return r.rc;
-  // FFN
-  GemmBatch dw{}; dw.count = M;
-  GemmBatch dx{}; dx.count = M;
-  LnBatch lb{}; lb.count = M;
-  for (int i = 0; i < M; ++i) {
-    // dres16[i] carries the FFN dropout mask; the FFN output-bias grad was summed with it
-    const bf16_t* g = d16_cur(c, r, i);
-    dw.p[i] = gp_dw(g, C, r.W<bf16_t>(a[i].f), 4 * C, grads, x[i].F2, R);
-    dx.p[i] = gp_dx(g, C, wpk, x[i].F2, R);
-    dx.p[i].aux = r.W<bf16_t>(a[i].f); dx.p[i].ldaux = 4 * C; dx.p[i].o16 = r.W<bf16_t>(p.gbig[par][i]); dx.p[i].ldo16 = 4 * C;
-    dx.p[i].dbias = grads + x[i].bf0;
-    if (r.c->relu_bits) { dx.p[i].mask8 = r.W<uint8_t>(a[i].fm); dx.p[i].ldm8 = 4 * C / 8; }  // ReLU' from bits
-  }
-  // MMT_DW_ATTN_SMALL=1: the FFN weight gradients (the side-stream launches still running when the
-  // self-attention backward starts) on the 128 x 128 tile, whose 64 KiB of LDS leave room on their CUs for
-  // one of the attention backward's 80 KiB workgroups
-  static const int dw_attn_small = mmt_env_int("MMT_DW_ATTN_SMALL", 0);
-  const int ffn_dw_hint = dw_attn_small ? 2 : 0;
-  r.dwgemm(dw, "ffn2_dw", ffn_dw_hint);
-  r.gemm(dx, true, false, EPI_DRELU_BF16, 1, "ffn2_dx");
-  for (int i = 0; i < M; ++i) {
-    const bf16_t* g = r.W<bf16_t>(p.gbig[par][i]);
-    dw.p[i] = gp_dw(g, 4 * C, r.W<bf16_t>(a[i].c), C, grads, x[i].F0, R);
-    dx.p[i] = gp_dx(g, 4 * C, wpk, x[i].F0, R);
-    dx.p[i].o32 = r.W<float>(p.dln[i]); dx.p[i].ldc = C;
-  }
-  r.dwgemm(dw, "ffn0_dw", ffn_dw_hint);
+  // FFN: dres16[i] carries the FFN dropout mask; the FFN output-bias grad was summed with it
+  const int ffn_dw_hint = kn.dw_attn_small ? 2 : 0;  // (Knobs: MMT_DW_ATTN_SMALL)
+  r.dwgemm(gemms(M, [&](int i) { return dw_of(d16_cur(c, r, i), C, a[i].f, 4 * C, x[i].F2); }), "ffn2_dw", ffn_dw_hint);
+  r.gemm(gemms(M, [&](int i) {
+           GemmProblem d = dx_act(d16_cur(c, r, i), C, x[i].F2, a[i].f, p.gbig[par][i], 4 * C, x[i].bf0);
+           if (c->relu_bits) { d.mask8 = r.W<uint8_t>(a[i].fm); d.ldm8 = 4 * C / 8; }  // ReLU' from bits
+           return d;
+         }), true, false, EPI_DRELU_BF16, 1, "ffn2_dx");
+  r.dwgemm(gemms(M, [&](int i) { return dw_of(r.b16(p.gbig[par][i]), 4 * C, a[i].c, C, x[i].F0); }), "ffn0_dw", ffn_dw_hint);
   r.flush();
   d16_advance(c);
-  for (int i = 0; i < M; ++i) {
-    lb.p[i].x = r.W<float>(a[i].x1); lb.p[i].gamma = r.P(x[i].ln2w); lb.p[i].mean = r.W<float>(a[i].mean2);
-    lb.p[i].rstd = r.W<float>(a[i].rstd2); lb.p[i].dy = r.W<float>(p.dln[i]); lb.p[i].dx = r.W<float>(p.dres[i]);
-    lb.p[i].dx16 = d16_cur(c, r, i); lb.p[i].dgamma = grads + x[i].ln2w; lb.p[i].dbeta = grads + x[i].ln2b;
-    r.set_drop(lb.p[i], l, i, DS_SA_PROJ);  // the copy feeds the SA projection backward
-    lb.p[i].dsum = grads + x[i].bp2;
-  }
-  r.gemm_ln_bwd(dx, lb, R, C, "ffn0_dx", "ln2_bwd");
+  r.gemm_ln_bwd(gemms(M, [&](int i) { return dx_ln(r.b16(p.gbig[par][i]), 4 * C, x[i].F0, i); }),
+                lns(M, [&](int i) {
+                  LnProblem q = ln_bwd(LN2, i, r.f32(a[i].x1));
+                  q.dx16 = d16_cur(c, r, i);
+                  r.set_drop(q, l, i, DS_SA_PROJ);  // the copy feeds the SA projection backward
+                  q.dsum = grads + x[i].bp2;
+                  return q;
+                }), R, C, "ffn0_dx", "ln2_bwd");
   // SA output projection
-  for (int i = 0; i < M; ++i) {
-    const bf16_t* g = d16_cur(c, r, i);
-    dw.p[i] = gp_dw(g, C, r.W<bf16_t>(a[i].p1), ldp, grads, x[i].P2, R);
-    dx.p[i] = gp_dx(g, C, wpk, x[i].P2, R);
-    dx.p[i].aux = r.W<bf16_t>(a[i].p1); dx.p[i].ldaux = ldp; dx.p[i].o16 = r.W<bf16_t>(p.gp[par][i]); dx.p[i].ldo16 = ldp;
-    dx.p[i].dbias = grads + x[i].bp0;
-  }
-  r.dwgemm(dw, "proj2_dw");
-  {
-    // both data-gradient products in one launch where the fused kernel takes the shape (C = 256 / 512)
-    GemmProblem pdx0[MAXM];
-    for (int i = 0; i < M; ++i) {
-      const bf16_t* g = r.W<bf16_t>(p.gp[par][i]);
-      pdx0[i] = gp_dx(g, ldp, wpk, x[i].P0, R);
-      pdx0[i].o16 = r.W<bf16_t>(p.gdo[i]); pdx0[i].ldo16 = C;
-    }
-    const bool fused = r.mlp2(dx.p, pdx0, M, "proj_dx", true);
-    if (!fused) r.gemm(dx, true, false, EPI_DTANH_BF16, 1, "proj2_dx");
-    for (int i = 0; i < M; ++i) {
-      const bf16_t* g = r.W<bf16_t>(p.gp[par][i]);
-      dw.p[i] = gp_dw(g, ldp, r.W<bf16_t>(a[i].o), C, grads, x[i].P0, R);
-      dx.p[i] = pdx0[i];
-    }
-    r.dwgemm(dw, "proj0_dw");
-    if (!fused) r.gemm(dx, true, false, EPI_STORE_BF16, 1, "proj0_dx");
-  }
-  r.flush();
-  AttnBatch ab{}; ab.count = M;
-  for (int i = 0; i < M; ++i) {
-    AttnProblem& q = ab.p[i];
-    bf16_t* qkv = r.W<bf16_t>(a[i].qkv);
-    bf16_t* gq = r.W<bf16_t>(p.gqkv[i]);
-    q.q = qkv + C; q.q_ld = 3 * C; q.k[0] = qkv; q.v[0] = qkv + 2 * C; q.kv_ld = 3 * C; q.kv_hstride = hs;
-    q.o = r.W<bf16_t>(a[i].o); q.o_ld = C; q.lse[0] = r.W<float>(a[i].lse); q.nstreams = 1;
-    q.dout = r.W<bf16_t>(p.gdo[i]); q.dout_ld = C; q.dvec[0] = r.W<float>(p.dvec[i][0]);
+  static const char* const sa_labels[5] = {"proj2_dw", "proj_dx", "proj2_dx", "proj0_dw", "proj0_dx"};
+  proj_bwd(M, [](int u) { return u; }, [&](int i) { return ProjMats{&x[i].P0, &x[i].P2, x[i].bp0}; }, &ActLM::p1, &ActLM::o, p.gp,
+           sa_labels);
+  AttnBatch ab = batch_of<AttnBatch>(M, [&](int i) {
+    AttnProblem q = r.self_attn(a[i], l, i);
+    bf16_t* gq = r.b16(p.gqkv[i]);
+    q.dout = r.b16(p.gdo[i]); q.dout_ld = C; q.dvec[0] = r.f32(p.dvec[i][0]);
     q.dq = gq + C; q.dq_ld = 3 * C; q.dk[0] = gq; q.dv[0] = gq + 2 * C; q.dkv_ld = 3 * C; q.dkv_hstride = hs;
-    r.set_drop(q, l, i, DS_SA_PROB);
-    if (r.drop) q.dmask[0] = r.W<uint32_t>(a[i].dm);
-  }
+    return q;
+  });
   // hs 32: the Q/K/V stage-2 backward runs in the attention kernel's epilogue (dQ / dK / dV stay on chip:
   // dh1, dW2, db1 leave it), so the separate qkv2 backward and its gqkv round trip go
-  const bool q2 = g_attn_qkv2 && mmt_attn_bwd_fuses_qkv2(ab, T, hs);
+  const bool q2 = kn.attn_qkv2 && mmt_attn_bwd_fuses_qkv2(ab, T, hs);
   if (q2)
     for (int i = 0; i < M; ++i) {
       AttnProblem& q = ab.p[i];
-      q.q2_h1 = r.W<bf16_t>(a[i].h1); q.q2_dh1 = r.W<bf16_t>(p.gh1[par][i]); q.q2_ld = ldh1;
+      q.q2_h1 = r.b16(a[i].h1); q.q2_dh1 = r.b16(p.gh1[par][i]); q.q2_ld = ldh1;
       q.q2_w2 = r.P(x[i].w2); q.q2_dw2 = grads + x[i].w2; q.q2_db1 = grads + x[i].b1;
       // Q / K / V on chip, as the forward latched it (bit 1: this kernel makes them from h1 and W2)
       if (c->onchip & 2) { q.oc_h1 = q.q2_h1; q.oc_ld = ldh1; q.oc_w2 = q.q2_w2; }
@@ -2017,12 +1952,6 @@ int run_backward_stage(mmt_ctx* c, Runner& r, int stage, const float* loss_grads
   if (c->onchip == 3 && !q2)  // (the knobs the forward decided on were changed since)
     return fail(c, MMT_ERR_STATE, "mmt_backward: the forward kept Q/K/V on chip (mmt_set_attn_qkv_onchip) and the "
                                   "backward that makes them again (mmt_set_attn_qkv2, mmt_attn_set_ring bit 6) is off");
-  Qkv2Batch qb{}; qb.count = M;
-  for (int i = 0; i < M; ++i) {
-    qb.p[i].h1 = r.W<bf16_t>(a[i].h1); qb.p[i].w2 = r.P(x[i].w2); qb.p[i].dout = r.W<bf16_t>(p.gqkv[i]);
-    qb.p[i].dh1 = r.W<bf16_t>(p.gh1[par][i]); qb.p[i].dw2 = grads + x[i].w2;
-    qb.p[i].db1 = grads + x[i].b1;  // stage-1 bias gradient: column sums of dh1, fused
-  }
   // dh1 rows are padded to ldh1 (a multiple of 8) and the qkv2 backward writes only the 3 H hh columns;
   // the stage-1 dX GEMM reads K in 8-column chunks against zero weight-pack pad rows, so the pad must be
   // finite: zeroed once per workspace (no kernel writes it). Garbage there made the gradient NaN at
@@ -2031,29 +1960,30 @@ int run_backward_stage(mmt_ctx* c, Runner& r, int stage, const float* loss_grads
     const size_t cols = 3 * (size_t)H * c->hh;
     for (int k = 0; k < 2; ++k)
       for (int i = 0; i < M; ++i)
-        r.ok(hipMemset2DAsync(r.W<bf16_t>(p.gh1[k][i]) + cols, (size_t)ldh1 * 2, 0, ((size_t)ldh1 - cols) * 2, (size_t)R, r.s),
+        r.ok(hipMemset2DAsync(r.b16(p.gh1[k][i]) + cols, (size_t)ldh1 * 2, 0, ((size_t)ldh1 - cols) * 2, (size_t)R, r.s),
              "gh1 pad");
     p.gh1_pad_ws = r.ws;
   }
   r.attn(ab, true, scale, "attn_bwd");
-  r.det_arm(qb);
-  if (!q2) r.ok(mmt_launch_qkv2_bwd(qb, R, 3 * H, hs, ldh1, 3 * C, r.s), "qkv2_bwd");
-  for (int i = 0; i < M; ++i) {
-    const bf16_t* g = r.W<bf16_t>(p.gh1[par][i]);
-    dw.p[i] = gp_dw(g, ldh1, r.W<bf16_t>(a[i].a), C, grads, x[i].W1, R);
-    dx.p[i] = gp_dx(g, ldh1, wpk, x[i].W1, R);
-    dx.p[i].o32 = r.W<float>(p.dln[i]); dx.p[i].ldc = C;
+  if (!q2) {
+    Qkv2Batch qb{}; qb.count = M;
+    for (int i = 0; i < M; ++i) {
+      qb.p[i].h1 = r.b16(a[i].h1); qb.p[i].w2 = r.P(x[i].w2); qb.p[i].dout = r.b16(p.gqkv[i]);
+      qb.p[i].dh1 = r.b16(p.gh1[par][i]); qb.p[i].dw2 = grads + x[i].w2;
+      qb.p[i].db1 = grads + x[i].b1;  // stage-1 bias gradient: column sums of dh1, fused
+    }
+    r.det_arm(qb);
+    r.ok(mmt_launch_qkv2_bwd(qb, R, 3 * H, hs, ldh1, 3 * C, r.s), "qkv2_bwd");
   }
-  r.dwgemm(dw, "qkv1_dw");
+  r.dwgemm(gemms(M, [&](int i) { return dw_of(r.b16(p.gh1[par][i]), ldh1, a[i].a, C, x[i].W1); }), "qkv1_dw");
   r.flush();
   d16_advance(c);
-  for (int i = 0; i < M; ++i) {
-    lb.p[i].x = xin[i]; lb.p[i].gamma = r.P(x[i].ln1w); lb.p[i].mean = r.W<float>(a[i].mean1);
-    lb.p[i].rstd = r.W<float>(a[i].rstd1); lb.p[i].dy = r.W<float>(p.dln[i]); lb.p[i].dx = r.W<float>(p.dres[i]);
-    lb.p[i].dgamma = grads + x[i].ln1w; lb.p[i].dbeta = grads + x[i].ln1b;
-    set_dres16_consumer(c, r, lb.p[i], i, l - 1, grads);
-  }
-  r.gemm_ln_bwd(dx, lb, R, C, "qkv1_dx", "ln1_bwd");
+  r.gemm_ln_bwd(gemms(M, [&](int i) { return dx_ln(r.b16(p.gh1[par][i]), ldh1, x[i].W1, i); }),
+                lns(M, [&](int i) {
+                  LnProblem q = ln_bwd(LN1, i, xin[i]);
+                  set_dres16_consumer(c, r, q, i, l - 1, grads);
+                  return q;
+                }), R, C, "qkv1_dx", "ln1_bwd");
   return r.rc;
 }
 
@@ -2104,18 +2034,15 @@ int ensure_device_tables(mmt_ctx* c) {
 }
 
 // the side stream (weight-gradient GEMMs in the backward, dropout keep bits in the forward), made
-// lazily on the caller's current device; MMT_SIDE_STREAM=0 runs everything on the caller's stream
+// lazily on the caller's current device (Knobs: MMT_SIDE_STREAM, MMT_SIDE_PRIORITY)
 void ensure_side(mmt_ctx* c) {
-  static const bool use_side = mmt_env_int("MMT_SIDE_STREAM", 1) != 0;
   int dev = -1;
-  if (!use_side || hipGetDevice(&dev) != hipSuccess || (c->side && c->side_device == dev)) return;
+  if (knobs().side_stream == 0 || hipGetDevice(&dev) != hipSuccess || (c->side && c->side_device == dev)) return;
   if (c->side) (void)hipStreamDestroy(c->side);
   for (auto& e : c->evpool) (void)hipEventDestroy(e);  // events of the previous device
   c->evpool.clear();
   c->side = nullptr;
-  // MMT_SIDE_PRIORITY (optional): HIP stream priority of the side stream (lower = higher priority,
-  // clamped to the device's range); unset = default priority
-  static const char* prio_env = getenv("MMT_SIDE_PRIORITY");
+  const char* prio_env = knobs().side_priority;
   // (a CU-masked side stream measured far slower -- it cannot be created non-blocking, so it
   // serialises against the caller's stream: profiles/r3q_side_cumask_ab.txt; removed in round 4)
   hipError_t ce;
@@ -2169,7 +2096,7 @@ mmt_ctx* mmt_create(const mmt_config* cfg) {
   }
   if (c->M - 1 > MMT_MAX_STREAMS) { g_create_err = "too many KV streams"; delete c; return nullptr; }
   c->fp8 = cfg->precision == 1;
-  c->relu_bits = g_relu_bits != 0;
+  c->relu_bits = knobs().relu_bits != 0;
   build_layout(c);
   return c;
 }
@@ -2231,7 +2158,7 @@ int mmt_forward(mmt_ctx* c, void* stream, int32_t batch, const int64_t* const* i
   if (rc) return rc;
   c->side_off = c->side_off_req;
   c->det = c->det_req;
-  c->onchip_req = training ? g_attn_qkv_onchip : 0;
+  c->onchip_req = training ? knobs().attn_qkv_onchip : 0;
   c->onchip = 0;
   Runner r{c, (hipStream_t)stream, workspace, params, nullptr, batch, batch * c->T};
   // dropout (training mode only, as nn.Dropout): one seed per training forward, reused by its backward
@@ -2425,10 +2352,7 @@ int mmt_backward_stage(mmt_ctx* c, void* stream, int32_t stage, const float* los
   const bool defer = c->defer_join && r.side_stream();
   if (defer && stage >= 2)  // the side stream's work of stage - 2 read this stage's scratch copies
     r.ok(hipStreamWaitEvent(r.s, c->stage_ev[stage & 1], 0), "stream wait");
-  // MMT_FLUSH_HOLD=1: one side-stream fork per stage (every stage but the last layer's, whose weight
-  // gradients would otherwise only start after its data-gradient chain, at the end of the step)
-  static const int flush_hold = mmt_env_int("MMT_FLUSH_HOLD", 0);
-  r.hold = defer && flush_hold && stage < c->L;
+  r.hold = defer && knobs().flush_hold && stage < c->L;  // (Knobs: MMT_FLUSH_HOLD)
   const int rc = run_backward_stage(c, r, stage, loss_grads, grads);
   r.hold = false;
   if (defer) {
@@ -2563,7 +2487,7 @@ extern "C" int mmt_probe_set(mmt_ctx* c, const char* label) {
   }
   // event pairs for the recorded launches, made here (event creation is a host call of tens of
   // microseconds: inside the timed loop it starved the GPU); recording stops when they run out
-  static const size_t pool = (size_t)mmt_env_int("MMT_PROBE_EVENTS", 4096);
+  const size_t pool = (size_t)knobs().probe_events;
   while (!c->probe_pats.empty() && c->probe_pool.size() < pool) {
     hipEvent_t a, b;
     if (hipEventCreate(&a) != hipSuccess) break;
