@@ -766,15 +766,30 @@ int mmt_gemm_set_t2(int v);
  * bits 4-7 weight gradients: 0 = K-step 64 x 2 LDS stages, 1 = 32 x 2, 2 = 32 x 3, 3 = 32 x 4,
  * 4 = 64 x 3, 5 = 32 x 3 and 6 = 32 x 2 at 3+ blocks per CU (64-row epilogue passes). 256x256 tile:
  * bits 8-11 (0 = environment / default policy, 1 / 2 / 3 = BK 32 x 4 / x 3 / x 2); bit 16: the 256x256 tile
- * whatever K. Returns -1 for a field out of range. variant < 0: the default policy (128x128: 6 for
- * bf16-output epilogues without an aux operand, else 0; 256x256: 1 for the weight gradients, else
- * BK 64 x 2). */
+ * whatever K (M, N >= 256); bit 17: the 256x256 ping-pong kernel wherever it is built (weight gradients and the
+ * row-wide LayerNorm-fused launches included), bit 18 (without bit 17): never, the 256x256 ring instead; neither:
+ * the environment (MMT_GEMM8, MMT_GEMM8_LN, MMT_GEMM8_DW). Returns -1 for a field out of range. variant < 0:
+ * the default policy (128x128: 6 for bf16-output epilogues without an aux operand, else 0; 256x256: 1 for
+ * the weight gradients, else BK 64 x 2). */
 int mmt_gemm_set_variant(int variant);
 /* splits: split-K factor of EPI atomic_f32 launches (<= 0: automatic) */
 int mmt_op_gemm(void* stream, int32_t a_kc, int32_t b_kc, int32_t epi, int32_t splits, int32_t M, int32_t N,
                 int32_t K, const void* A, int32_t lda, const void* B, int32_t ldb, const float* bias,
                 const void* aux, int32_t ldaux, const float* resid, int32_t ldres, float* o32, int32_t ldc,
                 void* o16, int32_t ldo16, float alpha);
+/* The launch plan of a GEMM batch, from sizes alone: no stream, no device memory, no HIP call, so it runs
+ * without a GPU (tests/test_gemm_plan_cpu.py pins the dispatch policy with it). kind: 0 = mmt_op_gemm's launcher
+ * (a_kc, b_kc, epi, splits as there), 1 = weight gradient (slab_bytes: slab capacity, 0 = none), 2 = residual +
+ * LayerNorm forward, 3 = LayerNorm-backward, 4 = MX-fp8 (epi). count problems of M[g] x N[g] x K[g]; lda / ldb:
+ * 0 = K (or M / N for an MN-contiguous operand) padded to 8 elements (fp8: 16); tile_hint / dw_blocks: the
+ * engine's per-launch hints (0: none); flags bit 0: the fused Q/K/V stage 2 (hh 16), bit 1: the next LayerNorm's
+ * output. Writes 16 ints: status (0 ok, 1 nothing to launch, 2 invalid), family (0 ring, 1 ping-pong, 2 fp8),
+ * tile (0 = 128x128, 1 = 128x256, 2 = 256x256, 3 = 128x512), K-step, stages, minimum blocks per CU, SWAP,
+ * a_kc, b_kc, epi of the kernel, grid x / y / z, slabs (weight gradients: 1 = split-K slabs + reduce, 0 =
+ * accumulate in place), the reduce launch's blocks, the XCD-plane flag. */
+int mmt_op_gemm_plan(int32_t kind, int32_t a_kc, int32_t b_kc, int32_t epi, int32_t splits, int32_t count,
+                     const int32_t* M, const int32_t* N, const int32_t* K, int32_t lda, int32_t ldb, int32_t tile_hint,
+                     int32_t dw_blocks, int64_t slab_bytes, int32_t flags, int32_t* plan);
 /* Q/K/V projection of the engine's forward (reference model.py:36-50, every head's key / query /
  * value MLP at once): h1[M, N] = bf16(tanh(A[M, K] B[N, K]^T + bias)) (stage 1, N = 3 H hh) and, fused
  * into the same GEMM's epilogue, stage 2 out[m, blk*2hh + o] = bf16(sum_i w2[blk][o][i] h1[m, blk*hh + i])

@@ -19,6 +19,7 @@
 
 #include "mmt.h"
 #include "mmt_common.h"
+#include "mmt_gemm_plan.h"
 #include "mmt_kernels.h"
 
 namespace {
@@ -1179,7 +1180,7 @@ struct Runner {
     for (auto& q : pend) {
       if (!merged.empty()) {
         GemmBatch& m = merged.back().first;
-        if (m.count + q.first.count <= MMT_MAX_GROUP && mmt_gemm_wgrad_big(m) == mmt_gemm_wgrad_big(q.first)) {
+        if (m.count + q.first.count <= MMT_MAX_GROUP && wgrad_small(m) == wgrad_small(q.first)) {
           for (int g = 0; g < q.first.count; ++g) m.p[m.count++] = q.first.p[g];
           merged.back().second += std::string("+") + q.second;
           continue;
@@ -1189,6 +1190,10 @@ struct Runner {
     }
     for (auto& q : merged) wgrad(q.first, q.second.c_str(), ss);
     pend.clear();
+  }
+  // whether a weight-gradient batch stays on the 128 x 128 tile (launches can only be merged when equal)
+  static bool wgrad_small(const GemmBatch& b) {
+    return mmt_gemm_plan(b, GEMM_WGRAD).tile == GEMM_TILE_128;
   }
   void wgrad(const GemmBatch& b, const char* what, hipStream_t st) {
     launch(what, st, [&] { return mmt_launch_gemm_wgrad(b, W<float>(c->plan.slab), (int64_t)c->plan.slab_bytes, st); },
@@ -1338,8 +1343,9 @@ int run_forward(mmt_ctx* c, Runner& r, const int64_t* const* idx, const int64_t*
     GemmBatch qkv1 = gemms(M, [&](int i) {
       return lin(a[i].a, a[i].a8, a[i].as8, C, ldsC, x[i].W1, x[i].b1).out16(r.b16(a[i].h1), ldh1);
     });
-    // (the 128 x 128 bf16 tile only: not on the fp8 kernel, not where the GEMM takes the 256 x 256 tile)
-    const bool fuse_qkv2 = kn.qkv2_fuse != 0 && (c->hh == 16 || c->hh == 32) && !f8 && !mmt_gemm_wgrad_big(qkv1);
+    // (the 128 x 128 bf16 tile only: not on the fp8 kernel, not where the launch below leaves that tile)
+    const bool fuse_qkv2 = kn.qkv2_fuse != 0 && (c->hh == 16 || c->hh == 32) && !f8 &&
+                           mmt_gemm_plan(qkv1, GEMM_LINEAR, true, true, EPI_BIAS_TANH_BF16, 1, 0).tile == GEMM_TILE_128;
     AttnBatch ab = batch_of<AttnBatch>(M, [&](int i) { return r.self_attn(a[i], l, i); });
     // Q / K / V on chip (mmt_set_attn_qkv_onchip; training forwards only): exactly where this GEMM would make
     // them in its epilogue and the backward will take the one-pass hs-32 kernel with the stage-2 backward in it.

@@ -27,31 +27,7 @@
 #include <type_traits>
 
 #include "mmt_gemm_dev.h"
-
-
-// tuning knob (mmt_gemm_set_variant): pipeline variant of the forward / backward-data GEMMs in
-// bits 0-3 and of the weight-grad (split-K, atomic) GEMMs in bits 4-7:
-//   0 = BK 64 x 2 stages, 1 = BK 32 x 2, 2 = BK 32 x 3, 3 = BK 32 x 4, 4 = BK 64 x 3,
-//   5 = BK 32 x 3 and 6 = BK 32 x 2 at 3 blocks per CU (64-row epilogue passes)
-static int g_gemm_variant = -1;     // forward / backward-data (-1: per-epilogue policy, launch_t)
-
-static int g_gemm_big_variant_rt = 0;  // bits 8-11 of mmt_gemm_set_variant: 256x256 pipeline (0: env / default)
-static int g_force_big_rt = 0;         // bit 16: the 256x256 tile whatever K (M, N >= 256), for tests / benches
-static int g_gemm8_rt = -1;            // bit 17 / 18: ping-pong 256x256 kernel (gemm8_kernel) on / off (-1: env / default)
-static int g_gemm_variant_dw = 0;   // weight grad (split-K atomic)
-extern "C" int mmt_gemm_set_variant(int v) {
-  if (v < 0) {  // back to the default policy
-    g_gemm_variant = -1; g_gemm_variant_dw = 0; g_gemm_big_variant_rt = 0; g_force_big_rt = 0; g_gemm8_rt = -1;
-    return 0;
-  }
-  if ((v & 15) > 6 || ((v >> 4) & 15) > 6 || ((v >> 8) & 15) > 3) return -1;
-  g_gemm_variant = v & 15;
-  g_gemm_variant_dw = (v >> 4) & 15;
-  g_gemm_big_variant_rt = (v >> 8) & 15;
-  g_force_big_rt = (v >> 16) & 1;
-  g_gemm8_rt = ((v >> 17) & 1) ? 1 : ((v >> 18) & 1) ? 0 : -1;
-  return 0;
-}
+#include "mmt_gemm_plan.h"
 
 
 // Diagnostic timestamps (-DMMT_GEMM_STAMPS builds only; tools/gemm_stamps.py): thread 0 of each block
@@ -538,65 +514,79 @@ __global__ __launch_bounds__(TL::NT) void gemm_f8_kernel(GemmBatch batch) {
 }
 
 
-template <class TL, int BK, int ST, bool A_KC, bool B_KC, bool SWAP, int EPI, int MINB = 1>
-static void launch_v(const GemmBatch& b, dim3 grid, hipStream_t s) {
-#ifdef MMT_GEMM_STAMPS
-  GemmBatch bs = b;
-  bs.stamps = g_stamps;
-  hipLaunchKernelGGL((gemm_kernel<TL, BK, ST, A_KC, B_KC, SWAP, EPI, MINB>), grid, dim3(TL::NT), 0, s, bs);
-#else
-  hipLaunchKernelGGL((gemm_kernel<TL, BK, ST, A_KC, B_KC, SWAP, EPI, MINB>), grid, dim3(TL::NT), 0, s, b);
-#endif
-}
+// =============================================================================================
+// Host half. One plan per launch (mmt_gemm_plan, mmt_gemm_plan.h) decides the kernel, its template
+// arguments and the grid from the batch and the knobs below; the launchers launch what it says.
+// =============================================================================================
 
-template <class TL>
-static int max_tiles(const GemmBatch& b, int* total) {
-  int maxtiles = 0, sum = 0;
-  for (int g = 0; g < b.count; ++g) {
-    const GemmProblem& P = b.p[g];
-    const int t = ((P.M + TL::BM - 1) / TL::BM) * ((P.N + TL::BN - 1) / TL::BN);
-    maxtiles = t > maxtiles ? t : maxtiles;
-    sum += t;
+// Every MMT_* environment variable of the GEMM launch policy and what its two setters write (DESIGN.md §3
+// "GEMM knobs" has the same table), read once when the library loads. The measurement behind each default is
+// beside the rule that uses it, in mmt_gemm_plan.
+struct GemmKnobs {
+  // mmt_gemm_set_variant (no variable): 128 x 128 pipeline of the forward / backward-data launches in bits 0-3
+  // (-1: the per-epilogue policy) and of the atomic weight gradients in bits 4-7, 256 x 256 ring pipeline in bits
+  // 8-11 (0: MMT_GEMM_BIG_VARIANT / default), bit 16 the 256 x 256 tile whatever K, bit 17 / 18 the ping-pong
+  // kernel on everywhere it is built / off (-1: MMT_GEMM8 and its companions)
+  int variant = -1, variant_dw = 0, big_variant_rt = 0, force_big = 0, gemm8_rt = -1;
+  // MMT_GEMM_T2 / mmt_gemm_set_t2: 1 = every big launch with K below MMT_GEMM_BIG_KMIN on the 128 x 256 tile
+  int t2 = mmt_env_int("MMT_GEMM_T2", 0);
+  // MMT_GEMM_BIG=0: no 256 x 256 tile outside the row-wide launches
+  int big = mmt_env_int("MMT_GEMM_BIG", 1);
+  // MMT_GEMM_BIG_KMIN: K from which a launch whose problems all have M, N >= 256 takes the 256 x 256 tile
+  int big_kmin = mmt_env_int("MMT_GEMM_BIG_KMIN", 1024);
+  // MMT_GEMM_BIG_VARIANT: 256 x 256 ring pipeline of every launch (-1: BK 32 x 4 for the weight gradients, else 64 x 2)
+  int big_variant = mmt_env_int("MMT_GEMM_BIG_VARIANT", -1);
+  // MMT_GEMM8=0: the 256 x 256 ring instead of the ping-pong kernel everywhere
+  int gemm8 = mmt_env_int("MMT_GEMM8", 1);
+  // MMT_GEMM8_LN=0: only the row-wide (N = 256) LayerNorm-fused launches stay on the ring
+  int gemm8_ln = mmt_env_int("MMT_GEMM8_LN", 1) != 0;
+  // MMT_GEMM8_DW=1: the weight gradients on the ping-pong kernel too
+  int gemm8_dw = mmt_env_int("MMT_GEMM8_DW", 0) != 0;
+  // MMT_GEMM8_KMIN, MMT_GEMM8_MIN_TILES: a launch with K below MMT_GEMM_BIG_KMIN still goes big (on the ping-pong
+  // kernel) from this K and this many 256 x 256 tiles on
+  int gemm8_kmin = mmt_env_int("MMT_GEMM8_KMIN", 512);
+  int gemm8_min_tiles = mmt_env_int("MMT_GEMM8_MIN_TILES", 1024);
+  // MMT_GEMM_DW_VARIANT: 128 x 128 pipeline of the non-atomic launches with both operands MN-contiguous (-1: as the rest)
+  int dw_variant = mmt_env_int("MMT_GEMM_DW_VARIANT", -1);
+  // MMT_DW_SMALL=1: every weight gradient on the 128 x 128 tile (4x the tiles of the 256 x 256 one, so a quarter
+  // of the K splits and of the split-K slab traffic at the ~128-block side-stream target)
+  int dw_small = mmt_env_int("MMT_DW_SMALL", 0);
+  // MMT_WGRAD_BLOCKS: blocks per weight-gradient launch the automatic split-K factor aims at (0: GemmBatch::dw_blocks / 128)
+  int wgrad_blocks = mmt_env_int("MMT_WGRAD_BLOCKS", 0);
+  // MMT_DW_XCD_PLANE=0: no XCD-major remap of the weight gradients' (tile, split, problem) grid
+  int dw_xcd_plane = mmt_env_int("MMT_DW_XCD_PLANE", 1);
+};
+static GemmKnobs g_kn;
+
+extern "C" int mmt_gemm_set_variant(int v) {
+  if (v < 0) {  // back to the default policy
+    g_kn.variant = -1; g_kn.variant_dw = 0; g_kn.big_variant_rt = 0; g_kn.force_big = 0; g_kn.gemm8_rt = -1;
+    return 0;
   }
-  if (total) *total = sum;
-  return maxtiles;
+  if ((v & 15) > 6 || ((v >> 4) & 15) > 6 || ((v >> 8) & 15) > 3) return -1;
+  g_kn.variant = v & 15;
+  g_kn.variant_dw = (v >> 4) & 15;
+  g_kn.big_variant_rt = (v >> 8) & 15;
+  g_kn.force_big = (v >> 16) & 1;
+  g_kn.gemm8_rt = ((v >> 17) & 1) ? 1 : ((v >> 18) & 1) ? 0 : -1;
+  return 0;
+}
+extern "C" int mmt_gemm_set_t2(int v) {
+  const int old = g_kn.t2;
+  g_kn.t2 = v;
+  return old;
 }
 
-// split-K factor of a weight-gradient launch (splits <= 0: automatic). Every split adds one fp32
-// atomic per output element and an epilogue, so aim at ~2 blocks per CU for the 128x128 tile and
-// ~1 for the 256x256 one, keeping >= 8 K-steps per split. Measured at C1 (128x128, grouped
-// launches): 8 tiles 44.5 -> 29.2 us going from 8 to 32 splits, 24 tiles 50.7 -> 64.9 us from 8 to 22.
-template <class TL>
-static int auto_splits(const GemmBatch& b, int splits) {
-  if (splits > 0) return splits;
-  int tiles = 0, maxk = 0;
-  max_tiles<TL>(b, &tiles);
-  for (int g = 0; g < b.count; ++g) maxk = b.p[g].K > maxk ? b.p[g].K : maxk;
-  if (tiles <= 0) return 1;
-  static const int env_target = mmt_env_int("MMT_WGRAD_BLOCKS", 0);  // tuning knob: blocks per weight-gradient launch
-  // ~128 blocks: the weight gradients run on the side stream next to the data-gradient chain, so
-  // half the chip for longer beats the whole chip with twice the split-K slab traffic (measured at
-  // C1: 128 -> 9.97-10.28 ms/step, 256 -> 10.21-10.50, 64 -> 10.6)
-  const int target = env_target > 0 ? env_target : b.dw_blocks > 0 ? b.dw_blocks : 128;
-  const int cap = 32;
-  const int s = target / tiles;
-  const int maxs = std::max(1, std::min(cap, maxk / 512));
-  return std::max(1, std::min(s, maxs));
-}
-
-// 256x256 pipeline (MMT_GEMM_BIG_VARIANT): 0 = BK 64 x 2 stages, 1 = BK 32 x 4 (three K-steps in
-// flight), 2 = BK 32 x 3. Round 4 also built a software-pipelined K-step (the next sub-step's fragments
-// read while this one's MFMAs issue, the prefetch pieces spread between MFMAs) and a persistent
-// 256 x 256 kernel that prefetches the next tile's first stage under the last K-step and the epilogue.
-// Both won standalone (tools/gemm_bench.py: 4096^3 1136 -> 1180 TF/s, C4 ffn0 889 -> 915) and lost in
-// the training step beside the side stream (C1 8.78 -> 8.88 ms/step, target 20.47 -> 20.98), so they
-// were removed at the end of round 4.
-// Default: BK 32 x 4 for the weight gradients (both operands MN-contiguous, K = B*T: 128+ K-steps, the
-// deeper ring keeps three in flight; C1 *_dw family 3.44 -> 3.20 ms/step live, C3 73.8 -> 69.4),
-// BK 64 x 2 for the rest (the forward / data-gradient 256 x 256 launches measured 0.3-0.9 % slower
-// at BK 32 x 4 in C3 / C4: profiles/r4z_big_variant_ab.txt). MMT_GEMM_BIG_VARIANT sets all of them.
-static int g_big_variant = mmt_env_int("MMT_GEMM_BIG_VARIANT", -1);
-
+// 128 x 256, 4 waves (TileL's per-wave 128 x 64) at two workgroups per CU (BK 32 x 3 stages: 72 KiB each), so one
+// workgroup's prologue / epilogue overlaps the other's K loop
+using TileM = TileCfg<1, 4, 4, 2>;
+// ring depth of the 128 x 512 row-wide GEMMs (LayerNorm backward / forward fused): 3 stages of BK 32
+// (120 KiB, one block per CU) against 2 (80 KiB, two blocks per CU): target step 20.39 -> 19.64 ms
+// with the LayerNorm-backward GEMMs on it, 4 stages equal to 3 (profiles/r4k_ab.txt); at 2 stages the
+// next K-step's DMA had one 32-deep step of MFMAs to hide under
+#ifndef MMT_GEMM_W_ST
+#define MMT_GEMM_W_ST 3
+#endif
 // default 128 x 128 pipelines (build-time, tools/build_variant.py A/B): bf16-output epilogues at 3
 // blocks per CU (variant 6: BK 32 x 2), the others at 2 (variant 0: BK 64 x 2). Deeper rings lose
 // in the step (round 4, profiles/r4m_ab.txt: variant 5 for the former C1 +0.6 %, variants 2 / 4 for
@@ -607,149 +597,91 @@ static int g_big_variant = mmt_env_int("MMT_GEMM_BIG_VARIANT", -1);
 #ifndef MMT_DEF_VARIANT
 #define MMT_DEF_VARIANT 0
 #endif
-hipError_t mmt_launch_gemm8(const GemmBatch& b, int epi, bool a_kc, bool b_kc, dim3 grid, hipStream_t s);  // mmt_gemm8.hip
-// the (operand layouts, epilogue) pairs mmt_gemm8.hip instantiates
-constexpr bool gemm8_supports(bool akc, bool bkc, int epi) {
-  return (akc && bkc && (epi == EPI_STORE_BF16 || epi == EPI_BIAS_TANH_BF16 || epi == EPI_BIAS_RELU_BF16 ||
-                         epi == EPI_BIAS_RESID_F32 || epi == EPI_STORE_F32 || epi == EPI_ACC_F32)) ||
-         (akc && !bkc && (epi == EPI_STORE_BF16 || epi == EPI_DTANH_BF16 || epi == EPI_DRELU_BF16 ||
-                          epi == EPI_STORE_F32 || epi == EPI_ACC_F32 || epi == EPI_LN_BWD_F32)) ||
-         (!akc && !bkc && (epi == EPI_STORE_F32 || epi == EPI_ACC_F32));
+
+// log2 of the tiles' rows and columns, by GemmTile (this runs before every launch: shifts, no divisions)
+static constexpr int kTileShM[] = {7, 7, 8, 7}, kTileShN[] = {7, 8, 8, 9};
+static_assert(TileS::BM == 1 << 7 && TileM::BM == 1 << 7 && TileL::BM == 1 << 8 && TileW::BM == 1 << 7, "kTileShM");
+static_assert(TileS::BN == 1 << 7 && TileM::BN == 1 << 8 && TileL::BN == 1 << 8 && TileW::BN == 1 << 9, "kTileShN");
+
+static int max_tiles(const GemmBatch& b, int tile, int* total) {
+  const int shm = kTileShM[tile], shn = kTileShN[tile];
+  int maxtiles = 0, sum = 0;
+  for (int g = 0; g < b.count; ++g) {
+    const GemmProblem& P = b.p[g];
+    const int t = ((P.M + (1 << shm) - 1) >> shm) * ((P.N + (1 << shn) - 1) >> shn);
+    maxtiles = t > maxtiles ? t : maxtiles;
+    sum += t;
+  }
+  if (total) *total = sum;
+  return maxtiles;
+}
+static int max_k(const GemmBatch& b) {
+  int maxk = 0;
+  for (int g = 0; g < b.count; ++g) maxk = std::max(maxk, b.p[g].K);
+  return maxk;
 }
 
-static bool gemm8_ln_on();
+// split-K factor of a weight-gradient launch (splits <= 0: automatic). Every split adds one fp32
+// atomic per output element and an epilogue, so aim at ~2 blocks per CU for the 128x128 tile and
+// ~1 for the 256x256 one, keeping >= 8 K-steps per split. Measured at C1 (128x128, grouped
+// launches): 8 tiles 44.5 -> 29.2 us going from 8 to 32 splits, 24 tiles 50.7 -> 64.9 us from 8 to 22.
+static int auto_splits(const GemmBatch& b, int tile, int splits) {
+  if (splits > 0) return splits;
+  int tiles = 0;
+  max_tiles(b, tile, &tiles);
+  if (tiles <= 0) return 1;
+  // ~128 blocks: the weight gradients run on the side stream next to the data-gradient chain, so
+  // half the chip for longer beats the whole chip with twice the split-K slab traffic (measured at
+  // C1: 128 -> 9.97-10.28 ms/step, 256 -> 10.21-10.50, 64 -> 10.6)
+  const int target = g_kn.wgrad_blocks > 0 ? g_kn.wgrad_blocks : b.dw_blocks > 0 ? b.dw_blocks : 128;
+  const int maxs = std::max(1, std::min(32, max_k(b) / 512));
+  return std::max(1, std::min(target / tiles, maxs));
+}
 
+static bool has_qkv2(const GemmBatch& b) {
+  for (int g = 0; g < b.count; ++g)
+    if (b.p[g].qkv2_out || b.p[g].qkv2_h1_only) return true;
+  return false;
+}
+
+// variant bit 17 / 18 force the ping-pong kernel on / off (the kernel tests)
 static bool gemm8_on() {
   // default on (round 5): C4 355 -> 350 ms/step, C3 153.3 -> 152.4, target / C1 neutral (same-box A/B,
   // profiles/r5_gemm8_mlp2_ab.txt); MMT_GEMM8=0 restores the 2-stage 256 x 256 ring everywhere
-  static const int env = mmt_env_int("MMT_GEMM8", 1);
-  return g_gemm8_rt >= 0 ? g_gemm8_rt != 0 : env != 0;
-}
-
-// the row-wide (N = 256) LayerNorm-fused launches on the ping-pong kernel: MMT_GEMM8_LN=0 keeps them on the
-// 2-stage ring (variant bit 17 / 18 still force the ping-pong kernel on / off for the tests)
-static bool gemm8_ln_on() {
-  static const bool env = mmt_env_int("MMT_GEMM8_LN", 1) != 0;
-  if (g_gemm8_rt >= 0) return g_gemm8_rt == 1;
-  return gemm8_on() && env;
-}
-
-// K threshold 1024 (round 2 c): at K = 512 (d512 forward GEMMs and data gradients) the 128x128 tile at
-// 2-3 blocks per CU overlaps one block's epilogue with the others' K loops and shares the chip with
-// the side stream better than the single 256x256 block per CU (target step 23.13 -> 22.73 ms)
-static int g_big_kmin = mmt_env_int("MMT_GEMM_BIG_KMIN", 1024);
-// MMT_GEMM_T2=1: the big launches with K below the 256 x 256 tile's threshold (K = 512: the d512 FFN and
-// cross-attention K/V products the ping-pong kernel takes by default) on a 128 x 256 tile of 4 waves (TileL's
-// per-wave 128 x 64) at two workgroups per CU (BK 32 x 3 stages: 72 KiB each), so one workgroup's prologue /
-// epilogue overlaps the other's K loop
-using TileM = TileCfg<1, 4, 4, 2>;
-static int g_gemm_t2 = mmt_env_int("MMT_GEMM_T2", 0);
-extern "C" int mmt_gemm_set_t2(int v) {
-  const int old = g_gemm_t2;
-  g_gemm_t2 = v;
-  return old;
-}
-
-template <bool A_KC, bool B_KC, bool SWAP, int EPI>
-static hipError_t launch_t(const GemmBatch& b, int splits, bool big, hipStream_t s) {
-  if (b.count == 0) return hipSuccess;
-  if constexpr (SWAP && EPI != EPI_ATOMIC_F32) {
-    if (big && (g_gemm_t2 || b.tile_hint == 1)) {
-      int maxk = 0;
-      for (int g = 0; g < b.count; ++g) maxk = std::max(maxk, b.p[g].K);
-      if (maxk < g_big_kmin) {
-        const int mt = max_tiles<TileM>(b, nullptr);
-        if (mt == 0) return hipSuccess;
-        launch_v<TileM, 32, 3, A_KC, B_KC, SWAP, EPI, 2>(b, dim3(mt, std::max(1, splits), b.count), s);
-        return hipGetLastError();
-      }
-    }
-  }
-  if (big) {
-    const int mt = max_tiles<TileL>(b, nullptr);
-    if (mt == 0) return hipSuccess;
-    dim3 grid(mt, EPI == EPI_ATOMIC_F32 ? auto_splits<TileL>(b, splits) : std::max(1, splits), b.count);
-    // forward / backward-data products on the ping-pong kernel; the weight gradients (both operands
-    // MN-contiguous) only with MMT_GEMM8_DW=1: standalone 2-4 % faster, but on the side stream beside the
-    // main stream's attention backward the step measured slower (C1 attention backward 198 -> 207 us live,
-    // the *_dw family 107 -> 113 us; profiles/r5_gemm8_mlp2_ab.txt)
-    if constexpr (SWAP && gemm8_supports(A_KC, B_KC, EPI)) {
-      static const bool dw8 = mmt_env_int("MMT_GEMM8_DW", 0) != 0;
-      // (mmt_gemm_set_variant bit 17 forces it everywhere: the kernel tests)
-      if (gemm8_on() && (A_KC || dw8 || g_gemm8_rt == 1)) return mmt_launch_gemm8(b, EPI, A_KC, B_KC, grid, s);
-    }
-    const int bv = g_gemm_big_variant_rt ? g_gemm_big_variant_rt
-                   : g_big_variant >= 0  ? g_big_variant
-                   : (!A_KC && !B_KC)    ? 1
-                                         : 0;
-    switch (bv) {
-      case 1: launch_v<TileL, 32, 4, A_KC, B_KC, SWAP, EPI>(b, grid, s); break;
-      case 2: launch_v<TileL, 32, 3, A_KC, B_KC, SWAP, EPI>(b, grid, s); break;
-      // BK 32 x 2 (66.5 KiB with the epilogue tile): leaves room on its CU for an 80 KiB attention-backward
-      // workgroup beside it (measured for the weight gradients)
-      case 3: launch_v<TileL, 32, 2, A_KC, B_KC, SWAP, EPI>(b, grid, s); break;
-      default: launch_v<TileL, 64, 2, A_KC, B_KC, SWAP, EPI>(b, grid, s); break;
-    }
-    return hipGetLastError();
-  }
-  const int mt = max_tiles<TileS>(b, nullptr);
-  if (mt == 0) return hipSuccess;
-  dim3 grid(mt, EPI == EPI_ATOMIC_F32 ? auto_splits<TileS>(b, splits) : std::max(1, splits), b.count);
-  // default policy (variant knob unset): bf16-output epilogues with no aux operand stage 64 rows
-  // per epilogue pass and run 3+ blocks per CU (variant 6: 33 KB of LDS instead of 66 KB), which
-  // overlaps one block's short K loop with the others' prologue / stores; epilogues that read an aux
-  // or residual operand or store fp32 measured faster at 2 blocks per CU with the 64-deep ring
-  // (profiles/r2_gemm_bench.txt)
-  constexpr bool occ3 = EPI == EPI_STORE_BF16 || EPI == EPI_BIAS_TANH_BF16 || EPI == EPI_BIAS_RELU_BF16;
-  // tuning knob: pipeline variant of the 128x128 weight-gradient GEMMs
-  static const int env_dw = mmt_env_int("MMT_GEMM_DW_VARIANT", -1);
-  // (a 256 x 128 tile at two blocks per CU won standalone on the target ffn0, 214 -> 194 us, but not in
-  // the step beside the side stream, 20.21 -> 20.37 ms: profiles/r3y_tilem_ab.txt; removed in round 4)
-  // (the ReLU' epilogue reading bits has no 16-B aux operand left, but at 3 blocks per CU it measured
-  // neutral: C1 8.558 vs 8.555, target 19.937 vs 19.935 ms, profiles/r5ac_drelu_occ3_ab.txt)
-  const int var = EPI == EPI_ATOMIC_F32 ? g_gemm_variant_dw
-                  : (!A_KC && !B_KC && env_dw >= 0) ? env_dw
-                  : (g_gemm_variant >= 0 ? g_gemm_variant : occ3 ? MMT_OCC3_VARIANT : MMT_DEF_VARIANT);
-  switch (var) {
-    case 1: launch_v<TileS, 32, 2, A_KC, B_KC, SWAP, EPI>(b, grid, s); break;
-    case 2: launch_v<TileS, 32, 3, A_KC, B_KC, SWAP, EPI>(b, grid, s); break;
-    case 3: launch_v<TileS, 32, 4, A_KC, B_KC, SWAP, EPI>(b, grid, s); break;
-    case 4: launch_v<TileS, 64, 3, A_KC, B_KC, SWAP, EPI>(b, grid, s); break;
-    case 5: launch_v<TileS, 32, 3, A_KC, B_KC, SWAP, EPI, 3>(b, grid, s); break;
-    case 6: launch_v<TileS, 32, 2, A_KC, B_KC, SWAP, EPI, 3>(b, grid, s); break;
-    default: launch_v<TileS, 64, 2, A_KC, B_KC, SWAP, EPI>(b, grid, s); break;
-  }
-  return hipGetLastError();
+  return g_kn.gemm8_rt >= 0 ? g_kn.gemm8_rt != 0 : g_kn.gemm8 != 0;
 }
 
 // tile policy: the 256x256 tile where every problem of the launch fills it (M, N >= 256) and the
-// K loop is long enough to amortise its prologue/epilogue (K >= g_big_kmin; weight gradients
-// always qualify: K = B*T). MMT_GEMM_BIG=0 disables it, MMT_GEMM_BIG_KMIN sets the K threshold.
-static int g_big_mode = mmt_env_int("MMT_GEMM_BIG", 1);
-
-// K threshold of the ping-pong 256 x 256 kernel for launches with many tiles: at K = 512 it wins where
+// K loop is long enough to amortise its prologue/epilogue (K >= MMT_GEMM_BIG_KMIN; weight gradients
+// always qualify: K = B*T). MMT_GEMM_BIG=0 disables it.
+// K threshold 1024 (round 2 c): at K = 512 (d512 forward GEMMs and data gradients) the 128x128 tile at
+// 2-3 blocks per CU overlaps one block's epilogue with the others' K loops and shares the chip with
+// the side stream better than the single 256x256 block per CU (target step 23.13 -> 22.73 ms)
+// Shorter K on the ping-pong kernel for launches with many tiles: at K = 512 it wins where
 // the launch has >= 4 tiles per CU (the target's ffn0 and ffn2 dX: 221 -> 177 and 252 -> 230 us
 // standalone; smaller launches leave CUs idle or lose the 128 x 128 tile's 2-3 blocks per CU beside the
 // side stream: every K = 512 launch on it measured +1 % on the target step)
-static int g_gemm8_kmin = mmt_env_int("MMT_GEMM8_KMIN", 512);
-static int g_gemm8_min_tiles = mmt_env_int("MMT_GEMM8_MIN_TILES", 1024);
 static bool use_big(const GemmBatch& b) {
-  if (!g_big_mode || b.count == 0) return false;
-  bool big = true, qkv2 = false;
+  if (!g_kn.big || b.count == 0) return false;
+  bool big = true;
   int tiles = 0;
   for (int g = 0; g < b.count; ++g) {
     const GemmProblem& P = b.p[g];
     if (P.M < TileL::BM || P.N < TileL::BN) return false;
-    if (P.K < g_big_kmin && !g_force_big_rt) big = false;
-    qkv2 = qkv2 || P.qkv2_out != nullptr || P.qkv2_h1_only;
+    if (P.K < g_kn.big_kmin && !g_kn.force_big) big = false;
     tiles += ((P.M + 255) / 256) * ((P.N + 255) / 256);
   }
   if (big) return true;
   // shorter K on the ping-pong kernel: only big launches, and never the fused Q/K/V stage 2 (128 x 128 only)
-  if (!gemm8_on() || qkv2 || tiles < g_gemm8_min_tiles) return false;
+  if (!gemm8_on() || has_qkv2(b) || tiles < g_kn.gemm8_min_tiles) return false;
   for (int g = 0; g < b.count; ++g)
-    if (b.p[g].K < g_gemm8_kmin) return false;
+    if (b.p[g].K < g_kn.gemm8_kmin) return false;
   return true;
+}
+
+// 16-byte LDS-DMA pieces need 8-element-aligned leading dimensions (mask 7; fp8 bytes: 15) and 16-byte aligned bases
+static bool operands_ok(const GemmProblem& P, int ldmask) {
+  return !((P.lda | P.ldb) & ldmask) && !(((uintptr_t)P.A | (uintptr_t)P.B) & 15);
 }
 
 // the fused per-head Q/K/V stage 2 (qkv2_fused): forward tanh epilogue only, hh 16 or 32, 16-B stores,
@@ -774,6 +706,243 @@ static bool gemm_span_ok(const GemmBatch& b) {
   return true;
 }
 
+// the row-wide launches (a tile as wide as the row: its block owns whole rows of the LayerNorm): every problem
+// N == 256 or N == 512, all alike, 16-B aligned rows; ln_bwd: EPI_LN_BWD_F32's operands, else the forward's lnf_*
+static bool row_wide_ok(const GemmBatch& b, bool ln_bwd) {
+  if (b.count == 0) return false;
+  for (int g = 0; g < b.count; ++g) {
+    const GemmProblem& P = b.p[g];
+    if ((P.N != TileL::BN && P.N != TileW::BN) || P.N != b.p[0].N || !P.resid || !P.o32 || (P.ldc & 3) ||
+        (P.ldres & 3) || (P.o16 && (P.ldo16 & 7)) || !operands_ok(P, 7) || (((uintptr_t)P.o32 | (uintptr_t)P.resid) & 15))
+      return false;
+    if (ln_bwd) {  // (o16: the epilogue's 16-B dropout-masked copy stores)
+      if (!P.ln_gamma || !P.ln_mean || !P.ln_rstd || !P.ln_dgamma || !P.ln_dbeta ||
+          (((uintptr_t)P.ln_gamma | (uintptr_t)P.o16) & 15))
+        return false;
+    } else if (P.lnf_y && (!P.lnf_gamma || !P.lnf_beta || !P.lnf_mean || !P.lnf_rstd ||
+                           (((uintptr_t)P.lnf_y | (uintptr_t)P.lnf_gamma | (uintptr_t)P.lnf_beta) & 15))) {
+      return false;
+    }
+  }
+  return true;
+}
+bool mmt_gemm_resid_ln_ok(const GemmBatch& b) { return row_wide_ok(b, false); }
+bool mmt_gemm_ln_bwd_ok(const GemmBatch& b) { return row_wide_ok(b, true); }
+
+static bool f8_ok(const GemmProblem& P) {
+  if ((P.K & 31) || !operands_ok(P, 15) || (P.lds_a & 3) || (P.lds_b & 3) ||
+      (((uintptr_t)P.sa | (uintptr_t)P.sb) & 3) || P.lds_a * 32 < P.K || P.lds_b * 32 < P.K)
+    return false;
+  if (P.o8 && ((P.N & 31) || (P.ld8 & 7) || ((uintptr_t)P.o8 & 7))) return false;
+  return !P.qkv2_out && !P.qkv2_h1_only;  // (no fused Q/K/V stage 2 on the fp8 kernel)
+}
+
+// slab elements of one weight-gradient split over all problems (each problem's slab 16-B aligned)
+static int64_t slab_elems(const GemmBatch& b) {
+  int64_t per = 0;
+  for (int g = 0; g < b.count; ++g) per += ((int64_t)b.p[g].M * b.p[g].N + 3) / 4 * 4;
+  return per;
+}
+
+GemmPlan mmt_gemm_plan(const GemmBatch& b, int kind, bool a_kc, bool b_kc, int epi, int splits, int64_t slab_bytes) {
+  const GemmKnobs& kn = g_kn;
+  const bool linear = kind == GEMM_LINEAR, wgrad = kind == GEMM_WGRAD, f8 = kind == GEMM_F8;
+  const bool row_wide = kind == GEMM_RESID_LN || kind == GEMM_LN_BWD;
+  GemmPlan p{};
+  p.status = GEMM_PLAN_INVALID;
+  p.minb = 1;
+  p.swap = 1;
+  // the kernel's operand layouts and epilogue; (layouts, epilogue) outside the family's list: invalid
+  gemm_kind_ops(kind, a_kc, b_kc, epi);
+  p.a_kc = a_kc; p.b_kc = b_kc; p.epi = epi;
+  if (b.count == 0 && (wgrad || f8)) { p.status = GEMM_PLAN_EMPTY; return p; }
+  bool built = row_wide || wgrad;
+  if (linear) {
+    switch (gemm_op_key(a_kc, b_kc, epi)) {
+#define X(A, B, SW, E) case gemm_op_key(A, B, E): built = true; p.swap = SW; break;
+      GEMM_RING_OPS(X)
+#undef X
+    }
+  } else if (f8) {
+    switch (epi) {
+#define X(E) case E:
+      GEMM_F8_OPS(X) built = true;
+#undef X
+    }
+  }
+  if (!built) return p;
+  if (b.count == 0 && linear) { p.status = GEMM_PLAN_EMPTY; return p; }
+
+  // ---- tile -------------------------------------------------------------------------------------------
+  bool big;
+  if (f8) {
+    // the 256x256 tile where every problem fills it and K is long (as the bf16 policy), else 128x128 (tile_hint 1:
+    // the 128 x 128 tile, which fits beside other streams' waves where the 256 x 256 one needs a free CU)
+    big = kn.big != 0 && b.tile_hint != 1;
+    for (int g = 0; g < b.count; ++g)
+      if (b.p[g].M < TileL::BM || b.p[g].N < TileL::BN || b.p[g].K < kn.big_kmin) big = false;
+  } else {
+    // MMT_DW_SMALL / GemmBatch::tile_hint 2: this weight gradient on the 128 x 128 tile, 64 KiB of LDS, which fits on a
+    // CU beside the main stream's 80 KiB attention-backward workgroups where the 256 x 256 one's 128 KiB does not
+    big = use_big(b) && !(wgrad && (kn.dw_small || b.tile_hint == 2));
+  }
+  p.tile = big ? GEMM_TILE_256 : GEMM_TILE_128;
+  // row-wide, whatever K: 256 x 256 at C = 256, 128 x 512 at C = 512 (BK 64 measured neutral there, a
+  // 128 x 256 tile at C = 256 slower: 63.7 -> 92.9 us per launch, profiles/r3i_lnb_tile_ab.txt)
+  if (row_wide) p.tile = b.p[0].N == TileW::BN ? GEMM_TILE_128x512 : GEMM_TILE_256;
+  if (wgrad) {  // the split-K factor, capped by the slab's capacity; without a slab one K pass
+    splits = auto_splits(b, p.tile, 0);
+    const int64_t cap = slab_bytes > 0 ? slab_bytes / (int64_t)sizeof(float) / std::max<int64_t>(1, slab_elems(b)) : 1;
+    if (splits > cap) splits = (int)cap;
+    p.slabs = splits > 1;  // (one K pass accumulates straight into the gradient)
+    p.epi = epi = p.slabs ? EPI_STORE_F32 : EPI_ACC_F32;
+    p.xcd_plane = kn.dw_xcd_plane;
+    int64_t maxn4 = 0;
+    for (int g = 0; g < b.count; ++g) maxn4 = std::max<int64_t>(maxn4, ((int64_t)b.p[g].M * b.p[g].N + 3) / 4);
+    p.reduce_blocks = p.slabs ? (int)std::min<int64_t>(4096, (maxn4 + 255) / 256) : 0;
+  }
+  // MMT_GEMM_T2=1 / tile_hint 1: the big launches with K below the 256 x 256 tile's threshold (K = 512: the d512
+  // FFN and cross-attention K/V products the ping-pong kernel takes by default) on the 128 x 256 tile (SWAP
+  // non-atomic epilogues only)
+  if ((linear || wgrad) && big && p.swap && epi != EPI_ATOMIC_F32 && (kn.t2 || b.tile_hint == 1) && max_k(b) < kn.big_kmin)
+    p.tile = GEMM_TILE_128x256;
+
+  // ---- validity -----------------------------------------------------------------------------------------
+  if (!gemm_span_ok(b)) return p;
+  if (row_wide && !row_wide_ok(b, kind == GEMM_LN_BWD)) return p;
+  for (int g = 0; g < b.count; ++g) {
+    const GemmProblem& P = b.p[g];
+    if (f8 ? !f8_ok(P) : !operands_ok(P, 7)) return p;
+    if (linear && !qkv2_ok(P, epi, a_kc && b_kc)) return p;
+  }
+  if (linear && big && has_qkv2(b)) return p;  // fused stage 2: 128 x 128 tile only
+
+  // ---- grid ---------------------------------------------------------------------------------------------
+  p.gx = max_tiles(b, p.tile, nullptr);
+  p.gz = b.count;
+  const bool split_k = wgrad || epi == EPI_ATOMIC_F32 || (!a_kc && !b_kc && epi == EPI_STORE_F32);
+  p.gy = epi == EPI_ATOMIC_F32 ? auto_splits(b, p.tile, splits) : split_k ? std::max(1, splits) : 1;
+  if (p.gx == 0) { p.status = GEMM_PLAN_EMPTY; return p; }
+  p.status = GEMM_PLAN_OK;
+
+  // ---- kernel family and pipeline -------------------------------------------------------------------------
+  p.family = GEMM_RING; p.bk = 64; p.stages = 2;
+  if (f8) {
+    p.family = GEMM_FP8; p.bk = 128;
+  } else if (p.tile == GEMM_TILE_128x512) {
+    p.bk = 32; p.stages = MMT_GEMM_W_ST;
+  } else if (p.tile == GEMM_TILE_128x256) {
+    p.bk = 32; p.stages = 3; p.minb = 2;
+  } else if (p.tile == GEMM_TILE_256) {
+    // forward / backward-data products on the ping-pong kernel; the weight gradients (both operands
+    // MN-contiguous) only with MMT_GEMM8_DW=1: standalone 2-4 % faster, but on the side stream beside the
+    // main stream's attention backward the step measured slower (C1 attention backward 198 -> 207 us live,
+    // the *_dw family 107 -> 113 us; profiles/r5_gemm8_mlp2_ab.txt). The row-wide tile takes it too (same
+    // epilogue, LayerNorm included) unless MMT_GEMM8_LN=0; variant bit 17 forces it everywhere.
+    const bool on8 = row_wide ? (kn.gemm8_rt >= 0 ? kn.gemm8_rt == 1 : gemm8_on() && kn.gemm8_ln)
+                              : gemm8_on() && (a_kc || kn.gemm8_dw || kn.gemm8_rt == 1);
+    if (on8 && p.swap && gemm8_supports(a_kc, b_kc, epi)) {
+      p.family = GEMM_PINGPONG;
+    } else if (!row_wide) {
+      // 256x256 ring pipeline: 0 = BK 64 x 2 stages, 1 = BK 32 x 4 (three K-steps in flight), 2 = BK 32 x 3,
+      // 3 = BK 32 x 2 (66.5 KiB with the epilogue tile: leaves room on its CU for an 80 KiB attention-backward
+      // workgroup beside it; measured for the weight gradients). Round 4 also built a
+      // software-pipelined K-step (the next sub-step's fragments read while this one's MFMAs issue, the prefetch
+      // pieces spread between MFMAs) and a persistent 256 x 256 kernel that prefetches the next tile's first stage
+      // under the last K-step and the epilogue. Both won standalone (tools/gemm_bench.py: 4096^3 1136 -> 1180
+      // TF/s, C4 ffn0 889 -> 915) and lost in the training step beside the side stream (C1 8.78 -> 8.88 ms/step,
+      // target 20.47 -> 20.98), so they were removed at the end of round 4.
+      // Default: BK 32 x 4 for the weight gradients (both operands MN-contiguous, K = B*T: 128+ K-steps, the
+      // deeper ring keeps three in flight; C1 *_dw family 3.44 -> 3.20 ms/step live, C3 73.8 -> 69.4),
+      // BK 64 x 2 for the rest (the forward / data-gradient 256 x 256 launches measured 0.3-0.9 % slower
+      // at BK 32 x 4 in C3 / C4: profiles/r4z_big_variant_ab.txt). MMT_GEMM_BIG_VARIANT sets all of them.
+      const int bv = kn.big_variant_rt ? kn.big_variant_rt : kn.big_variant >= 0 ? kn.big_variant : (!a_kc && !b_kc) ? 1 : 0;
+      if (bv >= 1 && bv <= 3) { p.bk = 32; p.stages = 5 - bv; }
+    }
+  } else {
+    // default policy (variant knob unset): bf16-output epilogues with no aux operand stage 64 rows
+    // per epilogue pass and run 3+ blocks per CU (variant 6: 33 KB of LDS instead of 66 KB), which
+    // overlaps one block's short K loop with the others' prologue / stores; epilogues that read an aux
+    // or residual operand or store fp32 measured faster at 2 blocks per CU with the 64-deep ring
+    // (profiles/r2_gemm_bench.txt)
+    // (a 256 x 128 tile at two blocks per CU won standalone on the target ffn0, 214 -> 194 us, but not in
+    // the step beside the side stream, 20.21 -> 20.37 ms: profiles/r3y_tilem_ab.txt; removed in round 4)
+    // (the ReLU' epilogue reading bits has no 16-B aux operand left, but at 3 blocks per CU it measured
+    // neutral: C1 8.558 vs 8.555, target 19.937 vs 19.935 ms, profiles/r5ac_drelu_occ3_ab.txt)
+    const bool occ3 = epi == EPI_STORE_BF16 || epi == EPI_BIAS_TANH_BF16 || epi == EPI_BIAS_RELU_BF16;
+    const int var = epi == EPI_ATOMIC_F32                      ? kn.variant_dw
+                    : (!a_kc && !b_kc && kn.dw_variant >= 0) ? kn.dw_variant
+                    : kn.variant >= 0                          ? kn.variant
+                    : occ3                                     ? MMT_OCC3_VARIANT
+                                                               : MMT_DEF_VARIANT;
+    // 0 = BK 64 x 2 stages, 1 = BK 32 x 2, 2 = BK 32 x 3, 3 = BK 32 x 4, 4 = BK 64 x 3,
+    // 5 = BK 32 x 3 and 6 = BK 32 x 2 at 3 blocks per CU (64-row epilogue passes)
+    static constexpr int kVar[7][3] = {{64, 2, 1}, {32, 2, 1}, {32, 3, 1}, {32, 4, 1}, {64, 3, 1}, {32, 3, 3}, {32, 2, 3}};
+    if (var >= 1 && var <= 6) { p.bk = kVar[var][0]; p.stages = kVar[var][1]; p.minb = kVar[var][2]; }
+  }
+  return p;
+}
+
+// ---- plan -> template instantiation, once per kernel family -------------------------------------------------
+template <class TL, int BK, int ST, bool A_KC, bool B_KC, bool SWAP, int EPI, int MINB = 1>
+static hipError_t launch_v(const GemmBatch& b, const GemmPlan& p, hipStream_t s) {
+  const dim3 grid(p.gx, p.gy, p.gz);
+#ifdef MMT_GEMM_STAMPS
+  GemmBatch bs = b;
+  bs.stamps = g_stamps;
+  hipLaunchKernelGGL((gemm_kernel<TL, BK, ST, A_KC, B_KC, SWAP, EPI, MINB>), grid, dim3(TL::NT), 0, s, bs);
+#else
+  hipLaunchKernelGGL((gemm_kernel<TL, BK, ST, A_KC, B_KC, SWAP, EPI, MINB>), grid, dim3(TL::NT), 0, s, b);
+#endif
+  return hipGetLastError();
+}
+
+constexpr int ring_key(int tile, int bk, int stages, int minb) { return (tile << 16) | (bk << 8) | (stages << 4) | minb; }
+// the ring: 128 x 128 in seven pipelines and 256 x 256 in four for every GEMM_RING_OPS entry, 128 x 256 for its SWAP
+// non-atomic ones, 128 x 512 for the two row-wide epilogues; LayerNorm backward only on the two row-wide tiles
+template <bool A_KC, bool B_KC, bool SWAP, int EPI>
+static hipError_t launch_ring(const GemmBatch& b, const GemmPlan& p, hipStream_t s) {
+  constexpr bool ln_bwd = EPI == EPI_LN_BWD_F32;
+  constexpr bool row_wide = ln_bwd || (A_KC && B_KC && EPI == EPI_BIAS_RESID_F32);
+  const int v = ring_key(p.tile, p.bk, p.stages, p.minb);
+#define V(TL, TILE, BK, ST, MINB) \
+  if (v == ring_key(TILE, BK, ST, MINB)) return launch_v<TL, BK, ST, A_KC, B_KC, SWAP, EPI, MINB>(b, p, s);
+  if constexpr (!ln_bwd) { V(TileS, GEMM_TILE_128, 32, 2, 3) V(TileS, GEMM_TILE_128, 64, 2, 1) }  // (the defaults first)
+  V(TileL, GEMM_TILE_256, 64, 2, 1)
+  if constexpr (row_wide) V(TileW, GEMM_TILE_128x512, 32, MMT_GEMM_W_ST, 1)
+  if constexpr (!ln_bwd) {
+    V(TileL, GEMM_TILE_256, 32, 4, 1) V(TileL, GEMM_TILE_256, 32, 3, 1) V(TileL, GEMM_TILE_256, 32, 2, 1)
+    V(TileS, GEMM_TILE_128, 32, 2, 1) V(TileS, GEMM_TILE_128, 32, 3, 1) V(TileS, GEMM_TILE_128, 32, 4, 1)
+    V(TileS, GEMM_TILE_128, 64, 3, 1) V(TileS, GEMM_TILE_128, 32, 3, 3)
+    if constexpr (SWAP && EPI != EPI_ATOMIC_F32) V(TileM, GEMM_TILE_128x256, 32, 3, 2)
+  }
+#undef V
+  return hipErrorInvalidValue;
+}
+
+static hipError_t launch_plan(const GemmBatch& b, const GemmPlan& p, hipStream_t s) {
+  if (p.status != GEMM_PLAN_OK) return p.status == GEMM_PLAN_EMPTY ? hipSuccess : hipErrorInvalidValue;
+  if (p.family == GEMM_PINGPONG) return mmt_launch_gemm8(b, p, s);
+  if (p.family == GEMM_FP8) {
+    switch (p.epi) {
+#define X(E)                                                                                                      \
+  case E:                                                                                                         \
+    if (p.tile == GEMM_TILE_256) hipLaunchKernelGGL((gemm_f8_kernel<TileL, E>), dim3(p.gx, p.gy, p.gz), dim3(TileL::NT), 0, s, b); \
+    else hipLaunchKernelGGL((gemm_f8_kernel<TileS, E>), dim3(p.gx, p.gy, p.gz), dim3(TileS::NT), 0, s, b);         \
+    return hipGetLastError();
+      GEMM_F8_OPS(X)
+#undef X
+    }
+    return hipErrorInvalidValue;
+  }
+  switch (gemm_op_key(p.a_kc, p.b_kc, p.epi)) {
+#define X(A, B, SW, E) case gemm_op_key(A, B, E): return launch_ring<A, B, SW, E>(b, p, s);
+    GEMM_RING_OPS(X) GEMM_RING_LN_BWD_OP(X)
+#undef X
+  }
+  return hipErrorInvalidValue;
+}
+
 // Deterministic mode (GemmBatch::det, mmt_det.h): the epilogue's column sums (dbias; with `ln` also
 // ln_dgamma / ln_dbeta) are stored per row tile at [slot][ceil(M / 128)][N] of the problem's scratch and
 // one ordered sum behind the launch adds them into the gradients
@@ -792,6 +961,7 @@ int64_t mmt_gemm_det_floats(int count, int M, int N, bool ln) {
 }
 template <class F>
 static hipError_t gemm_det_run(const GemmBatch& b, bool ln, hipStream_t s, F run) {
+  if (!b.det.base) return run(b);
   bool any = false;
   for (int g = 0; g < b.count; ++g) any = any || b.p[g].dbias || (ln && (b.p[g].ln_dgamma || b.p[g].ln_dbeta));
   GemmBatch d = b;
@@ -818,57 +988,21 @@ static hipError_t gemm_det_run(const GemmBatch& b, bool ln, hipStream_t s, F run
   return L.finish();
 }
 
-static hipError_t launch_gemm_any(const GemmBatch& b, bool a_kc, bool b_kc, int epi, int splits, hipStream_t s);
 hipError_t mmt_launch_gemm(const GemmBatch& b, bool a_kc, bool b_kc, int epi, int splits, hipStream_t s) {
-  if (!b.det.base) return launch_gemm_any(b, a_kc, b_kc, epi, splits, s);
-  return gemm_det_run(b, false, s, [&](const GemmBatch& d) { return launch_gemm_any(d, a_kc, b_kc, epi, splits, s); });
+  return gemm_det_run(b, false, s, [&](const GemmBatch& d) {
+    return launch_plan(d, mmt_gemm_plan(d, GEMM_LINEAR, a_kc, b_kc, epi, splits, 0), s);
+  });
 }
-
-static hipError_t launch_gemm_any(const GemmBatch& b, bool a_kc, bool b_kc, int epi, int splits, hipStream_t s) {
-  if (!gemm_span_ok(b)) return hipErrorInvalidValue;
-  for (int g = 0; g < b.count; ++g) {
-    const GemmProblem& P = b.p[g];
-    // 16-byte LDS-DMA pieces need 8-element-aligned leading dimensions and 16-byte aligned bases
-    if ((P.lda & 7) || (P.ldb & 7) || (((uintptr_t)P.A | (uintptr_t)P.B) & 15)) return hipErrorInvalidValue;
-    if (!qkv2_ok(P, epi, a_kc && b_kc)) return hipErrorInvalidValue;
-  }
-  const bool big = use_big(b);
-  for (int g = 0; g < b.count; ++g)
-    if (big && (b.p[g].qkv2_out || b.p[g].qkv2_h1_only)) return hipErrorInvalidValue;  // fused stage 2: 128 x 128 tile only
-  if (a_kc && b_kc) {
-    switch (epi) {
-      case EPI_STORE_BF16: return launch_t<true, true, true, EPI_STORE_BF16>(b, 1, big, s);
-      case EPI_BIAS_TANH_BF16: return launch_t<true, true, true, EPI_BIAS_TANH_BF16>(b, 1, big, s);
-      case EPI_BIAS_RELU_BF16: return launch_t<true, true, true, EPI_BIAS_RELU_BF16>(b, 1, big, s);
-      case EPI_BIAS_RESID_F32: return launch_t<true, true, true, EPI_BIAS_RESID_F32>(b, 1, big, s);
-      case EPI_STORE_F32: return launch_t<true, true, true, EPI_STORE_F32>(b, 1, big, s);
-      case EPI_ACC_F32: return launch_t<true, true, true, EPI_ACC_F32>(b, 1, big, s);
-      default: break;
-    }
-  } else if (a_kc && !b_kc) {
-    switch (epi) {
-      case EPI_STORE_BF16: return launch_t<true, false, true, EPI_STORE_BF16>(b, 1, big, s);
-      case EPI_DTANH_BF16: return launch_t<true, false, true, EPI_DTANH_BF16>(b, 1, big, s);
-      case EPI_DRELU_BF16: return launch_t<true, false, true, EPI_DRELU_BF16>(b, 1, big, s);
-      case EPI_STORE_F32: return launch_t<true, false, true, EPI_STORE_F32>(b, 1, big, s);
-      case EPI_ACC_F32: return launch_t<true, false, true, EPI_ACC_F32>(b, 1, big, s);
-      default: break;
-    }
-  } else if (!a_kc && !b_kc) {
-    switch (epi) {
-      case EPI_ATOMIC_F32: return launch_t<false, false, false, EPI_ATOMIC_F32>(b, splits, big, s);
-      case EPI_STORE_F32: return launch_t<false, false, true, EPI_STORE_F32>(b, splits, big, s);
-      case EPI_ACC_F32: return launch_t<false, false, true, EPI_ACC_F32>(b, 1, big, s);
-      default: break;
-    }
-  } else {
-    switch (epi) {
-      case EPI_ATOMIC_F32: return launch_t<false, true, false, EPI_ATOMIC_F32>(b, splits, big, s);
-      case EPI_STORE_F32: return launch_t<false, true, true, EPI_STORE_F32>(b, 1, big, s);
-      default: break;
-    }
-  }
-  return hipErrorInvalidValue;
+hipError_t mmt_launch_gemm_ln_bwd(const GemmBatch& b, hipStream_t s) {
+  return gemm_det_run(b, true, s, [&](const GemmBatch& d) {
+    return launch_plan(d, mmt_gemm_plan(d, GEMM_LN_BWD), s);
+  });
+}
+hipError_t mmt_launch_gemm_resid_ln(const GemmBatch& b, hipStream_t s) {
+  return launch_plan(b, mmt_gemm_plan(b, GEMM_RESID_LN), s);
+}
+hipError_t mmt_launch_gemm_f8(const GemmBatch& b, int epi, hipStream_t s) {
+  return launch_plan(b, mmt_gemm_plan(b, GEMM_F8, true, true, epi, 1, 0), s);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -928,181 +1062,27 @@ __global__ __launch_bounds__(256) void slab_reduce_kernel(SlabBatch b) {
   }
 }
 
-// MMT_DW_SMALL=1: every weight gradient on the 128 x 128 tile (4x the tiles of the 256 x 256 one, so a
-// quarter of the K splits and of the split-K slab traffic at the ~128-block side-stream target)
-static const int g_dw_small = mmt_env_int("MMT_DW_SMALL", 0);
-// (GemmBatch::tile_hint 2: this launch on the 128 x 128 tile, 64 KiB of LDS, which fits on a CU beside the
-// main stream's 80 KiB attention-backward workgroups where the 256 x 256 one's 128 KiB does not)
-static bool use_big_dw(const GemmBatch& b) { return !g_dw_small && b.tile_hint != 2 && use_big(b); }
-
 hipError_t mmt_launch_gemm_wgrad(const GemmBatch& b, float* slab, int64_t slab_bytes, hipStream_t s) {
-  if (b.count == 0) return hipSuccess;
-  if (!gemm_span_ok(b)) return hipErrorInvalidValue;
-  for (int g = 0; g < b.count; ++g) {
-    const GemmProblem& P = b.p[g];
-    if ((P.lda & 7) || (P.ldb & 7) || (((uintptr_t)P.A | (uintptr_t)P.B) & 15)) return hipErrorInvalidValue;
-  }
-  const bool big = use_big_dw(b);
-  int splits = big ? auto_splits<TileL>(b, 0) : auto_splits<TileS>(b, 0);
-  int64_t per = 0;  // slab elements of one split over all problems (each slab 16-B aligned)
-  for (int g = 0; g < b.count; ++g) per += ((int64_t)b.p[g].M * b.p[g].N + 3) / 4 * 4;
-  if (slab) {
-    const int64_t cap = slab_bytes / (int64_t)sizeof(float) / std::max<int64_t>(1, per);
-    if (splits > cap) splits = (int)cap;
-  } else {
-    splits = 1;
-  }
-  // XCD-major remap of the (tile, split, problem) grid (MMT_DW_XCD_PLANE=0 turns it off)
-  static const int xcd_plane = mmt_env_int("MMT_DW_XCD_PLANE", 1);
-  if (splits <= 1) {  // one K pass: accumulate straight into the gradient
-    GemmBatch d = b;
-    d.xcd_plane = xcd_plane;
-    for (int g = 0; g < d.count; ++g) d.p[g].split_stride = 0;
-    return launch_t<false, false, true, EPI_ACC_F32>(d, 1, big, s);
-  }
+  const GemmPlan p = mmt_gemm_plan(b, GEMM_WGRAD, false, false, 0, 0, slab ? slab_bytes : 0);
   GemmBatch d = b;
-  d.xcd_plane = xcd_plane;
+  d.xcd_plane = p.xcd_plane;
   SlabBatch sb{};
   sb.count = b.count;
-  sb.splits = splits;
+  sb.splits = p.gy;
+  const int64_t per = p.slabs ? slab_elems(b) : 0;
   int64_t off = 0;
   for (int g = 0; g < d.count; ++g) {
     GemmProblem& P = d.p[g];
-    const int64_t mn = ((int64_t)P.M * P.N + 3) / 4 * 4;
+    P.split_stride = per;
+    if (!p.slabs) continue;  // one K pass: accumulate straight into the gradient
     sb.p[g] = SlabProblem{slab + off, P.o32, P.M, P.N, P.ldc, per};
     P.o32 = slab + off;
     P.ldc = P.N;
-    P.split_stride = per;
-    off += mn;
+    off += ((int64_t)P.M * P.N + 3) / 4 * 4;
   }
-  hipError_t e = launch_t<false, false, true, EPI_STORE_F32>(d, splits, big, s);
-  if (e != hipSuccess) return e;
-  int64_t maxn4 = 0;
-  for (int g = 0; g < b.count; ++g) maxn4 = std::max<int64_t>(maxn4, ((int64_t)b.p[g].M * b.p[g].N + 3) / 4);
-  const int blocks = (int)std::min<int64_t>(4096, (maxn4 + 255) / 256);
-  hipLaunchKernelGGL(slab_reduce_kernel, dim3(blocks, b.count), dim3(256), 0, s, sb);
+  const hipError_t e = launch_plan(d, p, s);
+  // (a batch without tiles has one split, so an EMPTY plan never has slabs to reduce)
+  if (e != hipSuccess || !p.slabs || p.status != GEMM_PLAN_OK) return e;
+  hipLaunchKernelGGL(slab_reduce_kernel, dim3(p.reduce_blocks, p.gz), dim3(256), 0, s, sb);
   return hipGetLastError();
 }
-
-
-
-bool mmt_gemm_wgrad_big(const GemmBatch& b) { return use_big_dw(b); }
-
-bool mmt_gemm_resid_ln_ok(const GemmBatch& b) {
-  if (b.count == 0) return false;
-  for (int g = 0; g < b.count; ++g) {
-    const GemmProblem& P = b.p[g];
-    if ((P.N != TileL::BN && P.N != TileW::BN) || P.N != b.p[0].N || !P.resid || !P.o32 || (P.ldc & 3) ||
-        (P.ldres & 3) || (P.o16 && (P.ldo16 & 7)) || (P.lda & 7) || (P.ldb & 7) ||
-        (((uintptr_t)P.A | (uintptr_t)P.B | (uintptr_t)P.o32 | (uintptr_t)P.resid) & 15))
-      return false;
-    if (P.lnf_y && (!P.lnf_gamma || !P.lnf_beta || !P.lnf_mean || !P.lnf_rstd ||
-                    (((uintptr_t)P.lnf_y | (uintptr_t)P.lnf_gamma | (uintptr_t)P.lnf_beta) & 15)))
-      return false;
-  }
-  return true;
-}
-
-// ring depth of the 128 x 512 row-wide GEMMs (LayerNorm backward / forward fused): 3 stages of BK 32
-// (120 KiB, one block per CU) against 2 (80 KiB, two blocks per CU): target step 20.39 -> 19.64 ms
-// with the LayerNorm-backward GEMMs on it, 4 stages equal to 3 (profiles/r4k_ab.txt); at 2 stages the
-// next K-step's DMA had one 32-deep step of MFMAs to hide under
-#ifndef MMT_GEMM_W_ST
-#define MMT_GEMM_W_ST 3
-#endif
-hipError_t mmt_launch_gemm_resid_ln(const GemmBatch& b, hipStream_t s) {
-  if (!mmt_gemm_resid_ln_ok(b) || !gemm_span_ok(b)) return hipErrorInvalidValue;
-  // a tile as wide as the row whatever K (its block owns whole rows): 256 x 256 (as launch_t's big
-  // path, variant 0) at C = 256, 128 x 512 at C = 512
-  if (b.p[0].N == TileW::BN) {
-    const int mt = max_tiles<TileW>(b, nullptr);
-    if (mt == 0) return hipSuccess;
-    launch_v<TileW, 32, MMT_GEMM_W_ST, true, true, true, EPI_BIAS_RESID_F32>(b, dim3(mt, 1, b.count), s);
-  } else {
-    const int mt = max_tiles<TileL>(b, nullptr);
-    if (mt == 0) return hipSuccess;
-    // the ping-pong kernel takes the 256 x 256 row-wide tile too (same epilogue, LayerNorm included)
-    if (gemm8_ln_on()) return mmt_launch_gemm8(b, EPI_BIAS_RESID_F32, true, true, dim3(mt, 1, b.count), s);
-    launch_v<TileL, 64, 2, true, true, true, EPI_BIAS_RESID_F32>(b, dim3(mt, 1, b.count), s);
-  }
-  return hipGetLastError();
-}
-
-bool mmt_gemm_ln_bwd_ok(const GemmBatch& b) {
-  if (b.count == 0) return false;
-  for (int g = 0; g < b.count; ++g) {
-    const GemmProblem& P = b.p[g];
-    if ((P.N != TileL::BN && P.N != TileW::BN) || P.N != b.p[0].N || !P.resid || !P.o32 || !P.ln_gamma || !P.ln_mean || !P.ln_rstd || !P.ln_dgamma ||
-        !P.ln_dbeta || (P.ldc & 3) || (P.ldres & 3) || (P.o16 && (P.ldo16 & 7)) || (P.lda & 7) || (P.ldb & 7) ||
-        (((uintptr_t)P.A | (uintptr_t)P.B | (uintptr_t)P.o32 | (uintptr_t)P.resid | (uintptr_t)P.ln_gamma |
-          (uintptr_t)P.o16) & 15))  // (o16: the epilogue's 16-B dropout-masked copy stores)
-      return false;
-  }
-  return true;
-}
-
-static hipError_t launch_gemm_ln_bwd_any(const GemmBatch& b, hipStream_t s);
-hipError_t mmt_launch_gemm_ln_bwd(const GemmBatch& b, hipStream_t s) {
-  if (!b.det.base) return launch_gemm_ln_bwd_any(b, s);
-  return gemm_det_run(b, true, s, [&](const GemmBatch& d) { return launch_gemm_ln_bwd_any(d, s); });
-}
-
-static hipError_t launch_gemm_ln_bwd_any(const GemmBatch& b, hipStream_t s) {
-  if (!mmt_gemm_ln_bwd_ok(b) || !gemm_span_ok(b)) return hipErrorInvalidValue;
-  // a tile as wide as the row, whatever K: its block owns whole rows of the LayerNorm (C = 256:
-  // 256 x 256; C = 512: 128 x 512 at BK 32 x 2 stages = 80 KiB of ring; BK 64 measured neutral, a
-  // 128 x 256 tile at C = 256 slower: 63.7 -> 92.9 us per launch, profiles/r3i_lnb_tile_ab.txt)
-  if (b.p[0].N == TileW::BN) {
-    const int mt = max_tiles<TileW>(b, nullptr);
-    if (mt == 0) return hipSuccess;
-    launch_v<TileW, 32, MMT_GEMM_W_ST, true, false, true, EPI_LN_BWD_F32>(b, dim3(mt, 1, b.count), s);
-  } else {
-    const int mt = max_tiles<TileL>(b, nullptr);
-    if (mt == 0) return hipSuccess;
-    if (gemm8_ln_on()) return mmt_launch_gemm8(b, EPI_LN_BWD_F32, true, false, dim3(mt, 1, b.count), s);
-    launch_v<TileL, 64, 2, true, false, true, EPI_LN_BWD_F32>(b, dim3(mt, 1, b.count), s);
-  }
-  return hipGetLastError();
-}
-
-template <class TL, int EPI>
-static hipError_t launch_f8(const GemmBatch& b, hipStream_t s) {
-  int mt = 0;
-  for (int g = 0; g < b.count; ++g)
-    mt = std::max(mt, ((b.p[g].M + TL::BM - 1) / TL::BM) * ((b.p[g].N + TL::BN - 1) / TL::BN));
-  if (mt == 0) return hipSuccess;
-  hipLaunchKernelGGL((gemm_f8_kernel<TL, EPI>), dim3(mt, 1, b.count), dim3(TL::NT), 0, s, b);
-  return hipGetLastError();
-}
-
-template <int EPI>
-static hipError_t launch_f8_tile(const GemmBatch& b, hipStream_t s) {
-  // the 256x256 tile where every problem fills it and K is long (as the bf16 policy), else 128x128
-  // (tile_hint 1: the 128 x 128 tile, which fits beside other streams' waves where the 256 x 256 one needs a free CU)
-  bool big = g_big_mode != 0 && b.tile_hint != 1;
-  for (int g = 0; g < b.count; ++g)
-    if (b.p[g].M < TileL::BM || b.p[g].N < TileL::BN || b.p[g].K < g_big_kmin) big = false;
-  return big ? launch_f8<TileL, EPI>(b, s) : launch_f8<TileS, EPI>(b, s);
-}
-
-hipError_t mmt_launch_gemm_f8(const GemmBatch& b, int epi, hipStream_t s) {
-  if (b.count == 0) return hipSuccess;
-  if (!gemm_span_ok(b)) return hipErrorInvalidValue;
-  for (int g = 0; g < b.count; ++g) {
-    const GemmProblem& P = b.p[g];
-    if ((P.K & 31) || (P.lda & 15) || (P.ldb & 15) || (((uintptr_t)P.A | (uintptr_t)P.B) & 15) || (P.lds_a & 3) ||
-        (P.lds_b & 3) || (((uintptr_t)P.sa | (uintptr_t)P.sb) & 3) || P.lds_a * 32 < P.K || P.lds_b * 32 < P.K)
-      return hipErrorInvalidValue;
-    if (P.o8 && ((P.N & 31) || (P.ld8 & 7) || ((uintptr_t)P.o8 & 7))) return hipErrorInvalidValue;
-    if (P.qkv2_out || P.qkv2_h1_only) return hipErrorInvalidValue;  // (no fused Q/K/V stage 2 on the fp8 kernel)
-  }
-  switch (epi) {
-    case EPI_STORE_BF16: return launch_f8_tile<EPI_STORE_BF16>(b, s);
-    case EPI_BIAS_TANH_BF16: return launch_f8_tile<EPI_BIAS_TANH_BF16>(b, s);
-    case EPI_BIAS_RELU_BF16: return launch_f8_tile<EPI_BIAS_RELU_BF16>(b, s);
-    case EPI_BIAS_RESID_F32: return launch_f8_tile<EPI_BIAS_RESID_F32>(b, s);
-    case EPI_STORE_F32: return launch_f8_tile<EPI_STORE_F32>(b, s);
-    default: return hipErrorInvalidValue;
-  }
-}
-

@@ -1,5 +1,6 @@
-// 256 x 256 ping-pong bf16 GEMM for gfx950 (round 5; launched by mmt_gemm.hip's launch_t).
+// 256 x 256 ping-pong bf16 GEMM for gfx950 (round 5; launched by mmt_gemm.hip's launch_plan).
 #include "mmt_gemm_dev.h"
+#include "mmt_gemm_plan.h"
 
 #include <type_traits>
 
@@ -222,44 +223,17 @@ __global__ __launch_bounds__(512, 1) void gemm8_kernel(GemmBatch batch) {
   epilogue_swap<TL, EPI, EPI_ROWS>(P, acc, lds, o32, alpha, m0, n0, tid, lane, wave, det_of(batch, prob));
 }
 
-template <int EPI, bool A_KC, bool B_KC>
-static hipError_t launch8(const GemmBatch& b, dim3 grid, hipStream_t s) {
-  hipLaunchKernelGGL((gemm8_kernel<EPI, A_KC, B_KC>), grid, dim3(512), 0, s, b);
-  return hipGetLastError();
-}
-
 // grid = (256 x 256 tiles of the largest problem, K slices, problems). The forward (a_kc, b_kc), backward-data
-// (a_kc, !b_kc: W stored [K][N]) and weight-gradient (!a_kc, !b_kc: slab or accumulate) products;
+// (a_kc, !b_kc: W stored [K][N]) and weight-gradient (!a_kc, !b_kc: slab or accumulate) products of GEMM8_OPS;
 // hipErrorInvalidValue for an epilogue the kernel does not instantiate.
-hipError_t mmt_launch_gemm8(const GemmBatch& b, int epi, bool a_kc, bool b_kc, dim3 grid, hipStream_t s) {
-  if (a_kc && b_kc) {
-    switch (epi) {
-      case EPI_STORE_BF16: return launch8<EPI_STORE_BF16, true, true>(b, grid, s);
-      case EPI_BIAS_TANH_BF16: return launch8<EPI_BIAS_TANH_BF16, true, true>(b, grid, s);
-      case EPI_BIAS_RELU_BF16: return launch8<EPI_BIAS_RELU_BF16, true, true>(b, grid, s);
-      case EPI_BIAS_RESID_F32: return launch8<EPI_BIAS_RESID_F32, true, true>(b, grid, s);
-      case EPI_STORE_F32: return launch8<EPI_STORE_F32, true, true>(b, grid, s);
-      case EPI_ACC_F32: return launch8<EPI_ACC_F32, true, true>(b, grid, s);
-      default: return hipErrorInvalidValue;
-    }
-  }
-  if (a_kc) {
-    switch (epi) {
-      case EPI_LN_BWD_F32: return launch8<EPI_LN_BWD_F32, true, false>(b, grid, s);
-      case EPI_STORE_BF16: return launch8<EPI_STORE_BF16, true, false>(b, grid, s);
-      case EPI_DTANH_BF16: return launch8<EPI_DTANH_BF16, true, false>(b, grid, s);
-      case EPI_DRELU_BF16: return launch8<EPI_DRELU_BF16, true, false>(b, grid, s);
-      case EPI_STORE_F32: return launch8<EPI_STORE_F32, true, false>(b, grid, s);
-      case EPI_ACC_F32: return launch8<EPI_ACC_F32, true, false>(b, grid, s);
-      default: return hipErrorInvalidValue;
-    }
-  }
-  if (!b_kc) {
-    switch (epi) {
-      case EPI_STORE_F32: return launch8<EPI_STORE_F32, false, false>(b, grid, s);
-      case EPI_ACC_F32: return launch8<EPI_ACC_F32, false, false>(b, grid, s);
-      default: return hipErrorInvalidValue;
-    }
+hipError_t mmt_launch_gemm8(const GemmBatch& b, const GemmPlan& p, hipStream_t s) {
+  switch (gemm_op_key(p.a_kc, p.b_kc, p.epi)) {
+#define X(A_KC, B_KC, EPI)                                                                              \
+  case gemm_op_key(A_KC, B_KC, EPI):                                                                    \
+    hipLaunchKernelGGL((gemm8_kernel<EPI, A_KC, B_KC>), dim3(p.gx, p.gy, p.gz), dim3(512), 0, s, b);    \
+    return hipGetLastError();
+    GEMM8_OPS(X)
+#undef X
   }
   return hipErrorInvalidValue;
 }

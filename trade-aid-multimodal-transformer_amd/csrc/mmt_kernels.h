@@ -170,9 +170,7 @@ hipError_t mmt_launch_ffn(const Mlp2Batch& b, hipStream_t s);
 // with E8M0 exponents per 32 K elements; K % 32 == 0) via v_mfma_scale_f32_32x32x64_f8f6f4, any
 // of the bf16 GEMM's forward epilogues; fp32 accumulation
 hipError_t mmt_launch_gemm_f8(const GemmBatch& b, int epi, hipStream_t s);
-// whether a batch runs on the 256x256 tile (weight-gradient launches can only be merged when equal;
-// the fused Q/K/V stage 2 needs the 128x128 tile)
-bool mmt_gemm_wgrad_big(const GemmBatch& b);
+// (which kernel, tile and grid each of these launches takes: mmt_gemm_plan, mmt_gemm_plan.h)
 
 // ------------------------------------------------------------------------------------------
 // LayerNorm (eps = 1e-5, weight+bias). Row-major [R, C] fp32 in, bf16 out; saves mean/rstd.

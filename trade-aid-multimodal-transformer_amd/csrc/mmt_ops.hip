@@ -1,8 +1,10 @@
 // Single-problem C-ABI wrappers over the kernel launchers (include/mmt.h, mmt_op_*), used by the
 // kernel-level parity tests. Same kernels the engine launches, one group member.
 #include <hip/hip_runtime.h>
+#include <string.h>
 
 #include "mmt.h"
+#include "mmt_gemm_plan.h"
 #include "mmt_kernels.h"
 
 static int st(hipError_t e) { return e == hipSuccess ? MMT_OK : MMT_ERR_HIP; }
@@ -52,6 +54,40 @@ int mmt_op_gemm_wgrad(void* stream, int32_t M, int32_t N, int32_t K, const void*
   const hipError_t e = mmt_launch_gemm_wgrad(b, (float*)slab, slab ? slab_bytes : 0, (hipStream_t)stream);
   if (e == hipErrorInvalidValue) return MMT_ERR_UNSUPPORTED;
   return st(e);
+}
+
+// The launch plan of a GemmBatch made from sizes alone (no stream, no device memory, no HIP call): what
+// mmt_launch_gemm* would launch for it. Pointers the validity checks want are set to a dummy that is never read.
+int mmt_op_gemm_plan(int32_t kind, int32_t a_kc, int32_t b_kc, int32_t epi, int32_t splits, int32_t count,
+                     const int32_t* M, const int32_t* N, const int32_t* K, int32_t lda, int32_t ldb, int32_t tile_hint,
+                     int32_t dw_blocks, int64_t slab_bytes, int32_t flags, int32_t* plan) {
+  if (count < 0 || count > MMT_MAX_GROUP || kind < GEMM_LINEAR || kind > GEMM_F8 || !plan || (count && (!M || !N || !K)))
+    return MMT_ERR_INVALID;
+  alignas(16) static float dummy[4];
+  bool akc = a_kc != 0, bkc = b_kc != 0;
+  gemm_kind_ops(kind, akc, bkc, epi);  // (the leading dimensions below default by layout)
+  const auto pad = [](int v, int to) { return (v + to - 1) / to * to; };
+  const int ldpad = kind == GEMM_F8 ? 16 : 8;
+  GemmBatch b{};
+  b.count = count; b.tile_hint = tile_hint; b.dw_blocks = dw_blocks;
+  for (int g = 0; g < count; ++g) {
+    GemmProblem& p = b.p[g];
+    p.M = M[g]; p.N = N[g]; p.K = K[g]; p.alpha = 1.f;
+    p.lda = lda ? lda : pad(akc ? p.K : p.M, ldpad);
+    p.ldb = ldb ? ldb : pad(bkc ? p.K : p.N, ldpad);
+    p.ldc = p.ldres = p.ldo16 = pad(p.N, 8);
+    p.lds_a = p.lds_b = pad((p.K + 31) / 32, 4);
+    if (kind == GEMM_RESID_LN || kind == GEMM_LN_BWD) {
+      p.resid = dummy; p.o32 = dummy;
+      p.ln_gamma = p.ln_mean = p.ln_rstd = dummy; p.ln_dgamma = p.ln_dbeta = dummy;
+    }
+    if (flags & 1) { p.qkv2_w2 = dummy; p.qkv2_out = (bf16_t*)dummy; p.qkv2_hh = 16; p.qkv2_ld = pad(2 * p.N, 8); }
+    if (flags & 2) { p.lnf_y = (bf16_t*)dummy; p.lnf_gamma = p.lnf_beta = dummy; p.lnf_mean = p.lnf_rstd = dummy; }
+  }
+  const GemmPlan pl = mmt_gemm_plan(b, kind, akc, bkc, epi, splits, slab_bytes);
+  static_assert(sizeof(GemmPlan) == GEMM_PLAN_INTS * sizeof(int32_t), "GemmPlan is all ints");
+  memcpy(plan, &pl, sizeof(pl));
+  return MMT_OK;
 }
 
 int mmt_op_mlp2(void* stream, int32_t M, int32_t C, const void* x, int32_t ldx, const void* w0, int32_t ldw0,
