@@ -125,6 +125,35 @@ int mmt_decode_fanout_step(mmt_ctx* ctx, void* stream, int32_t batch, int32_t sa
                            int32_t pos, const int64_t* const* idx, const float* params, float* const* logits,
                            const void* workspace, void* fan);
 
+/* Rolling-window step (generate with num_samples and rolling=True, past block_size): the paths of a prompt share
+ * the first p rows of their block_size window (the prompt's rows, shifted) and differ only in the last m rows, the
+ * tokens generated so far. One step recomputes those m rows of every path through all layers, over batch*samples*m
+ * compact rows (row r*m + i: tail position i of path r = b*samples + s, at position p + i), and returns the logits
+ * of each path's last row. Cost in rows through the layers: batch*p for the prefix forward plus batch*samples*m,
+ * where the tiled re-forward takes batch*samples*block_size.
+ *   mmt_rolling_bytes  the size of the caller-owned roll buffer for tails of up to max_tail rows: the compact
+ *                      scratch of one step, batch*samples*max_tail rows. The paths' own keys / values are that
+ *                      scratch's K|Q|V and cross-K/V rows of the layer in flight and the residual rows rotate over
+ *                      two layer slots, so the size does not depend on n_layer. -1 for batch, samples or max_tail
+ *                      < 1, max_tail >= block_size, or rows beyond the launchers' 32-bit row * column range.
+ *   mmt_rolling_step   idx[i] points at the first tail token of row 0 of modality i inside an int64 [rows, idx_ld]
+ *                      buffer: tail token i of path r is idx[i][r*idx_ld + i] (idx_ld >= m; no token is copied).
+ *                      logits[i] is fp32 [batch*samples, V_i]. Keys / values of positions < p of path r are the
+ *                      workspace cache rows of sequence r / samples: the last mmt_forward on `workspace` must have
+ *                      been over `batch` sequences whose first p positions are the shared prefix (the engine
+ *                      checks the batch, not the length). The workspace is only read, and the roll buffer holds
+ *                      nothing between calls: any (p, m) with p >= 1, m >= 1, p + m <= block_size and a buffer of
+ *                      mmt_rolling_bytes(batch, samples, max_tail >= m) is valid after such a forward, in any order,
+ *                      and the same call twice gives the same bits. bf16, eval semantics.
+ * MMT_ERR_STATE without such a forward (another batch included), after a forward that sampled dropout and at
+ * precision fp8; MMT_ERR_INVALID for a null pointer, samples / p / m < 1, p + m > block_size, idx_ld < m, rows
+ * beyond the launchers' range, and after a training forward that kept Q/K/V on chip. Every refusal returns before
+ * any launch and leaves logits alone. The launches carry roll_* labels (mmt_probe_set). */
+int64_t mmt_rolling_bytes(mmt_ctx* ctx, int32_t batch, int32_t samples, int32_t max_tail);
+int mmt_rolling_step(mmt_ctx* ctx, void* stream, int32_t batch, int32_t samples, int32_t p, int32_t m,
+                     const int64_t* const* idx, int64_t idx_ld, const float* params, float* const* logits,
+                     const void* workspace, void* roll);
+
 /* Device-side sampling of generate (reference model.py:425-427: softmax of the last logits, torch.multinomial,
  * nothing else): one token per row from fp32 logits with temperature, top-k and top-p, a draw keyed by
  * (seed, row, position), and the log-probability of the token, in ONE launch for all rows (one 256-thread
@@ -937,6 +966,19 @@ int mmt_op_attention_decode_fanout(void* stream, int32_t B, int32_t samples, int
                                    const void* const* k, const void* const* v, int32_t kv_ld, int32_t kv_hstride,
                                    const void* const* tail_k, const void* const* tail_v, int32_t tail_ld,
                                    int32_t tail_rows, void* o, int32_t o_ld);
+/* Rolling-window fan-out attention, the kernel under mmt_rolling_step: every row r = b*samples + s has m tail
+ * positions and all of them are queries, in ONE launch. q and o are compact [B*samples*m, *]: query (r, i) is row
+ * r*m + i. Its keys / values are the cache rows b*T + 0..p-1 of k[j] / v[j], then the row's own tail rows r*m + 0..i
+ * of tail_k[j] / tail_v[j] (bf16 [B*samples*m, tail_ld]; tail_rows must equal m). The arithmetic of query (r, i) is
+ * mmt_op_attention_decode_fanout's at n0 = p, t = p + i on the same buffers with tail_rows = m (one device function
+ * serves both kernels): the same bits. Cache rows >= p, tail rows of other samples and rows past B*samples*m are
+ * never read or written. Before any launch: the checks of mmt_op_attention_decode_fanout with p for n0 and
+ * p + m - 1 for t (so p >= 1, m >= 1, p + m <= T), and MMT_ERR_INVALID for tail_rows != m. */
+int mmt_op_attention_rolling_fanout(void* stream, int32_t B, int32_t samples, int32_t p, int32_t m, int32_t T,
+                                    int32_t H, int32_t hs, int32_t nstreams, const void* q, int32_t q_ld,
+                                    const void* const* k, const void* const* v, int32_t kv_ld, int32_t kv_hstride,
+                                    const void* const* tail_k, const void* const* tail_v, int32_t tail_ld,
+                                    int32_t tail_rows, void* o, int32_t o_ld);
 /* hs-32 causal self-attention (T <= 256) with Q / K / V made on chip: in place of q / k / v the kernels take
  * the stage-1 rows h1 (bf16 [B*T][ld_h1], ld_h1 % 8 == 0, 16-B aligned; column block blk = kind * H + head of
  * 16 columns, kinds K, Q, V; pad columns and rows past the batch are never read) and w2 (fp32 [3 H][32][16],

@@ -13,6 +13,11 @@
 // running state, per sample, 64 keys at a time straight from memory. Scores and probabilities are fp32 on the
 // VALU, the output is rounded once. No atomics; nothing a sample computes depends on the other samples of its
 // group (a short last group recomputes sample S - 1 in its idle lanes and stores nothing for them).
+//
+// The rolling-window step (generate with rolling=True, mmt_rolling_step) has m tail rows per sample and needs the
+// attention of ALL of them: attn_rolling_fanout_kernel is the same body (fanout_body) with the tail position i in
+// blockIdx.y, query / output row r*m + i, the prefix n0 = p and i + 1 tail keys: one launch for the m positions, and
+// per query the bits of attn_decode_fanout_kernel at n0 = p, t = p + i.
 #include "mmt_common.h"
 #include "mmt_kernels.h"
 
@@ -52,11 +57,14 @@ __device__ __forceinline__ void merge_tile(const float (&sc)[4], float& m, float
 
 }  // namespace
 
+// The body both kernels run: one workgroup, its group of samples, n0 prefix keys and nt tail keys. Sample row r
+// reads query row r * qo_rows + qo_at, the tail rows r * tail_rows + 0..nt-1, and writes output row
+// r * qo_rows + qo_at (the fan-out step: qo_rows = 1, qo_at = 0; the rolling step: qo_rows = tail_rows = m,
+// qo_at = the tail position, nt = qo_at + 1).
 template <int HS>
-__global__ __launch_bounds__(256) void attn_decode_fanout_kernel(FanoutAttnBatch batch, int S, int n0, int t, int T,
-                                                                 int H, int tail_rows, float scale) {
+__device__ __forceinline__ void fanout_body(const FanoutAttnProblem& P, int S, int n0, int nt, int T, int H,
+                                            int tail_rows, int qo_rows, int qo_at, float scale) {
   constexpr int NC = (HS + 15) / 16, LDK = HS + 4, CH = HS / 8;
-  const FanoutAttnProblem& P = batch.p[blockIdx.z];
   const int ngrp = (S + FAN_G - 1) / FAN_G;
   const int grp = blockIdx.x % ngrp, bh = blockIdx.x / ngrp, b = bh / H, head = bh % H;
   const int tid = threadIdx.x, sl = tid >> 4, kl = tid & 15;
@@ -68,7 +76,7 @@ __global__ __launch_bounds__(256) void attn_decode_fanout_kernel(FanoutAttnBatch
   float* ps = Ps + sl * FAN_KT;
   float q[HS];
   {
-    const bf16_t* qp = P.q + r * P.q_ld + head * HS;
+    const bf16_t* qp = P.q + (r * qo_rows + qo_at) * P.q_ld + head * HS;
 #pragma unroll
     for (int c = 0; c < CH; ++c) {
       const u32x4 v = *reinterpret_cast<const u32x4*>(qp + 8 * c);
@@ -79,7 +87,6 @@ __global__ __launch_bounds__(256) void attn_decode_fanout_kernel(FanoutAttnBatch
       }
     }
   }
-  const int nt = t - n0 + 1;  // tail keys of every sample
   float o[NC];
 #pragma unroll
   for (int c = 0; c < NC; ++c) o[c] = 0.f;
@@ -178,8 +185,24 @@ __global__ __launch_bounds__(256) void attn_decode_fanout_kernel(FanoutAttnBatch
   if (live) {
 #pragma unroll
     for (int c = 0; c < NC; ++c)
-      if (kl + 16 * c < HS) P.o[r * P.o_ld + head * HS + kl + 16 * c] = f2bf(o[c]);
+      if (kl + 16 * c < HS) P.o[(r * qo_rows + qo_at) * P.o_ld + head * HS + kl + 16 * c] = f2bf(o[c]);
   }
+}
+
+template <int HS>
+__global__ __launch_bounds__(256) void attn_decode_fanout_kernel(FanoutAttnBatch batch, int S, int n0, int t, int T,
+                                                                 int H, int tail_rows, float scale) {
+  fanout_body<HS>(batch.p[blockIdx.z], S, n0, t - n0 + 1 /* tail keys of every sample */, T, H, tail_rows, 1, 0, scale);
+}
+
+// Rolling-window step (mmt_rolling_step): every sample has m tail rows and ALL of them are queries. blockIdx.y = i is
+// the tail position: query / output row r*m + i against the p prefix keys and the sample's tail rows 0..i, the
+// arithmetic of attn_decode_fanout_kernel at n0 = p, t = p + i (same tile walk, same merge order, same bits).
+template <int HS>
+__global__ __launch_bounds__(256) void attn_rolling_fanout_kernel(FanoutAttnBatch batch, int S, int p, int m, int T,
+                                                                  int H, float scale) {
+  const int i = blockIdx.y;
+  fanout_body<HS>(batch.p[blockIdx.z], S, p, i + 1, T, H, m, m, i, scale);
 }
 
 hipError_t mmt_launch_attn_decode_fanout(const FanoutAttnBatch& b, int B, int S, int n0, int t, int T, int H, int hs,
@@ -201,5 +224,27 @@ hipError_t mmt_launch_attn_decode_fanout(const FanoutAttnBatch& b, int B, int S,
     default: return hipErrorInvalidValue;
   }
 #undef FAN_LAUNCH
+  return hipGetLastError();
+}
+
+hipError_t mmt_launch_attn_rolling_fanout(const FanoutAttnBatch& b, int B, int S, int p, int m, int T, int H, int hs,
+                                          float scale, hipStream_t s) {
+  if (b.count == 0) return hipSuccess;
+  if (B < 1 || S < 1 || H < 1 || p < 1 || m < 1 || (int64_t)p + m > T || m > 65535) return hipErrorInvalidValue;
+  const int64_t wgs = (int64_t)B * H * ((S + FAN_G - 1) / FAN_G);
+  if (wgs > 0x7fffffff) return hipErrorInvalidValue;
+  const dim3 grid((unsigned)wgs, (unsigned)m, b.count);
+#define ROLL_LAUNCH(HS_) \
+  hipLaunchKernelGGL(attn_rolling_fanout_kernel<HS_>, grid, dim3(256), 0, s, b, S, p, m, T, H, scale)
+  switch (hs) {
+    case 8: ROLL_LAUNCH(8); break;
+    case 16: ROLL_LAUNCH(16); break;
+    case 24: ROLL_LAUNCH(24); break;
+    case 32: ROLL_LAUNCH(32); break;
+    case 48: ROLL_LAUNCH(48); break;
+    case 64: ROLL_LAUNCH(64); break;
+    default: return hipErrorInvalidValue;
+  }
+#undef ROLL_LAUNCH
   return hipGetLastError();
 }

@@ -255,7 +255,7 @@ __global__ __launch_bounds__(256) void embed_fwd_kernel(EmbBatch batch, int R, i
   if (i >= (int64_t)R * C4) return;
   const int r = (int)(i / C4), c4 = (int)(i % C4);
   const int t = r % T;
-  int64_t id = P.idx[r];
+  int64_t id = P.idx_ld ? P.idx[(int64_t)(r / T) * P.idx_ld + t] : P.idx[r];
   id = id < 0 ? 0 : (id >= P.V ? P.V - 1 : id);
   const f32x4 a = reinterpret_cast<const f32x4*>(P.tok + id * C)[c4];
   const f32x4 p = reinterpret_cast<const f32x4*>(P.pos + (int64_t)t * C)[c4];

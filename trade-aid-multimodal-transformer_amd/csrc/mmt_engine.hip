@@ -123,6 +123,16 @@ struct FanPlan {
   std::vector<size_t> ca_tail;  // [L*M][MAXM]
 };
 
+// Rolling-window step (mmt_rolling_step): the compact scratch of B*S*m rows in the caller's roll buffer, residual
+// rows in two layer slots (dec_x [2*M][3]), and per modality the fp32 [B*S, C] rows the post block reads (the last
+// tail row of every path)
+struct RollPlan {
+  size_t total = 0;
+  Plan::Dec dec[MAXM];
+  std::vector<size_t> dec_x;
+  size_t last[MAXM];
+};
+
 }  // namespace
 
 // Every MMT_* environment variable the engine reads, with its default and its meaning (DESIGN.md §3 has the same
@@ -519,12 +529,13 @@ size_t flag_offset(const mmt_ctx* c) { return (size_t)rup(c->pack_elems * 2, 256
 // workspace plan for batch B (continued)
 // -------------------------------------------------------------------------------------------
 // the compact [rows, *] scratch of one decode step, every modality (rows = B, or B*S in a fan buffer)
+// xlayers: the layers whose residual rows are kept apart (every layer; the rolling step rotates over two)
 template <class Alloc>
-void plan_dec_rows(mmt_ctx* c, Alloc& A, size_t B, Plan::Dec* dec, std::vector<size_t>& dec_x) {
+void plan_dec_rows(mmt_ctx* c, Alloc& A, size_t B, Plan::Dec* dec, std::vector<size_t>& dec_x, int xlayers) {
   const int C = c->C, M = c->M, H = c->H;
   const size_t f4 = 4, b2 = 2;
   const int ldh1 = r8(3 * H * c->hh), ldp = r8(C / 2);
-  dec_x.resize((size_t)c->L * M * 3);
+  dec_x.resize((size_t)xlayers * M * 3);
   for (int i = 0; i < M; ++i) {
     Plan::Dec& d = dec[i];
     d.x0 = A(B * C * f4); d.a16 = A(B * C * b2); d.mean = A(B * f4); d.rstd = A(B * f4);
@@ -547,7 +558,7 @@ bool make_fan_plan(mmt_ctx* c, FanPlan& f, int B, int S, int max_new) {
   f.B = B; f.S = S; f.max_new = max_new;
   size_t cur = 0;
   auto A = [&](size_t bytes) { const size_t o = cur; cur += (size_t)rup((int64_t)bytes, 256); return o; };
-  plan_dec_rows(c, A, (size_t)rows, f.dec, f.dec_x);
+  plan_dec_rows(c, A, (size_t)rows, f.dec, f.dec_x, c->L);
   const int M = c->M;
   f.sa_tail.assign((size_t)c->L * M, 0);
   f.ca_tail.assign((size_t)c->L * M * MAXM, 0);
@@ -557,6 +568,24 @@ bool make_fan_plan(mmt_ctx* c, FanPlan& f, int B, int S, int max_new) {
       if (c->lm[(size_t)l * M + i].cross)
         for (int j = 0; j < M - 1; ++j) f.ca_tail[((size_t)l * M + i) * MAXM + j] = A((size_t)rows * max_new * 2 * c->C * 2);
     }
+  f.total = cur;
+  return true;
+}
+
+// the buffer of mmt_rolling_step (include/mmt.h) for tails of m rows: the compact scratch of B*S*m rows and nothing
+// else. The rows' own keys / values are that scratch's K|Q|V and cross-K/V rows of the layer in flight, and the
+// residual rows of layer l live in slot l & 1, so the size does not depend on the number of layers
+bool make_roll_plan(mmt_ctx* c, RollPlan& f, int B, int S, int m) {
+  f = RollPlan();
+  if (B < 1 || S < 1 || m < 1 || m >= c->T) return false;
+  const int64_t rows = (int64_t)B * S * m;
+  int64_t wide = 4 * (int64_t)c->C;
+  for (int i = 0; i < c->M; ++i) wide = std::max<int64_t>(wide, c->ldv[i]);
+  if ((int64_t)B * S >= ((int64_t)1 << 31) || rows * wide >= ((int64_t)1 << 31)) return false;  // as make_fan_plan
+  size_t cur = 0;
+  auto A = [&](size_t bytes) { const size_t o = cur; cur += (size_t)rup((int64_t)bytes, 256); return o; };
+  plan_dec_rows(c, A, (size_t)rows, f.dec, f.dec_x, 2);
+  for (int i = 0; i < c->M; ++i) f.last[i] = A((size_t)B * S * c->C * 4);
   f.total = cur;
   return true;
 }
@@ -658,7 +687,7 @@ void make_plan(mmt_ctx* c, int B) {
     p.det = A((size_t)df * f4);
   }
   // decode scratch (tiny: B rows)
-  plan_dec_rows(c, A, (size_t)B, p.dec, p.dec_x);
+  plan_dec_rows(c, A, (size_t)B, p.dec, p.dec_x, c->L);
   p.total = cur;
 }
 
@@ -1530,10 +1559,19 @@ int run_forward(mmt_ctx* c, Runner& r, const int64_t* const* idx, const int64_t*
 // leaves the workspace alone: keys / values of positions < n0 are read from the cache rows of sequence b,
 // position t is appended to the fan buffer's tails (row r*max_new + t - n0) and the attention is the fan-out
 // kernel. Everything else is the same launches over `rows` rows.
+//
+// The rolling step (mmt_rolling_step, roll_m > 0) is the same walk over B*S*m rows, row r*m + i being tail position
+// i of path r = b*S + s at sequence position roll_p + i: the embedding reads token i of row r of the caller's
+// [B*S, idx_ld] buffers, stage 2 and the cross-K/V projections write all m positions of every path, which makes the
+// compact K|Q|V and cross-K/V rows of the layer in flight the paths' tails (row r*m + i), and the attention is the
+// rolling fan-out kernel over the roll_p cache rows and those tails. The residual rows of layer l live in slot
+// l % xlayers; the post block runs over the B*S last tail rows, gathered to `last`. Its launches carry roll_* labels.
 // -------------------------------------------------------------------------------------------
 struct DecWhere {
   char* base; const Plan::Dec* dec; const size_t* dec_x; int rows;
   const FanPlan* fan = nullptr; int S = 1, n0 = 0;
+  int xlayers = 0;  // layer slots of dec_x (0: one per layer)
+  int roll_p = 0, roll_m = 0; int64_t idx_ld = 0; const size_t* last = nullptr;
   template <class T>
   T* at(size_t off) const { return reinterpret_cast<T*>(base + off); }
 };
@@ -1552,6 +1590,8 @@ int run_decode(mmt_ctx* c, Runner& r, const DecWhere& w, int t, const int64_t* c
                           hipMemcpyDeviceToDevice, r.s), what);
   };
   const int tail_rows = w.fan ? w.fan->max_new : 0;
+  const int rm = w.roll_m;  // > 0: the rolling step
+  auto lb = [&](const char* dec, const char* roll) { return rm ? roll : dec; };
   auto tail_append = [&](bf16_t* tail, int ld, const bf16_t* rows, const char* what) {
     // compact row r -> tail row r*max_new + (t - n0)
     r.ok(hipMemcpy2DAsync(tail + (size_t)(t - w.n0) * ld, (size_t)tail_rows * ld * 2, rows, (size_t)ld * 2,
@@ -1567,8 +1607,10 @@ int run_decode(mmt_ctx* c, Runner& r, const DecWhere& w, int t, const int64_t* c
     for (int i = 0; i < M; ++i) {
       eb.p[i].idx = idx[i]; eb.p[i].tok = r.P(c->post[i].tok); eb.p[i].pos = r.P(c->pos_off) + (int64_t)t * C;
       eb.p[i].x = w.at<float>(w.dec[i].x0); eb.p[i].V = c->V[i];
+      eb.p[i].idx_ld = w.idx_ld;  // rolling: token i of path r at idx[i][r * idx_ld + i], position t + i
     }
-    r.ok(mmt_launch_embed_fwd(eb, R, 1, C, r.s), "dec_embed");
+    r.ok(rm ? mmt_launch_embed_fwd(eb, R / rm, rm, C, r.s) : mmt_launch_embed_fwd(eb, R, 1, C, r.s),
+         lb("dec_embed", "roll_embed"));
   }
   std::vector<const float*> xin(M);
   for (int i = 0; i < M; ++i) xin[i] = w.at<float>(w.dec[i].x0);
@@ -1576,11 +1618,12 @@ int run_decode(mmt_ctx* c, Runner& r, const DecWhere& w, int t, const int64_t* c
     const LM* x = &c->lm[(size_t)l * M];
     const ActLM* a = &p.act[(size_t)l * M];
     const Plan::Dec* d = w.dec;
-    auto X = [&](int i, int k) { return w.at<float>(w.dec_x[((size_t)l * M + i) * 3 + k]); };
+    const size_t lx = w.xlayers ? l % w.xlayers : l;
+    auto X = [&](int i, int k) { return w.at<float>(w.dec_x[(lx * M + i) * 3 + k]); };
     r.ok(mmt_launch_ln_fwd(lns(M, [&](int i) { return ln(i, xin[i], x[i].ln1w, x[i].ln1b, d[i].a16); }), R, C, r.s),
-         "dec_ln1");
+         lb("dec_ln1", "roll_ln1"));
     r.fgemm(gemms(M, [&](int i) { return r.linear(D(d[i].a16), C, x[i].W1, x[i].b1).out16(D(d[i].h1), ldh1); }),
-            EPI_BIAS_TANH_BF16, "dec_qkv1");
+            EPI_BIAS_TANH_BF16, lb("dec_qkv1", "roll_qkv1"));
     Qkv2Batch qb{}; qb.count = M;
     for (int i = 0; i < M; ++i) {
       qb.p[i].h1 = D(d[i].h1); qb.p[i].w2 = r.P(x[i].w2); qb.p[i].out = D(d[i].qkv);
@@ -1588,8 +1631,18 @@ int run_decode(mmt_ctx* c, Runner& r, const DecWhere& w, int t, const int64_t* c
       // kernel forms (int64) row * ld and writes the 3C columns only), so no append copy and no compact K|Q|V row
       if (w.fan) qb.p[i].out = D(w.fan->sa_tail[(size_t)l * M + i]) + (size_t)(t - w.n0) * 3 * C;
     }
-    r.ok(mmt_launch_qkv2_fwd(qb, R, 3 * H, hs, ldh1, w.fan ? tail_rows * 3 * C : 3 * C, r.s), "dec_qkv2");
-    if (w.fan) {
+    r.ok(mmt_launch_qkv2_fwd(qb, R, 3 * H, hs, ldh1, w.fan ? tail_rows * 3 * C : 3 * C, r.s),
+         lb("dec_qkv2", "roll_qkv2"));
+    if (rm) {
+      const FanoutAttnBatch fb = batch_of<FanoutAttnBatch>(M, [&](int i) {
+        FanoutAttnProblem q{};
+        bf16_t* tail = D(d[i].qkv);  // the K|Q|V rows stage 2 just wrote: queries and tails at once
+        self_attn_io(q, tail + C, 3 * C, r.b16(a[i].qkv), D(d[i].o16), C, hs);
+        q.tk[0] = tail; q.tv[0] = tail + 2 * C; q.tail_ld = 3 * C;
+        return q;
+      });
+      r.ok(mmt_launch_attn_rolling_fanout(fb, B, w.S, w.roll_p, rm, T, H, hs, scale, r.s), "roll_attn");
+    } else if (w.fan) {
       const FanoutAttnBatch fb = batch_of<FanoutAttnBatch>(M, [&](int i) {
         FanoutAttnProblem q{};
         bf16_t* tail = D(w.fan->sa_tail[(size_t)l * M + i]);
@@ -1609,18 +1662,18 @@ int run_decode(mmt_ctx* c, Runner& r, const DecWhere& w, int t, const int64_t* c
       r.ok(mmt_launch_attn_decode(ab, B, t, T, H, hs, scale, r.s), "dec_attn");
     }
     r.fgemm(gemms(M, [&](int i) { return r.linear(D(d[i].o16), C, x[i].P0, x[i].bp0).out16(D(d[i].p1), ldp); }),
-            EPI_BIAS_TANH_BF16, "dec_proj0");
+            EPI_BIAS_TANH_BF16, lb("dec_proj0", "roll_proj0"));
     r.fgemm(gemms(M, [&](int i) { return r.linear(D(d[i].p1), ldp, x[i].P2, x[i].bp2).out32(X(i, 0), C, xin[i]); }),
-            EPI_BIAS_RESID_F32, "dec_proj2");
+            EPI_BIAS_RESID_F32, lb("dec_proj2", "roll_proj2"));
     r.ok(mmt_launch_ln_fwd(lns(M, [&](int i) { return ln(i, X(i, 0), x[i].ln2w, x[i].ln2b, d[i].a16); }), R, C, r.s),
-         "dec_ln2");
+         lb("dec_ln2", "roll_ln2"));
     r.fgemm(gemms(M, [&](int i) { return r.linear(D(d[i].a16), C, x[i].F0, x[i].bf0).out16(D(d[i].f), 4 * C); }),
-            EPI_BIAS_RELU_BF16, "dec_ffn0");
+            EPI_BIAS_RELU_BF16, lb("dec_ffn0", "roll_ffn0"));
     r.fgemm(gemms(M, [&](int i) {
               Lin g = r.linear(D(d[i].f), 4 * C, x[i].F2, x[i].bf2).out32(X(i, 1), C, X(i, 0));
               if (c->any_cross) g.out16(D(d[i].x2h), C);
               return g;
-            }), EPI_BIAS_RESID_F32, "dec_ffn2");
+            }), EPI_BIAS_RESID_F32, lb("dec_ffn2", "roll_ffn2"));
     std::vector<const float*> xout(M);
     for (int i = 0; i < M; ++i) xout[i] = X(i, 1);
     if (c->any_cross) {
@@ -1629,18 +1682,28 @@ int run_decode(mmt_ctx* c, Runner& r, const DecWhere& w, int t, const int64_t* c
       r.ok(mmt_launch_ln_fwd(lns(nc, [&](int u) {
                                const int i = cx[u];
                                return ln(i, X(i, 1), x[i].lncw, x[i].lncb, d[i].d16);
-                             }), R, C, r.s), "dec_lnc");
+                             }), R, C, r.s), lb("dec_lnc", "roll_lnc"));
       r.fgemm(gemms(nc, [&](int u) {
                 const int i = cx[u];
                 return r.linear(D(d[i].d16), C, x[i].Wq, -1).out16(D(d[i].qc), C);
-              }), EPI_STORE_BF16, "dec_ca_q");
+              }), EPI_STORE_BF16, lb("dec_ca_q", "roll_ca_q"));
       GemmBatch gk{};
       for_each_cross_kv(cx, M, false,
                         [&](int i, int j, int jj) {
                           gk.p[gk.count++] = r.linear(D(d[j].x2h), C, x[i].Wkv[jj], -1).out16(D(d[i].kv[jj]), 2 * C);
                         },
-                        [&] { r.fgemm(gk, EPI_STORE_BF16, "dec_ca_kv"); gk = GemmBatch{}; });
-      if (w.fan) {
+                        [&] { r.fgemm(gk, EPI_STORE_BF16, lb("dec_ca_kv", "roll_ca_kv")); gk = GemmBatch{}; });
+      if (rm) {
+        const FanoutAttnBatch fb = batch_of<FanoutAttnBatch>(nc, [&](int u) {
+          const int i = cx[u];
+          FanoutAttnProblem q{};
+          cross_attn_io(q, D(d[i].qc), [&](int j) { return r.b16(a[i].kv[j]); }, M - 1, D(d[i].oc), C, hs);
+          for (int j = 0; j < M - 1; ++j) { q.tk[j] = D(d[i].kv[j]); q.tv[j] = q.tk[j] + hs; }  // the rows just made
+          q.tail_ld = 2 * C;
+          return q;
+        });
+        r.ok(mmt_launch_attn_rolling_fanout(fb, B, w.S, w.roll_p, rm, T, H, hs, scale, r.s), "roll_ca_attn");
+      } else if (w.fan) {
         const FanoutAttnBatch fb = batch_of<FanoutAttnBatch>(nc, [&](int u) {
           const int i = cx[u];
           FanoutAttnProblem q{};
@@ -1667,16 +1730,36 @@ int run_decode(mmt_ctx* c, Runner& r, const DecWhere& w, int t, const int64_t* c
       r.fgemm(gemms(nc, [&](int u) {
                 const int i = cx[u];
                 return r.linear(D(d[i].oc), C, x[i].C0, x[i].bc0).out16(D(d[i].pc), ldp);
-              }), EPI_BIAS_TANH_BF16, "dec_ca_proj0");
+              }), EPI_BIAS_TANH_BF16, lb("dec_ca_proj0", "roll_ca_proj0"));
       r.fgemm(gemms(nc, [&](int u) {
                 const int i = cx[u];
                 return r.linear(D(d[i].pc), ldp, x[i].C2, x[i].bc2).out32(X(i, 2), C, X(i, 1));
-              }), EPI_BIAS_RESID_F32, "dec_ca_proj2");
+              }), EPI_BIAS_RESID_F32, lb("dec_ca_proj2", "roll_ca_proj2"));
       for (int i : cx) xout[i] = X(i, 2);
     }
     xin = xout;
   }
   if (r.rc != MMT_OK) return r.rc;
+  if (rm) {
+    // the post block over the paths' last tail rows only: fp32 row r*m + m - 1 -> row r of `last`
+    const int paths = R / rm;
+    for (int i = 0; i < M; ++i) {
+      float* dst = w.at<float>(w.last[i]);
+      r.ok(hipMemcpy2DAsync(dst, (size_t)C * 4, xin[i] + (size_t)(rm - 1) * C, (size_t)rm * C * 4, (size_t)C * 4, paths,
+                            hipMemcpyDeviceToDevice, r.s), "roll_last_rows");
+      xin[i] = dst;
+    }
+    if (r.rc != MMT_OK) return r.rc;
+    r.R = paths;
+    static const char* const roll_labels[3] = {"roll_lnf", "roll_head0", "roll_head2"};
+    run_post(c, r, paths, xin, nullptr,
+             [&](int i) {
+               const Plan::Dec& d = w.dec[i];
+               return PostRows{D(d.lnf16), w.at<float>(d.mean), w.at<float>(d.rstd), D(d.hh)};
+             },
+             logits, LnBatch{}, roll_labels);
+    return r.rc;
+  }
   static const char* const post_labels[3] = {"dec_lnf", "dec_head0", "dec_head2"};
   run_post(c, r, R, xin, nullptr,
            [&](int i) {
@@ -2255,6 +2338,47 @@ int mmt_decode_fanout_step(mmt_ctx* c, void* stream, int32_t batch, int32_t samp
   const int rc = run_decode(c, r, w, pos, idx, logits);
   if (rc == MMT_OK) { c->fan_n0 = n0; c->fan_S = samples; c->fan_next = pos + 1; }
   return rc;
+}
+
+int64_t mmt_rolling_bytes(mmt_ctx* c, int32_t batch, int32_t samples, int32_t max_tail) {
+  if (!c) return -1;
+  RollPlan f;
+  if (!make_roll_plan(c, f, batch, samples, max_tail)) return -1;
+  return (int64_t)f.total;
+}
+
+int mmt_rolling_step(mmt_ctx* c, void* stream, int32_t batch, int32_t samples, int32_t p, int32_t m,
+                     const int64_t* const* idx, int64_t idx_ld, const float* params, float* const* logits,
+                     const void* workspace, void* roll) {
+  if (!c) return MMT_ERR_INVALID;
+  const char* me = "mmt_rolling_step";
+  if (!idx || !params || !logits || !workspace || !roll) return fail(c, MMT_ERR_INVALID, std::string(me) + ": null argument");
+  for (int i = 0; i < c->M; ++i)
+    if (!idx[i] || !logits[i]) return fail(c, MMT_ERR_INVALID, std::string(me) + ": null token or logits pointer");
+  if (batch < 1) return fail(c, MMT_ERR_INVALID, std::string(me) + ": need batch >= 1");
+  if (c->plan.B != batch || !c->cache_ready)
+    return fail(c, MMT_ERR_STATE, std::string(me) + ": run mmt_forward over the prefix on this batch and workspace first");
+  if (c->onchip == 3)
+    return fail(c, MMT_ERR_INVALID, std::string(me) + ": the last forward (training != 0) kept the self-attention Q/K/V "
+                                    "on chip, so the workspace holds no K/V cache: run the forward with training = 0");
+  if (c->fwd_drop)
+    return fail(c, MMT_ERR_STATE, std::string(me) + ": the forward sampled dropout (training mode); the step has eval "
+                                  "semantics: run the forward with training = 0");
+  if (c->fp8)
+    return fail(c, MMT_ERR_STATE, std::string(me) + ": precision fp8 runs the forward with MX-fp8 GEMMs the bf16 step "
+                                  "would not reproduce");
+  if (samples < 1 || p < 1 || m < 1 || (int64_t)p + m > c->T || idx_ld < m)
+    return fail(c, MMT_ERR_INVALID, std::string(me) + ": need samples >= 1, p >= 1, m >= 1, p + m <= block_size, "
+                                    "idx_ld >= m");
+  // the plan of exactly m tail rows: no state is kept, and a buffer of mmt_rolling_bytes(max_tail >= m) holds it
+  RollPlan f;
+  if (!make_roll_plan(c, f, batch, samples, m))
+    return fail(c, MMT_ERR_INVALID, std::string(me) + ": batch * samples * m rows exceed the launchers' range");
+  const int rows = batch * samples * m;
+  Runner r{c, (hipStream_t)stream, const_cast<void*>(workspace), params, nullptr, batch, rows};
+  DecWhere w{static_cast<char*>(roll), f.dec, f.dec_x.data(), rows};
+  w.S = samples; w.xlayers = 2; w.roll_p = p; w.roll_m = m; w.idx_ld = idx_ld; w.last = f.last;
+  return run_decode(c, r, w, p, idx, logits);
 }
 
 int mmt_fanout_gather(mmt_ctx* c, void* stream, int32_t batch, int32_t samples, int32_t n0, int32_t max_new,

@@ -330,6 +330,11 @@ struct FanoutAttnProblem {
 struct FanoutAttnBatch { FanoutAttnProblem p[MMT_MAX_GROUP]; int count; };
 hipError_t mmt_launch_attn_decode_fanout(const FanoutAttnBatch& b, int B, int S, int n0, int t, int T, int H, int hs,
                                          int tail_rows, float scale, hipStream_t s);
+// Rolling-window step: every sample has m tail rows, all of them queries. q / o are [B*S*m, *] (query (r, i) is row
+// r*m + i), the tails [B*S*m, tail_ld]; query (r, i) sees the p prefix rows of its prompt and tail rows r*m + 0..i.
+// One launch, the tail position in blockIdx.y; the arithmetic of the fan-out kernel at n0 = p, t = p + i
+hipError_t mmt_launch_attn_rolling_fanout(const FanoutAttnBatch& b, int B, int S, int p, int m, int T, int H, int hs,
+                                          float scale, hipStream_t s);
 
 // Row gather of the fan-out tails (mmt_fanout_gather, mmt_evidence.hip): for every segment, the first `bytes`
 // bytes of dst row r become those of src row anc[r]; rows are row_bytes apart. Bases, row_bytes and bytes are
@@ -458,7 +463,8 @@ hipError_t mmt_launch_qkv2_bwd(const Qkv2Batch& b, int R, int nblk, int hs, int 
 // Misc elementwise / reduction kernels
 // ------------------------------------------------------------------------------------------
 struct EmbProblem {
-  const int64_t* idx;   // [B*T]
+  const int64_t* idx;   // [B*T]; forward with idx_ld != 0: row b's T tokens start at idx + b * idx_ld
+  int64_t idx_ld;
   const float* tok;     // [V, C]
   const float* pos;     // [T, C]
   float* x;             // [B*T, C]

@@ -352,6 +352,34 @@ int mmt_op_attention_decode_fanout(void* stream, int32_t B, int32_t samples, int
   return st(mmt_launch_attn_decode_fanout(b, B, samples, n0, t, T, H, hs, tail_rows, scale, (hipStream_t)stream));
 }
 
+// rolling-window fan-out attention (mmt_decode_fanout.hip), the launcher mmt_rolling_step calls: m tail queries per
+// row in one launch; the fan-out op's checks with n0 = p and t = p + m - 1, before any launch
+int mmt_op_attention_rolling_fanout(void* stream, int32_t B, int32_t samples, int32_t p, int32_t m, int32_t T,
+                                    int32_t H, int32_t hs, int32_t nstreams, const void* q, int32_t q_ld,
+                                    const void* const* k, const void* const* v, int32_t kv_ld, int32_t kv_hstride,
+                                    const void* const* tail_k, const void* const* tail_v, int32_t tail_ld,
+                                    int32_t tail_rows, void* o, int32_t o_ld) {
+  if (!q || !k || !v || !tail_k || !tail_v || !o || B < 1 || H < 1 || samples < 1) return MMT_ERR_INVALID;
+  if (nstreams < 1 || nstreams > MMT_MAX_STREAMS || p < 1 || m < 1 || (int64_t)p + m > T) return MMT_ERR_INVALID;
+  if (tail_rows != m) return MMT_ERR_INVALID;
+  if (hs != 8 && hs != 16 && hs != 24 && hs != 32 && hs != 48 && hs != 64) return MMT_ERR_UNSUPPORTED;
+  if ((q_ld & 7) || (kv_ld & 7) || (kv_hstride & 7) || (tail_ld & 7)) return MMT_ERR_INVALID;  // 16-byte loads
+  for (int j = 0; j < nstreams; ++j)
+    if (!k[j] || !v[j] || !tail_k[j] || !tail_v[j]) return MMT_ERR_INVALID;
+  FanoutAttnBatch b{};
+  b.count = 1;
+  FanoutAttnProblem& pr = b.p[0];
+  pr.q = (const bf16_t*)q; pr.q_ld = q_ld; pr.kv_ld = kv_ld; pr.kv_hstride = kv_hstride; pr.tail_ld = tail_ld;
+  pr.nstreams = nstreams;
+  for (int j = 0; j < nstreams; ++j) {
+    pr.k[j] = (const bf16_t*)k[j]; pr.v[j] = (const bf16_t*)v[j];
+    pr.tk[j] = (const bf16_t*)tail_k[j]; pr.tv[j] = (const bf16_t*)tail_v[j];
+  }
+  pr.o = (bf16_t*)o; pr.o_ld = o_ld;
+  const float scale = 1.0f / __builtin_sqrtf((float)hs);
+  return st(mmt_launch_attn_rolling_fanout(b, B, samples, p, m, T, H, hs, scale, (hipStream_t)stream));
+}
+
 // hs-32 self-attention with Q / K / V made on chip from the stage-1 rows (AttnProblem::oc_*)
 int mmt_op_attention_fwd_h1_drop(void* stream, int32_t B, int32_t T, int32_t H, const void* h1, int32_t ld_h1,
                                  const float* w2, void* o, int32_t o_ld, float* lse, uint32_t drop_key, uint32_t drop_thr,

@@ -110,7 +110,10 @@ _SIGS = {
     "mmt_fanout_bytes": (c_i64, [c_vp, c_i32, c_i32, c_i32]),
     "mmt_decode_fanout_step": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(c_vp), c_vp,
                                        ctypes.POINTER(c_vp), c_vp, c_vp]),
-    "mmt_sample": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_i64, c_f32, c_i32, c_f32, ctypes.c_uint64, ctypes.c_uint32,
+    "mmt_rolling_bytes": (c_i64, [c_vp, c_i32, c_i32, c_i32]),
+    "mmt_rolling_step": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(c_vp), c_i64, c_vp,
+                                 ctypes.POINTER(c_vp), c_vp, c_vp]),
+    "mmt_sample":(c_i32, [c_vp, c_i32, c_i32, c_vp, c_i64, c_f32, c_i32, c_f32, ctypes.c_uint64, ctypes.c_uint32,
                            ctypes.c_uint32, c_vp, c_i64, c_vp, c_vp, c_i64]),
     "mmt_sample_multi": (c_i32, [c_vp, c_i32, c_i32, ctypes.POINTER(c_i32), ctypes.POINTER(c_vp),
                                  ctypes.POINTER(c_i64), ctypes.POINTER(c_f32), ctypes.POINTER(c_i32),
@@ -253,6 +256,9 @@ _SIGS = {
     "mmt_op_attention_decode_fanout": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp,
                                                c_i32, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_i32, c_i32,
                                                ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_i32, c_i32, c_vp, c_i32]),
+    "mmt_op_attention_rolling_fanout": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp,
+                                                c_i32, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_i32, c_i32,
+                                                ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_i32, c_i32, c_vp, c_i32]),
     "mmt_op_attention_fwd_h1": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp]),
     "mmt_op_attention_bwd_h1": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32,
                                         c_vp, c_vp, c_vp]),

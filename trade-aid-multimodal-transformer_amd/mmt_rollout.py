@@ -7,7 +7,8 @@ views of the step and runs the stages on them, in this order: sample (mmt_sample
 (evidence, mmt_score_multi), forecast (mmt_forecast_multi), then the resampling point. There are two sources and they
 are all that differs between the paths: CachedSource (mmt_decode_step while the KV cache holds the position before,
 else the re-forward over the cropped buffers) and FanoutSource (one prefill over the prompts, then
-mmt_decode_fanout_step over the samples' rows). The int form of generate is a plan of one generated modality keyed by
+mmt_decode_fanout_step over the samples' rows; RollingSource carries it past the block: a forward over the prompts'
+shared rows and one mmt_rolling_step over each path's own). The int form of generate is a plan of one generated modality keyed by
 the raw seed (`rollout_int`). `reference_loop` is the reference's per-token loop with the choice of the next token
 passed in: torch.multinomial / sample_fn for the default path, mmt_sample for device calls with prompts of unequal
 lengths."""
@@ -279,6 +280,38 @@ def fans_out(cache, shapes, N, S, T):
             and shapes[0][1] >= 1 and shapes[0][1] + N <= T and N >= 1)
 
 
+def rolls(cache, shapes, N, S, T, rolling=False):
+    """Whether generate(num_samples=S, rolling=True) runs the rolling-window engine: `rolling` is given, the fans_out
+    conditions hold with the bound n0 + N <= T lifted (the cache rule, [B, n0 >= 1] prompts of one shape, N >= 1),
+    the prompt fits the block (n0 <= T), N <= T (so the shared prefix of the last step keeps a row) and the call
+    leaves the block at all: the last step reads a sequence of n0 + N - 1 > T tokens. A call that stays inside the
+    block is fans_out's (bit for bit the call without the keyword); everything else is tiled."""
+    return (bool(rolling) and S is not None and bool(cache) and all(len(sh) == 2 for sh in shapes)
+            and len(set(shapes)) == 1 and 1 <= shapes[0][1] <= T and 1 <= N <= T and shapes[0][1] + N - 1 > T)
+
+
+def generate_path(cache, shapes, N, S, T, rolling=False):
+    """model.last_generate_path of a call with num_samples: "fanout" where fans_out holds (whatever `rolling`
+    says), "rolling" where rolls holds, else "tiled"."""
+    if fans_out(cache, shapes, N, S, T):
+        return "fanout"
+    return "rolling" if rolls(cache, shapes, N, S, T, rolling) else "tiled"
+
+
+def rolling_step(n0, j, T):
+    """What new token j of a rolling call runs. The step reads a sequence of n = n0 + j tokens. While n <= T the
+    existing steps apply (None): the prefill at j == 0, then mmt_decode_fanout_step at position n - 1. Past the block
+    every position shifts: (k, m, p) with k = n - T the window's first column, m = j the path's own last rows and
+    p = T - m the rows of the prompt, shifted, that all paths of a prompt share."""
+    n = n0 + j
+    return None if n <= T else (n - T, j, T - j)
+
+
+def rolling_schedule(n0, N, T):
+    """rolling_step for j = 0..N-1."""
+    return [rolling_step(n0, j, T) for j in range(N)]
+
+
 @torch.no_grad()
 def reference_loop(model, seqs, N, g, use_cache, pick):
     """The reference's loop (its model.py:404-446) over `seqs`, a list the loop extends: per new token the logits of
@@ -391,16 +424,49 @@ class FanoutSource:
         self.fan, self.fan2 = self.fan2, self.fan
 
 
+class RollingSource(FanoutSource):
+    """FanoutSource for a call that leaves the block (rolls, rolling_step). While the sequence read fits the block
+    the steps are FanoutSource's, with a fan buffer for the block_size - n0 positions left. Past it, step j runs one
+    ordinary forward over the B prompts' columns k..n0-1 (the p = block_size - j rows every path of a prompt shares,
+    at their shifted positions), which leaves their keys / values in the workspace, then ONE mmt_rolling_step over
+    the paths' own m = j tokens, read in place from columns n0..n-1 of the [rows, cap] sequence buffers (generated,
+    given and held modalities alike). No torch op per token beyond that forward, and no sync."""
+
+    def __init__(self, model, prompts, shape, dec, need, nbytes, seqs, cap, roll_bytes):
+        B, S, n0, N = shape
+        super().__init__(model, prompts, (B, S, n0, model.block_size - n0), dec, need, nbytes, False)
+        self.seqs, self.cap = seqs, cap
+        self.roll_buf = torch.empty(roll_bytes, dtype=torch.uint8, device=prompts[0].device)
+        self.roll, self.tail = ML.ptr(self.roll_buf), ML.ptr_array(seqs)
+
+    def views(self, j, n, stream):
+        m = self.model
+        B, S, n0, _ = self.shape
+        step = rolling_step(n0, j, m.block_size)
+        if step is None:
+            return super().views(j, n, stream)
+        k, mt, p = step
+        m([pr[:, k:n0] for pr in self.prompts])
+        d = self.dec.at(j - 1)
+        for i, buf in enumerate(self.seqs):
+            self.tail[i] = buf.data_ptr() + 8 * (n - mt)
+        rc = ML.lib().mmt_rolling_step(m._ctx, stream, B, S, p, mt, self.tail, self.cap, d.flat, d.out, ML.ptr(m._ws),
+                                       self.roll)
+        ML.check(rc, m._ctx, "mmt_rolling_step")
+        return d.logits
+
+
 @torch.no_grad()
 def rollout(model, idx_list, plan, use_cache, temperature, top_k, top_p, seed, return_logprobs, logits_hook, S,
-            seed_of=MS.modality_seed):
+            seed_of=MS.modality_seed, rolling=False):
     """The device loop of generate. Every GENERATED modality i of the plan is sampled per step from its own head, all
     of them in one mmt_sample_multi launch, with the seed seed_of(seed, i); GIVEN modalities follow the caller's
     tokens; HELD ones stay at their last prompt token. The sequences live in preallocated [rows, n0 + N] buffers,
     given columns and held pads are written once before the loop (what the reference's pad / crop rule amounts to
     for prompts of one length), the sampler writes column n of a generated modality's buffer and the compact [rows]
     token buffer the next decode step reads (DecodeArgs). Per token the host asks the logits source for the step's
-    views (CachedSource; with num_samples where fans_out holds, FanoutSource over B*S rows, else the tiled prompts)
+    views (CachedSource; with num_samples where fans_out holds, FanoutSource over B*S rows, where rolls holds (`rolling`,
+    a call that leaves the block) RollingSource, else the tiled prompts)
     and runs the stages: no torch op, no sync. The draw of row r at sequence position n is keyed by (seed_of(seed,
     i), r, n): the same seed and the same logits give the same tokens whatever the cache mode and whatever else is in
     the batch. seed=None takes one from the device generator (never torch's CPU generator). `logits_hook(n, views)`
@@ -424,20 +490,26 @@ def rollout(model, idx_list, plan, use_cache, temperature, top_k, top_p, seed, r
     seed = MS.device_seed(dev) if seed is None else int(seed) & MS.MASK64
     L = ML.lib()
     cache = cache_rule(model, use_cache)
-    fan = fans_out(cache, [tuple(s.shape) for s in idx_list], N, S, T)
+    shapes = [tuple(s.shape) for s in idx_list]
+    fan = fans_out(cache, shapes, N, S, T)
+    roll = not fan and rolls(cache, shapes, N, S, T, rolling)
     nbytes = L.mmt_fanout_bytes(model._ctx, plan.B, S, N) if fan else 0
-    if nbytes < 0:
+    roll_bytes = 0
+    if roll:  # the fan buffer of the positions left in the block, the roll buffer of the longest tail (N - 1 rows)
+        nbytes = L.mmt_fanout_bytes(model._ctx, plan.B, S, T - n0) if n0 < T else 0
+        roll_bytes = L.mmt_rolling_bytes(model._ctx, plan.B, S, N - 1)
+    if nbytes < 0 or roll_bytes < 0:
         raise ValueError(f"generate: {plan.B} prompts x {S} samples are more rows than the decode launches address")
     if plan.evidence == "resample" and not (fan and S <= MS.RESAMPLE_MAX_SAMPLES):
         raise ValueError(
             "generate: evidence=\"resample\" runs on the fan-out engine only: it needs num_samples (at most "
             f"{MS.RESAMPLE_MAX_SAMPLES}), use_cache, eval mode or no dropout, precision bf16, max_new_tokens >= 1 and "
-            "n0 + max_new_tokens <= block_size")
+            "n0 + max_new_tokens <= block_size (rolling= does not lift that for it)")
     if plan.evidence is not None and S is not None and S > MS.RESAMPLE_MAX_SAMPLES:
         raise ValueError(f"generate: evidence= folds the weights of at most {MS.RESAMPLE_MAX_SAMPLES} samples per "
                          f"prompt, got num_samples={S}")
     if S is not None:
-        model.last_generate_path = "fanout" if fan else "tiled"
+        model.last_generate_path = "fanout" if fan else "rolling" if roll else "tiled"
     prompts = [s.to(device=dev, dtype=torch.long).contiguous() for s in idx_list]
     rows = prompts if S is None else tile_prompts(prompts, S)
     R, cap = rows[0].shape[0], n0 + N
@@ -532,9 +604,12 @@ def rollout(model, idx_list, plan, use_cache, temperature, top_k, top_p, seed, r
             st.copy_(st.index_select(1, a))
 
     dec = DecodeArgs(model, R, compact, held, steps)
-    if fan:  # the prefill's first rows: only of the modalities a stage (or the hook) reads
+    if fan or roll:  # the prefill's first rows: only of the modalities a stage (or the hook) reads
         need = range(M) if logits_hook is not None else gen + giv
-        source = FanoutSource(model, prompts, (plan.B, S, n0, N), dec, need, nbytes, bool(plan.points))
+        if fan:
+            source = FanoutSource(model, prompts, (plan.B, S, n0, N), dec, need, nbytes, bool(plan.points))
+        else:
+            source = RollingSource(model, prompts, (plan.B, S, n0, N), dec, need, nbytes, bufs, cap, roll_bytes)
     else:
         source = CachedSource(model, bufs, dec, cache)
     with torch.cuda.device(dev):
@@ -613,18 +688,21 @@ def rollout(model, idx_list, plan, use_cache, temperature, top_k, top_p, seed, r
 
 @torch.no_grad()
 def rollout_int(model, idx_list, max_new_tokens, g, use_cache, temperature, top_k, top_p, seed, return_logprobs,
-                logits_hook, S):
+                logits_hook, S, rolling=False):
     """The int form of generate on the device: the plan with modality g GENERATED and the others HELD, its one
     sampling problem keyed by the raw seed, and the results unwrapped to the int form's shapes (the hook sees the one
     [rows, V_g] view, the log-probabilities are a tensor). With num_samples the fan-out engine runs where fans_out
-    holds; otherwise, invalid input included, the prompts are tiled, which is the definition of the result. Prompts
+    holds, the rolling engine where rolls holds; otherwise, invalid input included, the prompts are tiled, which is the
+    definition of the result. Prompts
     of unequal lengths run the reference's loop (re-forward, pad / crop per step) around mmt_sample."""
     M, N, dev = model.num_modalities, int(max_new_tokens), model.flat_params.device
     if S is not None:
-        fan = (len(idx_list) == M and 0 <= g < M and dev.type == "cuda"
-               and fans_out(cache_rule(model, use_cache), [tuple(s.shape) for s in idx_list], N, S, model.block_size))
-        model.last_generate_path = "fanout" if fan else "tiled"
-        if not fan:
+        path = "tiled"
+        if len(idx_list) == M and 0 <= g < M and dev.type == "cuda":
+            path = generate_path(cache_rule(model, use_cache), [tuple(s.shape) for s in idx_list], N, S,
+                                 model.block_size, rolling)
+        model.last_generate_path = path
+        if path == "tiled":
             idx_list, S = tile_prompts(idx_list, S), None
     t, k, p = MS.check_settings(temperature, top_k, top_p)
     if len(idx_list) != M:
@@ -656,5 +734,5 @@ def rollout_int(model, idx_list, max_new_tokens, g, use_cache, temperature, top_
     plan = JointPlan([GENERATED if i == g else HELD for i in range(M)], [g], {}, int(B), n0, max(N, 0))
     hook = None if logits_hook is None else (lambda n, views: logits_hook(n, views[g]))
     out = rollout(model, idx_list, plan, use_cache, t, k, p, seed, return_logprobs, hook, S,
-                  seed_of=lambda seed, i: seed)
+                  seed_of=lambda seed, i: seed, rolling=rolling)
     return (out[0], out[1][g]) if return_logprobs else out

@@ -498,7 +498,7 @@ class MultimodalTransformer(nn.Module):
     def generate(self, idx_list, max_new_tokens=1, modality_to_generate=0, use_cache=True, sample_fn=None, *,
                  temperature=None, top_k=None, top_p=None, seed=None, return_logprobs=False, logits_hook=None,
                  num_samples=None, given=None, evidence=None, resample_every=1, ess_threshold=0.5, forecast=None,
-                 horizon=None, realised=None):
+                 horizon=None, realised=None, rolling=False):
         """model.py:404-446: per new token, the logits of the last position of the (block_size
         cropped) context, a sample from the softmax of the target modality's last logits
         (torch.multinomial, as the reference; `sample_fn(probs) -> [B, 1]` overrides it), appended;
@@ -526,6 +526,20 @@ class MultimodalTransformer(nn.Module):
         and decode steps over B*S rows that share each prompt's keys / values (mmt_decode_fanout_step). That engine runs with use_cache, in eval mode or without dropout, at bf16, for
         prompts of one length n0 >= 1 with n0 + max_new_tokens <= block_size; otherwise the prompts are tiled and
         the device path runs as without the keyword. `last_generate_path` says which ran: "fanout" or "tiled".
+
+        rolling=True (with num_samples; pass num_samples=1 for one path) lifts the bound n0 + max_new_tokens <=
+        block_size: a forecast from a full context window. Past the block every position shifts, so the tiled call
+        re-runs B*S windows of block_size rows per token. But the first p = block_size - j rows of every path's
+        window at new token j are the prompt's rows, shifted, and the same for all S paths; only the last m = j are
+        the path's own. A rolling step runs one ordinary forward over the B shifted prompts and ONE
+        mmt_rolling_step (include/mmt.h) over the B*S*m own rows: B*p + B*S*m rows through the layers where the tiled
+        step takes B*S*block_size. While the sequence still fits the block the steps are the fan-out engine's. It runs
+        under the fan-out conditions with that bound replaced by n0 <= block_size and max_new_tokens <= block_size;
+        `last_generate_path` is "rolling" when the call leaves the block (n0 + max_new_tokens - 1 > block_size),
+        "fanout" when it stays inside (bit for bit the call without the keyword), and the call falls back to "tiled"
+        otherwise. The logits are those of the tiled re-forward up to rounding, not bit for bit; draws stay keyed by
+        (seed, row, position). Both forms, given=, forecast=, horizon=, realised= and evidence="weights" run
+        unchanged on rolling steps; evidence="resample" still needs the call to stay inside the block.
 
         Joint rollouts: modality_to_generate as a sequence of distinct ints (even of one) or "all" samples each of
         those modalities per step from its own head and feeds them back together (always the
@@ -616,6 +630,9 @@ class MultimodalTransformer(nn.Module):
         realised=."""
         if num_samples is not None:
             num_samples = check_num_samples(num_samples)
+        elif rolling:
+            raise ValueError("generate: rolling=True rolls the num_samples paths of each prompt: pass num_samples "
+                             "(num_samples=1 for one path)")
         plan = plan_joint(modality_to_generate, given, self.vocab_sizes, [tuple(s.shape) for s in idx_list],
                           max_new_tokens, num_samples, evidence, resample_every, ess_threshold, forecast, horizon,
                           realised)
@@ -624,14 +641,14 @@ class MultimodalTransformer(nn.Module):
                 raise ValueError("generate: sample_fn cannot be combined with a joint rollout (a list of modalities "
                                  "or \"all\"): it samples on the GPU")
             return MR.rollout(self, idx_list, plan, use_cache, temperature, top_k, top_p, seed, return_logprobs,
-                              logits_hook, num_samples)
+                              logits_hook, num_samples, rolling=rolling)
         if not (temperature is None and top_k is None and top_p is None and seed is None and not return_logprobs
                 and logits_hook is None and num_samples is None):
             if sample_fn is not None:
                 raise ValueError("generate: sample_fn cannot be combined with temperature / top_k / top_p / seed / "
                                  "return_logprobs / logits_hook / num_samples (the device path samples on the GPU)")
             return MR.rollout_int(self, idx_list, max_new_tokens, modality_to_generate, use_cache, temperature, top_k,
-                                  top_p, seed, return_logprobs, logits_hook, num_samples)
+                                  top_p, seed, return_logprobs, logits_hook, num_samples, rolling)
         sample = sample_fn or (lambda probs: torch.multinomial(probs, num_samples=1))
         return MR.reference_loop(self, [idx.clone() for idx in idx_list], max_new_tokens, modality_to_generate,
                                  use_cache, lambda j, n, last: sample(torch.softmax(last, dim=-1)))
@@ -683,6 +700,34 @@ class MultimodalTransformer(nn.Module):
                                           ML.ptr(self._fan))
         ML.check(rc, self._ctx, "mmt_decode_fanout_step")
         self._keep_decode = idx  # alive until the step's kernels have read them
+        return logits
+
+    @torch.no_grad()
+    def _rolling_step(self, seqs, samples, p, m):
+        """Logits [B*S, V_i] of every modality at position p + m - 1 of the B*S paths (row b*S + s), given the int64
+        [B*S, cap >= p + m] sequences `seqs` whose columns p..p+m-1 are the paths' own tokens; the workspace must
+        hold a forward over the B prompts' first p positions (include/mmt.h mmt_rolling_step)."""
+        flat = self.flat_params
+        dev = flat.device
+        R, cap = seqs[0].shape
+        B = R // samples
+        if self._ws is None or self._ws_batch != B or B * samples != R:
+            raise RuntimeError("_rolling_step: no forward at this batch size")
+        L = ML.lib()
+        nbytes = L.mmt_rolling_bytes(self._ctx, B, samples, m)
+        if nbytes < 0:
+            raise ValueError("_rolling_step: batch, samples or m out of range")
+        roll = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        idx = [t.to(device=dev, dtype=torch.long).contiguous() for t in seqs]
+        tail = ML.ptr_array(idx)
+        for i, t in enumerate(idx):
+            tail[i] = t.data_ptr() + 8 * p
+        logits = [torch.empty(R, V, dtype=torch.float32, device=dev) for V in self.vocab_sizes]
+        with torch.cuda.device(dev):
+            rc = L.mmt_rolling_step(self._ctx, ML.stream_ptr(dev), B, samples, int(p), int(m), tail, cap, ML.ptr(flat),
+                                    ML.ptr_array(logits), ML.ptr(self._ws), ML.ptr(roll))
+        ML.check(rc, self._ctx, "mmt_rolling_step")
+        self._keep_decode = idx + [roll]  # alive until the step's kernels have read them
         return logits
 
     def __del__(self):
