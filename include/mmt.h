@@ -556,6 +556,60 @@ int mmt_eval_positions(void* stream, int32_t count, int32_t batch, int32_t T, in
                        double* const* rec /* nullable, entries nullable */, double* const* pos,
                        double* const* rel, double* const* pit, void* scratch, int64_t scratch_bytes);
 
+/* Calibrated temperatures. Every head is sampled from softmax(logits / temperature); mmt_eval_temperatures scores
+ * the rows mmt_eval_positions scores under K temperatures from one read of each row, and reduces them to what a fit
+ * of the temperature needs: per temperature the summed log score, and the reliability tables of the direction
+ * masses. No context, no knobs.
+ *
+ * `count` problems over the same `batch`, `T`, `t_begin`, `bins`, `accumulate` and the same K temperatures
+ * (`temperatures`: a HOST array of K floats, 1 <= K <= 32, every one finite and > 0, strictly ascending). Per
+ * problem (HOST arrays) V, logits, xb, yb, values and is_percent are mmt_eval_positions' own. Outputs per problem:
+ * rec (device fp64 [batch, T, K, 4]; the array and its entries nullable: the records then live in the scratch),
+ * sum fp64 [K, 2], rel fp64 [K, 3, bins, 3]. scratch: mmt_eval_temperatures_scratch_bytes(count, batch, T, bins, K)
+ * bytes of device memory, 16-byte aligned, its contents unspecified before and after.
+ * Stage 1, the record of row (b, t) and temperature k, t >= t_begin. The law is mmt_sample's at temperature
+ * temperatures[k], top_k 0, top_p 1, by the sampler's own device functions: inv_t = 1.0f / temperatures[k] (one
+ * fp32 division on the host); z_i = logit_i * inv_t (one fp32 multiply), NaN as -inf; m = max z (the scaled maximum
+ * of the raw row: inv_t > 0 and rounding is monotone); e_i = expf(z_i - m), 1 at the maximum; S the fp64 sum of the
+ * e_i over the sampler's tree (mmt_eval_positions, stage 1). A mass is the sum over that tree of the e_i of a
+ * direction class (the other leaves zeroed), divided by S once; the classes are mmt_eval_positions'.
+ *   rec[0] the log-probability of yb: (z_yb - m) - log S rounded to fp32 once, widened; -inf where z_yb is -inf
+ *   rec[1..3] p_down, p_flat, p_up; NaN without values
+ * So at temperatures[k] == 1.0f the four fields are bit for bit mmt_eval_positions' rec[0..3], and for any
+ * temperature rec[0] is bit for bit the log-probability mmt_sample writes when it draws yb at that temperature,
+ * and what mmt_score_multi gives on logits * inv_t. A row is dead where mmt_eval_positions calls it dead (no finite
+ * logit, or xb or yb outside 0..V-1, neither then used as an index), for every k alike: its K x 4 fields are NaN.
+ * Records of rows with t < t_begin are not written.
+ * Stage 2, the tables, a function of the records and of the realised sign (that of yb, mmt_eval_positions'
+ * rec[7], taken again from values, xb and yb). A row is live when rec[0] is not NaN and has a direction when
+ * rec[1] is not NaN. Every sum is serial in fp64 from 0; counts are therefore exact.
+ *   sum[k, 0] live rows                 sum[k, 1] the sum of -rec[0]
+ *   rel[k, d, j, 0..2], d = 0, 1, 2 for down, flat, up: a row with a direction enters bin
+ *     j = min(bins - 1, floor(P_d * bins)), P_d = rec[1 + d]; the cell holds the count, the sum of P_d, and the
+ *     number of rows whose realised sign is d - 1
+ * A cell is the sum over t = t_begin..T-1 ascending of the position's own sum over b ascending. accumulate == 0
+ * writes the tables; otherwise each cell is added, with one fp64 addition, to what the buffer holds. No float
+ * atomics: a launch is bit-identical run to run, and a problem gives in company the bits it gives alone. Nothing
+ * outside the named buffers is written.
+ * Launches, per chunk of 8 problems: one over (batch (T - t_begin), problems) for the records (a second one for the
+ * problems with V > 8192, the sampler's re-read variant), one over (T - t_begin, K, problems) for the positions, one
+ * over (ceil(K (2 + 9 bins) / 256), problems) for the cells.
+ * MMT_ERR_INVALID before any launch, nothing written: what mmt_eval_positions refuses (count, batch or T negative;
+ * t_begin outside 0..T; bins outside 1..64; batch * T >= 2^31; with count > 0 a null V / logits / xb / yb / sum /
+ * rel array; V < 1; with batch > 0 and t_begin < T a null logits / xb / yb / sum / rel entry; with batch > 0 a null,
+ * misaligned or undersized scratch); K outside 1..32; a null temperatures; a temperature that is not finite, not
+ * > 0 or not above its predecessor. MMT_ERR_UNSUPPORTED for V > 2^20. count == 0, batch == 0 and t_begin == T
+ * launch nothing and write nothing. mmt_eval_temperatures_scratch_bytes returns -1 for arguments the entry
+ * refuses. */
+int64_t mmt_eval_temperatures_scratch_bytes(int32_t count, int32_t batch, int32_t T, int32_t bins, int32_t K);
+int mmt_eval_temperatures(void* stream, int32_t count, int32_t batch, int32_t T, int32_t t_begin, int32_t bins,
+                          int32_t accumulate, int32_t K, const float* temperatures, const int32_t* V,
+                          const float* const* logits, const int64_t* const* xb, const int64_t* const* yb,
+                          const double* const* values /* nullable, entries nullable */,
+                          const int32_t* is_percent /* nullable */,
+                          double* const* rec /* nullable, entries nullable */, double* const* sum,
+                          double* const* rel, void* scratch, int64_t scratch_bytes);
+
 /* failure detection (the reference's guard is the NaN check on eval losses,
  * main.py:606): byte offset in the workspace of two int32 bitmasks (the same for every batch size;
  * the query never touches the workspace plan of a pending backward or decode). The

@@ -23,7 +23,9 @@ _DEFAULTS = {
                             # build-only keys: evaluation at every position (mmt_eval.PositionMetrics in estimate_loss)
                             "eval_positions": "last", "eval_positions_from": 0,
                             # build-only keys: scored rollouts (mmt_eval.RolloutMetrics in estimate_loss); 0 paths: off
-                            "eval_rollout_paths": 0, "eval_rollout_steps": 16, "eval_rollout_seed": 0},
+                            "eval_rollout_paths": 0, "eval_rollout_steps": 16, "eval_rollout_seed": 0,
+                            # build-only key: fit each head's temperature (mmt_eval.TemperatureFit in estimate_loss)
+                            "eval_temperature": "off"},
     "model_architecture": {"n_embd": 384, "n_head": 6, "n_layer": 6, "dropout": 0.2,
                            "fixed_values": [-0.5, -0.2, -0.1, 0, 0.1, 0.2, 0.5],
                            # build-only key (the reference ignores unknown keys): "bf16" | "fp8"
@@ -185,6 +187,19 @@ def _get_eval_positions_from():
     v = _get_config().get("eval_positions_from", 0)
     if isinstance(v, bool) or not isinstance(v, int) or v < 0 or v > _get_block_size():
         raise ValueError(f"eval_positions_from must be an integer in 0..block_size, got {v!r}")
+    return v
+
+
+def _get_eval_temperature():
+    """Build-only knob: "off" (default, also when the key is absent): nothing runs. "fit": estimate_loss also hands
+    every iteration's logits to a mmt_eval.TemperatureFit, prints the fitted temperature of each scored head and,
+    after the val state, stores it in the model for generate(temperature="calibrated"). Independent of
+    eval_positions (it only shares eval_positions_from)."""
+    v = _get_config().get("eval_temperature", "off")
+    if v is False:  # YAML reads a bare `off` as a boolean
+        return "off"
+    if not isinstance(v, str) or v not in ("off", "fit"):
+        raise ValueError(f"eval_temperature must be 'off' or 'fit', got {v!r}")
     return v
 
 

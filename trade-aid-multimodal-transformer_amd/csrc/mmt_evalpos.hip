@@ -19,6 +19,7 @@
 // not depend on its company: a workgroup reads its own problem and nothing else.
 #include "mmt.h"
 #include "mmt_common.h"
+#include "mmt_eval_dev.h"
 #include "mmt_kernels.h"
 #include "mmt_sample_dev.h"
 
@@ -35,14 +36,6 @@ struct EvalShared {
   int cnt[SAMPLE_WAVES];
   int first[SAMPLE_WAVES];
 };
-
-__device__ __forceinline__ double ev_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
-
-// the reference's _get_direction_sign: of the value itself (percent) or of value - value[xb]
-__device__ __forceinline__ int ev_sign(double v, double vo, int pct) {
-  const double ch = pct ? v : v - vo;
-  return ch > 0.0 ? 1 : (ch < 0.0 ? -1 : 0);
-}
 
 template <bool ONCHIP>
 __global__ __launch_bounds__(SAMPLE_THREADS) void evalpos_record_kernel(EvalPosBatch batch, int T, int t_begin) {
@@ -121,11 +114,6 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void evalpos_record_kernel(EvalPosB
   out[5] = (double)cnt;
   out[6] = val ? (double)ev_sign(val[first], vo, pct) : ev_nan();
   out[7] = val ? (double)ev_sign(val[y], vo, pct) : ev_nan();
-}
-
-__device__ __forceinline__ int ev_bin(double p, int bins) {
-  const int k = (int)floor(p * (double)bins);
-  return k < bins - 1 ? k : bins - 1;
 }
 
 // what one record gives one cell of its position's partial table; 0 where it gives nothing

@@ -440,6 +440,26 @@ hipError_t mmt_launch_evalpos_records(const EvalPosBatch& b, int n, bool onchip,
 hipError_t mmt_launch_evalpos_tables(const EvalPosBatch& b, int n, int batch, int T, int t_begin, int bins,
                                      int accumulate, hipStream_t s);
 
+// Temperature sweep of the evaluation logits (mmt_eval_temperatures, mmt_evaltemp.hip). Row r = b * T + t, K
+// temperatures, a record of 4 fp64 per (row, k). The launchers validate nothing: the C entry does. `rec` is the
+// caller's record buffer or the problem's place in the scratch, `part` the problem's per-position partial tables
+// [T][K][2 + 9 bins] in the scratch.
+constexpr int MMT_ET_MAX_K = 32;
+struct EvalTempProblem {
+  const float* logits;                                            // [batch, T, V]
+  const int64_t* xb; const int64_t* yb;                           // [batch, T]
+  const double* values;                                           // nullable
+  double* rec; double* sum; double* rel; double* part;
+  int V, is_percent;
+};
+struct EvalTempBatch { EvalTempProblem p[MMT_MAX_GROUP]; float inv_t[MMT_ET_MAX_K]; int K; };
+// the records of n problems of one kind (onchip: every V <= 8192), grid (batch * (T - t_begin), n)
+hipError_t mmt_launch_evaltemp_records(const EvalTempBatch& b, int n, bool onchip, int batch, int T, int t_begin,
+                                       hipStream_t s);
+// the tables from the records: positions, grid (T - t_begin, K, n), then the cells, grid (ceil(cells / 256), n)
+hipError_t mmt_launch_evaltemp_tables(const EvalTempBatch& b, int n, int batch, int T, int t_begin, int bins,
+                                      int accumulate, hipStream_t s);
+
 // ------------------------------------------------------------------------------------------
 // Per-head Q/K/V stage 2: block-diagonal [hs/2 -> hs] maps (model.py:39,44,49), nblk = 3*H.
 //   out[r, blk*hs + o] = sum_i W2[blk][o][i] * h1[r, blk*hs/2 + i]

@@ -5,6 +5,13 @@ heads over all B x T rows an evaluation forward has written, not only the last p
     PositionMetrics(values, is_percent, ...).add(...) / .result() / .summary_lines(names)
                                                                                tables accumulated over many batches
 
+Calibrated temperatures (include/mmt.h: mmt_eval_temperatures): the same rows under a grid of temperatures, the
+temperature that minimises the NLL:
+
+    temperature_metrics(logits_list, xb_list, yb_list, values, is_percent, temperatures=None, ...)
+    TemperatureFit(values, is_percent, temperatures=None, ...).add(...) / .result() / .summary_lines(names)
+    fit_temperature(temperatures, rows, nll_sum) / derive_temperature(sum, rel, temperatures)      host fp64
+
 Scores of horizon forecasts against the realised series (include/mmt.h: mmt_horizon_score), accumulated the same way:
 
     RolloutMetrics().add(scores) / .result() / .summary_lines(names)            scores: what generate(realised=) returns
@@ -278,6 +285,242 @@ class PositionMetrics:
         if len(names) != len(res):
             raise ValueError(f"PositionMetrics.summary_lines: name must hold {len(res)} names, got {len(names)}")
         return [f"  - {n:<30}{summary_text(r)}" for n, r in zip(names, res)]
+
+
+# ------------------------------------------------------------------------------------------
+# Calibrated temperatures (mmt_eval_temperatures): NLL and reliability on a grid of temperatures, the fit
+# ------------------------------------------------------------------------------------------
+MAX_TEMPERATURES = 32
+TEMP_REC_FIELDS = ("logprob", "p_down", "p_flat", "p_up")  # rec[b, t, k, f]
+
+
+def default_temperatures():
+    """The default grid: the 17 fp32 values 2^((k - 8) / 4), k = 0..16 (0.25 .. 4, 1.0 exactly at k = 8)."""
+    return np.array([2.0 ** ((k - 8) / 4.0) for k in range(17)], dtype=np.float32)
+
+
+def _check_temperatures(temperatures):
+    """The grid as an fp32 numpy array: 1..32 finite values > 0, strictly ascending (as fp32)."""
+    t = default_temperatures() if temperatures is None else np.asarray(temperatures)
+    if t.ndim != 1 or not 1 <= t.size <= MAX_TEMPERATURES or t.dtype.kind not in "fiu":
+        raise ValueError(f"temperature_metrics: temperatures must hold 1..{MAX_TEMPERATURES} numbers")
+    with np.errstate(all="ignore"):
+        t = t.astype(np.float32)
+    if not (np.isfinite(t).all() and (t > 0).all() and (np.diff(t) > 0).all()):
+        raise ValueError("temperature_metrics: temperatures must be finite, > 0 and strictly ascending in fp32")
+    return t
+
+
+class TempLaunch:
+    """The host arrays of mmt_eval_temperatures over P problems (raw addresses; values / rec 0 = absent), made once."""
+
+    def __init__(self, V, is_percent, temperatures):
+        P = self.P = len(V)
+        n = max(1, P)
+        self.K = len(temperatures)
+        self.temperatures = (ctypes.c_float * self.K)(*[float(t) for t in temperatures])
+        self.V = (ctypes.c_int32 * n)(*[int(v) for v in V])
+        self.is_percent = (ctypes.c_int32 * n)(*[1 if x else 0 for x in is_percent])
+        self.logits, self.xb, self.yb, self.values, self.rec, self.sum, self.rel = (
+            (ctypes.c_void_p * n)() for _ in range(7))
+
+    def scratch_bytes(self, L, batch, T, bins):
+        n = L.mmt_eval_temperatures_scratch_bytes(self.P, int(batch), int(T), int(bins), self.K)
+        if n < 0:
+            raise ValueError(f"temperature_metrics: {batch} x {T} rows with {bins} bins is a shape the entry refuses")
+        return int(n)
+
+    def run(self, L, stream, batch, T, t_begin, bins, accumulate, scratch_ptr, scratch_bytes):
+        rc = L.mmt_eval_temperatures(stream, self.P, batch, T, t_begin, bins, 1 if accumulate else 0, self.K,
+                                     self.temperatures, self.V, self.logits, self.xb, self.yb, self.values,
+                                     self.is_percent, self.rec, self.sum, self.rel, scratch_ptr, scratch_bytes)
+        if rc != 0:
+            raise ML.MmtError(f"mmt_eval_temperatures failed (status {rc})")
+
+
+def _temp_views(flat, P, K, bins):
+    """The tables of P problems as views of one flat fp64 buffer: per problem sum [K, 2], rel [K, 3, bins, 3]."""
+    each = K * (2 + 9 * bins)
+    return [(flat[p * each:p * each + 2 * K].view(K, 2), flat[p * each + 2 * K:(p + 1) * each].view(K, 3, bins, 3))
+            for p in range(P)]
+
+
+def temperature_metrics(logits_list, xb_list, yb_list, values, is_percent, temperatures=None, t_begin=0, bins=10,
+                        records=False):
+    """One mmt_eval_temperatures call over P modalities; the inputs are position_metrics' (and checked as there),
+    temperatures 1..32 finite values > 0, strictly ascending (default: default_temperatures()). Returns a list of P
+    dicts of device tensors: "sum" fp64 [K, 2] (per temperature: live rows, the sum of -log p of the token that came),
+    "rel" fp64 [K, 3, bins, 3] (per temperature, direction and bin: count, sum of the probability, realised), and
+    with records=True "rec" fp64 [B, T, K, 4] (TEMP_REC_FIELDS; rows before t_begin hold NaN)."""
+    temps = _check_temperatures(temperatures)
+    _check_settings(t_begin, bins)
+    dev, B, T, Vs = _check_inputs(logits_list, xb_list, yb_list, values, is_percent, token_range=True)
+    _check_settings(t_begin, bins, T)
+    P, K = len(Vs), len(temps)
+    if P == 0:
+        return []
+    flat = torch.zeros(P * K * (2 + 9 * bins), dtype=torch.float64, device=dev)  # zeros: B == 0 launches nothing
+    views = _temp_views(flat, P, K, bins)
+    tl = TempLaunch(Vs, is_percent, temps)
+    recs = [torch.full((B, T, K, 4), float("nan"), dtype=torch.float64, device=dev) if records else None
+            for _ in range(P)]
+    for p in range(P):
+        tl.logits[p], tl.xb[p], tl.yb[p] = logits_list[p].data_ptr(), xb_list[p].data_ptr(), yb_list[p].data_ptr()
+        tl.values[p] = values[p].data_ptr() if values[p] is not None else None
+        tl.rec[p] = recs[p].data_ptr() if records and recs[p].numel() else None
+        tl.sum[p], tl.rel[p] = (x.data_ptr() for x in views[p])
+    L = ML.lib()
+    nbytes = tl.scratch_bytes(L, B, T, bins)
+    scratch = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        tl.run(L, ML.stream_ptr(dev), B, T, t_begin, bins, False, scratch.data_ptr(), nbytes)
+    out = []
+    for p in range(P):
+        d = {"sum": views[p][0], "rel": views[p][1]}
+        if records:
+            d["rec"] = recs[p]
+        out.append(d)
+    return out
+
+
+def fit_temperature(temperatures, rows, nll_sum):
+    """The temperature that minimises the mean NLL measured on a grid, in host fp64: (tau, k_star, at_bound).
+    mean_k = nll_sum[k] / rows, a non-finite mean counting as +inf; no rows or no finite mean: (nan, -1, True). k* is
+    the lowest index of the minimum. K == 1 or k* at either end of the grid: (tau_k*, k*, True): the minimum may lie
+    outside. A neighbour without a finite mean: (tau_k*, k*, False). Otherwise the vertex of the parabola through
+    (ln tau, mean) at k* - 1, k*, k* + 1 (NLL is convex in 1 / tau and smooth in ln tau); ln tau_k* instead when the
+    denominator is 0 or the vertex is not finite or leaves [ln tau_{k*-1}, ln tau_{k*+1}]."""
+    tau = [float(t) for t in temperatures]
+    K = len(tau)
+    rows = float(rows)
+    if not rows > 0:
+        return float("nan"), -1, True
+    with np.errstate(all="ignore"):
+        mean = [float(s) / rows for s in nll_sum]
+    mean = [m if np.isfinite(m) else float("inf") for m in mean]
+    if not any(np.isfinite(m) for m in mean):
+        return float("nan"), -1, True
+    ks = min(range(K), key=lambda k: (mean[k], k))
+    if K == 1 or ks == 0 or ks == K - 1:
+        return tau[ks], ks, True
+    if not (np.isfinite(mean[ks - 1]) and np.isfinite(mean[ks + 1])):
+        return tau[ks], ks, False
+    x0, x1, x2 = (float(np.log(tau[k])) for k in (ks - 1, ks, ks + 1))
+    y0, y1, y2 = mean[ks - 1], mean[ks], mean[ks + 1]
+    den = (x1 - x0) * (y1 - y2) - (x1 - x2) * (y1 - y0)
+    xs = x1
+    if den != 0.0:
+        with np.errstate(all="ignore"):
+            v = x1 - 0.5 * ((x1 - x0) ** 2 * (y1 - y2) - (x1 - x2) ** 2 * (y1 - y0)) / den
+        if np.isfinite(v) and x0 <= v <= x2:
+            xs = float(v)
+    return float(np.exp(xs)), ks, False
+
+
+def derive_temperature(sum, rel, temperatures):
+    """The numbers of one modality from its tables (numpy fp64: sum [K, 2], rel [K, 3, bins, 3]). Returns a dict: the
+    tables and the grid; rows; nll [K] (the mean per temperature, NaN without rows); ece {direction: [K]} (`derive`'s
+    formula per temperature); tau, k_star, at_bound (`fit_temperature`); k_one (the index of the grid point equal to
+    1.0, None if absent)."""
+    sum, rel = np.asarray(sum, np.float64), np.asarray(rel, np.float64)
+    temps = np.asarray(temperatures, np.float32)
+    K = len(temps)
+    rows = float(sum[0, 0]) if K else 0.0
+    nll = np.array([_ratio(sum[k, 1], sum[k, 0]) for k in range(K)])
+    ece = {name: np.array([_ratio(np.abs(rel[k, d, :, 1] - rel[k, d, :, 2]).sum(), rel[k, d, :, 0].sum())
+                           for k in range(K)]) for d, name in enumerate(DIRECTIONS)}
+    tau, ks, at_bound = fit_temperature(temps, rows, sum[:, 1])
+    one = np.nonzero(temps == np.float32(1.0))[0]
+    return {"sum": sum, "rel": rel, "temperatures": temps, "rows": int(rows), "nll": nll, "ece": ece, "tau": tau,
+            "k_star": ks, "at_bound": at_bound, "k_one": int(one[0]) if len(one) else None}
+
+
+def temperature_summary_text(r):
+    """One modality's line, without its name: the fitted temperature (marked when the minimum sits on the grid's
+    edge), then NLL and the ECE of p_up / p_down at temperature 1 -> at the grid point of the minimum."""
+    if r["k_star"] < 0:
+        return "no fit (no scored row)"
+
+    def pair(a):
+        f = lambda k: "n/a" if k is None or a[k] != a[k] else f"{a[k]:.4f}"
+        return f"{f(r['k_one'])} -> {f(r['k_star'])}"
+
+    mark = " (at the grid's edge)" if r["at_bound"] else ""
+    return (f"tau* {r['tau']:.4f}{mark} | NLL {pair(r['nll'])} | ECE up {pair(r['ece']['up'])} "
+            f"down {pair(r['ece']['down'])}")
+
+
+class TemperatureFit:
+    """The tables of mmt_eval_temperatures accumulated on the device over many evaluation batches. values, is_percent
+    as PositionMetrics'; temperatures as temperature_metrics'. `add` checks its inputs on the host (not the tokens'
+    range), launches with accumulate = 1 and does not sync; the first `add` fixes B, T and the V_p. `result` is one
+    device-to-host read."""
+
+    def __init__(self, values, is_percent, temperatures=None, t_begin=0, bins=10):
+        _check_settings(t_begin, bins)
+        if not isinstance(values, (list, tuple)) or not isinstance(is_percent, (list, tuple)) or (
+                len(values) != len(is_percent)):
+            raise ValueError("TemperatureFit: values and is_percent must be lists of one length")
+        self._temps = _check_temperatures(temperatures)
+        self.values, self.is_percent = list(values), [bool(x) for x in is_percent]
+        self.t_begin, self.bins = t_begin, bins
+        self.P = len(self.values)
+        self.batches = 0
+        self._shape = None
+
+    def temperatures(self):
+        """The grid, fp32 numpy [K]."""
+        return self._temps.copy()
+
+    def _setup(self, dev, B, T, Vs):
+        _check_settings(self.t_begin, self.bins, T)
+        self._shape = (dev, B, T, tuple(Vs))
+        K = len(self._temps)
+        self._flat = torch.zeros(self.P * K * (2 + 9 * self.bins), dtype=torch.float64, device=dev)
+        self._views = _temp_views(self._flat, self.P, K, self.bins)
+        self._launch = tl = TempLaunch(Vs, self.is_percent, self._temps)
+        for p in range(self.P):
+            tl.values[p] = self.values[p].data_ptr() if self.values[p] is not None else None
+            tl.sum[p], tl.rel[p] = (x.data_ptr() for x in self._views[p])
+        self._lib = ML.lib()
+        self._nbytes = tl.scratch_bytes(self._lib, B, T, self.bins)
+        self._scratch = torch.empty(max(self._nbytes, 16), dtype=torch.uint8, device=dev)
+
+    def add(self, logits_list, xb_list, yb_list):
+        if len(logits_list) != self.P:
+            raise ValueError(f"TemperatureFit.add: logits_list must hold {self.P} tensors")
+        dev, B, T, Vs = _check_inputs(logits_list, xb_list, yb_list, self.values, self.is_percent, token_range=False)
+        if self.P == 0:
+            return
+        if self._shape is None:
+            self._setup(dev, B, T, Vs)
+        elif self._shape != (dev, B, T, tuple(Vs)):
+            raise ValueError(f"TemperatureFit.add: logits_list does not match the first batch's device and shapes "
+                             f"(B {self._shape[1]}, T {self._shape[2]}, V {list(self._shape[3])})")
+        tl = self._launch
+        for p in range(self.P):
+            tl.logits[p], tl.xb[p], tl.yb[p] = logits_list[p].data_ptr(), xb_list[p].data_ptr(), yb_list[p].data_ptr()
+        with torch.cuda.device(dev):
+            tl.run(self._lib, ML.stream_ptr(dev), B, T, self.t_begin, self.bins, True, self._scratch.data_ptr(),
+                   self._nbytes)
+        self.batches += 1
+
+    def result(self):
+        """A list of P dicts (`derive_temperature`), from one device-to-host read of all tables. Before any `add`:
+        []."""
+        if self._shape is None:
+            return []
+        host = self._flat.cpu()
+        return [derive_temperature(s.numpy(), r.numpy(), self._temps)
+                for s, r in _temp_views(host, self.P, len(self._temps), self.bins)]
+
+    def summary_lines(self, name, result=None):
+        """The lines to print, one per modality: `name` is a list of P names (or one string when P == 1)."""
+        names = [name] if isinstance(name, str) else list(name)
+        res = self.result() if result is None else result
+        if len(names) != len(res):
+            raise ValueError(f"TemperatureFit.summary_lines: name must hold {len(res)} names, got {len(names)}")
+        return [f"  - {n:<30}{temperature_summary_text(r)}" for n, r in zip(names, res)]
 
 
 # ------------------------------------------------------------------------------------------

@@ -156,6 +156,11 @@ _SIGS = {
                                    ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), ctypes.POINTER(c_vp),
                                    ctypes.POINTER(c_vp), ctypes.POINTER(c_i32), ctypes.POINTER(c_vp),
                                    ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp, c_i64]),
+    "mmt_eval_temperatures_scratch_bytes": (c_i64, [c_i32, c_i32, c_i32, c_i32, c_i32]),
+    "mmt_eval_temperatures": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(c_f32),
+                                      ctypes.POINTER(c_i32), ctypes.POINTER(c_vp), ctypes.POINTER(c_vp),
+                                      ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), ctypes.POINTER(c_i32),
+                                      ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp, c_i64]),
     "mmt_fanout_gather": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "mmt_backward_stage_count": (c_i32, [c_vp]),
     "mmt_backward_stage_range": (c_i32, [c_vp, c_i32, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),

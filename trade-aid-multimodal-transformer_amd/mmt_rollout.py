@@ -12,6 +12,8 @@ shared rows and one mmt_rolling_step over each path's own). The int form of gene
 the raw seed (`rollout_int`). `reference_loop` is the reference's per-token loop with the choice of the next token
 passed in: torch.multinomial / sample_fn for the default path, mmt_sample for device calls with prompts of unequal
 lengths."""
+import numbers
+
 import torch
 
 import mmt_lib as ML
@@ -26,6 +28,58 @@ def check_num_samples(num_samples):
     if isinstance(num_samples, bool) or not isinstance(num_samples, int) or num_samples < 1:
         raise ValueError(f"generate: num_samples must be an integer >= 1 or None, got {num_samples!r}")
     return num_samples
+
+
+CALIBRATED = "calibrated"
+
+
+def check_calibrated_temperatures(mapping, num_modalities):
+    """set_calibrated_temperatures' argument as a fresh {modality: float}: None clears ({}); otherwise a dict whose
+    keys are ints 0..M - 1 and whose values are finite numbers > 0."""
+    if mapping is None:
+        return {}
+    if not isinstance(mapping, dict):
+        raise ValueError("set_calibrated_temperatures: pass {modality: temperature} or None")
+    out = {}
+    for i, tau in mapping.items():
+        if isinstance(i, bool) or not isinstance(i, int) or not 0 <= i < num_modalities:
+            raise ValueError(f"set_calibrated_temperatures: {i!r} is no modality; modalities are the ints "
+                             f"0..{num_modalities - 1}")
+        if isinstance(tau, bool) or not isinstance(tau, numbers.Real) or not 0.0 < float(tau) < float("inf"):
+            raise ValueError(f"set_calibrated_temperatures: the temperature of modality {i} must be a finite number "
+                             f"> 0, got {tau!r}")
+        out[i] = float(tau)
+    return out
+
+
+def resolve_calibrated(temperature, stored, modality_to_generate, num_modalities):
+    """generate's temperature="calibrated" as the numbers it stands for, from `stored` ({modality: tau}, what
+    set_calibrated_temperatures holds): the stored tau in the int form, {modality: tau} over the generated modalities
+    in the list form. ValueError names the first generated modality without a stored value. Any other temperature,
+    and a modality_to_generate that plan_joint will refuse anyway, pass through unchanged."""
+    if not (isinstance(temperature, str) and temperature == CALIBRATED):
+        return temperature
+    g = modality_to_generate
+    if isinstance(g, bool):
+        return temperature
+    if isinstance(g, int):
+        gen, as_int = [g], True
+    elif isinstance(g, str):
+        if g != "all":
+            return temperature
+        gen, as_int = list(range(num_modalities)), False
+    else:
+        try:
+            gen, as_int = list(g), False
+        except TypeError:
+            return temperature
+        if any(isinstance(i, bool) or not isinstance(i, int) for i in gen):
+            return temperature
+    for i in gen:
+        if i not in stored:
+            raise ValueError(f"generate: temperature=\"calibrated\" but modality {i} has no calibrated temperature "
+                             "(estimate_loss with eval_temperature: fit, or set_calibrated_temperatures, stores one)")
+    return stored[gen[0]] if as_int else {i: stored[i] for i in gen}
 
 
 def tile_prompts(idx_list, num_samples):

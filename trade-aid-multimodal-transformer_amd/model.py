@@ -129,12 +129,20 @@ class MultimodalTransformer(nn.Module):
         self._ws_bytes = {}
         self._fan = None  # the fan buffer of _decode_fanout_step
         self.last_generate_path = None  # generate(num_samples=...): "fanout" or "tiled", whichever ran last
+        self.calibrated_temperatures = {}  # set_calibrated_temperatures: what temperature="calibrated" stands for
         self._gen = 0
         self._last = None
         self._grad_sync = None  # mmt_dist.GradSync when data parallel
         self.grad_accumulation = False  # set_grad_accumulation: the backward writes into flat_params.grad in place
         self._grad_buf = None  # the in-place mode's persistent gradient buffer (becomes .grad when .grad is None)
         self._no_sync = False  # inside no_sync(): no gradient exchange
+
+    def set_calibrated_temperatures(self, mapping):
+        """The per-head temperatures generate(temperature="calibrated") stands for: {modality: tau}, ints 0..M - 1
+        and finite tau > 0 (ValueError otherwise); None clears them. estimate_loss with eval_temperature: fit stores
+        the val fit here. A plain attribute (`calibrated_temperatures`): no parameter, no buffer, not in
+        state_dict."""
+        self.calibrated_temperatures = MR.check_calibrated_temperatures(mapping, self.num_modalities)
 
     def set_deterministic(self, on):
         """Deterministic training mode (include/mmt.h, mmt_set_deterministic): bit-identical gradients
@@ -627,7 +635,15 @@ class MultimodalTransformer(nn.Module):
         vocabulary, or that has no live path, has NaN scores and enters no table. Refused (ValueError) without
         horizon=, in the int form, for a key that is not a generated modality with values and for a tensor that is
         not int64 [B, N]. Sequences, log-probabilities, `ev`, `fc` and `hz` are bit-identical to the call without
-        realised=."""
+        realised=.
+
+        temperature="calibrated" stands for the temperatures set_calibrated_temperatures holds (estimate_loss with
+        eval_temperature: fit stores the val fit): the stored number in the int form, {modality: tau} over the
+        generated modalities in the list form, resolved before anything else, so the call IS the call with those
+        numbers, bit for bit on every engine. ValueError names the first generated modality without one."""
+        if isinstance(temperature, str):
+            temperature = MR.resolve_calibrated(temperature, self.calibrated_temperatures, modality_to_generate,
+                                                self.num_modalities)
         if num_samples is not None:
             num_samples = check_num_samples(num_samples)
         elif rolling:

@@ -32,7 +32,11 @@ lines and log lines. What changed underneath:
   * estimate_loss with the build-only key eval_rollout_paths > 0 also rolls that many paths from the first
     block_size - eval_rollout_steps tokens of every evaluation window and scores the horizon forecast against the
     window's own tail (generate(realised=), mmt_eval.RolloutMetrics: CRPS skill, quantile coverage, direction) and
-    prints one more block; with the default, 0, nothing of that is imported or run.
+    prints one more block; with the default, 0, nothing of that is imported or run;
+  * estimate_loss with the build-only key eval_temperature: fit also scores the logits it has under a grid of
+    temperatures (mmt_eval.TemperatureFit), prints each head's fitted temperature and, after the val state, stores
+    it in the model for generate(temperature="calibrated"); with the default, off, nothing of that is imported or
+    run.
 """
 import ctypes
 import math
@@ -47,6 +51,7 @@ import torch
 import mmt_lib as ML
 from config_utils import (_get_batch_size, _get_block_size, _get_config, _get_device, _get_eval_iters,
                           _get_eval_positions, _get_eval_positions_from, _get_eval_rollout_paths,
+                          _get_eval_temperature,
                           _get_eval_rollout_seed, _get_eval_rollout_steps)
 
 __all__ = ["generate_batch_starting_indices", "get_batch", "estimate_loss", "calculate_evaluation_metrics"]
@@ -534,10 +539,9 @@ def calculate_evaluation_metrics(logits_list, xb_list, yb_list, num_modalities, 
 last_position_metrics = {}  # eval_positions: all. Per state the tables and numbers of the latest estimate_loss
 
 
-def _new_position_metrics(logits_list, yb_list):
-    """eval_positions: all. A PositionMetrics over the modalities calculate_evaluation_metrics scores (a numeric
-    vocabulary, a window long enough), made at the first batch of a state. Returns (metrics, indices, names)."""
-    import mmt_eval
+def _scored_modalities(logits_list, yb_list):
+    """The modalities calculate_evaluation_metrics scores (a numeric vocabulary, a window long enough): (indices,
+    values, is_percent, names)."""
     idx, values, pct, names = [], [], [], []
     for i in range(num_modalities):
         if not (len(logits_list) > i and len(yb_list) > i):
@@ -550,8 +554,28 @@ def _new_position_metrics(logits_list, yb_list):
         values.append(vt)
         pct.append(is_pct)
         names.append(all_modality_params[i][9] if all_modality_params[i][9] else f"Modality {i+1}")
+    return idx, values, pct, names
+
+
+def _new_position_metrics(logits_list, yb_list):
+    """eval_positions: all. A PositionMetrics over the scored modalities, made at the first batch of a state. Returns
+    (metrics, indices, names)."""
+    import mmt_eval
+    idx, values, pct, names = _scored_modalities(logits_list, yb_list)
     pm = mmt_eval.PositionMetrics(values, pct, t_begin=_get_eval_positions_from(), bins=10)
     return pm, idx, names
+
+
+last_temperature_fit = {}  # eval_temperature: fit. Per state the tables and numbers of the latest estimate_loss
+
+
+def _new_temperature_fit(logits_list, yb_list):
+    """eval_temperature: fit. A TemperatureFit (default grid) over the scored modalities, made at the first batch of
+    a state. Returns (fit, indices, names)."""
+    import mmt_eval
+    idx, values, pct, names = _scored_modalities(logits_list, yb_list)
+    tf = mmt_eval.TemperatureFit(values, pct, t_begin=_get_eval_positions_from(), bins=10)
+    return tf, idx, names
 
 
 last_rollout_metrics = {}  # eval_rollout_paths > 0. Per state the tables and numbers of the latest estimate_loss
@@ -589,9 +613,13 @@ def estimate_loss(current_step=None, max_steps=None):
     rollout_paths = _get_eval_rollout_paths()
     if rollout_paths:
         rollout_steps, rollout_seed = _get_eval_rollout_steps(), _get_eval_rollout_seed()
+    fit_temperature = _get_eval_temperature() == "fit"
+    if fit_temperature:
+        _get_eval_positions_from()
     m.eval()
     for state in ["train", "val"]:
         pm = None
+        tf = None
         rm, rm_hz, rm_names = None, None, {}
         now = datetime.now()
         current_time = now.strftime("%H:%M:%S")
@@ -626,6 +654,11 @@ def estimate_loss(current_step=None, max_steps=None):
                         pm, pm_idx, pm_names = _new_position_metrics(logits_list, yb_list)
                     pm.add([logits_list[i].contiguous() for i in pm_idx], [xb_list[i].contiguous() for i in pm_idx],
                            [yb_list[i].contiguous() for i in pm_idx])
+                if fit_temperature:  # the same logits under a grid of temperatures: one more call, no sync
+                    if tf is None:
+                        tf, tf_idx, tf_names = _new_temperature_fit(logits_list, yb_list)
+                    tf.add([logits_list[i].contiguous() for i in tf_idx], [xb_list[i].contiguous() for i in tf_idx],
+                           [yb_list[i].contiguous() for i in tf_idx])
                 if rollout_paths:
                     # a backtest on the window itself: roll the paths from its head, score the horizon forecast
                     # against its tail. After everything that reads this iteration's logits; an explicit seed, so
@@ -671,6 +704,17 @@ def estimate_loss(current_step=None, max_steps=None):
                   f"{_get_block_size() - rollout_steps})")
             for line in rm.summary_lines(rm_names, rm_res):
                 print(line)
+        tf_res = None
+        if tf is not None:
+            tf_res = tf.result()
+            last_temperature_fit[state] = {"indices": tf_idx, "names": tf_names, "results": tf_res,
+                                           "t_begin": tf.t_begin, "batches": tf.batches,
+                                           "temperatures": tf.temperatures()}
+            print(f"\nTEMPERATURE FIT - {disp}")
+            for line in tf.summary_lines(tf_names, tf_res):
+                print(line)
+            if state == "val":  # what generate(temperature="calibrated") stands for from here on
+                m.set_calibrated_temperatures({i: r["tau"] for i, r in zip(tf_idx, tf_res) if r["tau"] == r["tau"]})
         cfg = _get_config()
         output_file_name = cfg.get("output_file_name", "")
         project_file_path = cfg.get("project_file_path", "")
@@ -700,6 +744,10 @@ def estimate_loss(current_step=None, max_steps=None):
                     for i in sorted(rm_res):
                         f.write(f"   ROLLOUT METRICS {disp} - {rm_names[i]}: "
                                 f"{mmt_eval.rollout_summary_text(rm_res[i])}\n")
+                if tf_res is not None:
+                    import mmt_eval
+                    for name, r in zip(tf_names, tf_res):
+                        f.write(f"   TEMPERATURE FIT {disp} - {name}: {mmt_eval.temperature_summary_text(r)}\n")
                 if state == "train":
                     f.write("\n")
         if state == "train":
