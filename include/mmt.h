@@ -495,6 +495,66 @@ int mmt_horizon_score(void* stream, int32_t count, int32_t batch, int32_t sample
                       double* const* agg, double* const* aggq, double* const* aggb, double* const* pit, void* scratch,
                       int64_t scratch_bytes);
 
+/* Joint horizon forecasts. mmt_horizon_stats gives the marginal of each series after j steps; the paths of a joint
+ * rollout also carry the dependence between the series. mmt_horizon_joint reads it off the same paths: per basket
+ * (a position sum_p coef[k][p] x^(p) in the series) the moments, sign masses, quantiles, tail means and barrier hits
+ * of its value, per pair of series their covariance, correlation and the tables of their signs. No context.
+ *
+ * Paths: count, batch, samples, steps, V, tok, tok_stride, values, is_percent, origin, origin_stride, logw, nq, levels
+ * as mmt_horizon_stats takes them; count in 1..8 (one chunk), the caller passes only the series that take part.
+ * `nbk` <= 8 baskets: HOST fp64 coef[nbk][count], every entry finite, each basket with a non-zero entry; one `nb` <= 8
+ * for all baskets, HOST barriers[nbk][nb], finite and non-zero. `npair` <= 28 pairs: HOST int32 pairs[npair][2],
+ * problem indices p != q in 0..count-1. Outputs (HOST arrays of device pointers): per basket bstats fp64 [batch, steps,
+ * 9], bqval fp64, bqrow int32 and btail fp64 [batch, steps, nq], bhit fp64 [batch, steps, nb]; per pair pstats fp64
+ * [batch, steps, 22]; ess fp64 [batch] and live int32 [batch] (device, nullable). The arrays of a kind whose count
+ * (nbk, nq, nb, npair) is 0 may be NULL. scratch: mmt_horizon_joint_scratch_bytes(count, batch, samples, steps, nbk)
+ * bytes of device memory, 16-byte aligned, its contents unspecified before and after.
+ * The rule, per prompt b, every line ONE IEEE fp64 operation (nothing is contracted into a multiply-add):
+ *   1. every problem is walked by rule 1 of mmt_horizon_stats (the same device function): x, hi, lo, d bit for bit.
+ *      Basket k of row r at step j: y = 0.0; for p = 0..count-1 ascending t = coef[k][p] * x_j^(p); y = y + t (no
+ *      coefficient is skipped). hi^y_j = max(hi^y_{j-1}, y_j), lo^y_j = min(lo^y_{j-1}, y_j), both from 0. A row is dead
+ *      for the whole call when it is dead in any problem of the call or when some y is not finite: a cross-series
+ *      statistic needs every series of the row.
+ *   2. weights: rule 2 of mmt_horizon_stats over the rows that are not dead: w_s, W, Q, ess, live. Where no row is
+ *      dead they are bit for bit what mmt_horizon_stats writes.
+ *   3. bstats[b, j, 0..8], sums in row order over the same tree: [0] mean of y  [1] variance about that mean (second
+ *      pass, w * (dv * dv))  [2..4] the mass / W of y < 0, y == 0, y > 0  [5] mean of hi^y  [6] mean of lo^y  [7], [8]
+ *      the smallest and the largest y over the rows with weight.
+ *   4. bqval / bqrow: rule 4 of mmt_horizon_stats on the order (y_j, s).
+ *   5. btail, the mean of y below each quantile (the expected shortfall): m the place of the quantile row in that
+ *      order; P and A the inclusive prefixes of w and of w y (one product per row) through place m - 1 over the tree of
+ *      rule 4's prefix (both 0 at m = 0); target = levels[k] * W; rem = target - P; t = rem * y_(m); num = A + t; btail =
+ *      num / target. A caller mirrors the coefficients for the upper tail.
+ *   6. bhit: rule 5 of mmt_horizon_stats on hi^y / lo^y.
+ *   7. pstats[b, j, 0..21] of pair (p, q): m_p, m_q rule 3's means (sum w x / W). Per row a = x_p - m_p, c = x_q - m_q
+ *      and the terms w * (a * a), w * (c * c), w * (a * c): the product of the deviations first, then the weight, as
+ *      rule 3 of mmt_horizon_stats forms its variance. Summed in row order over the tree.
+ *        [0] cov = sum w a c / W   [1] corr = cov / (sqrt(var_p) * sqrt(var_q)), NaN when that denominator is 0, not
+ *        clamped   [2] var_p   [3] var_q   [4..12] the mass / W of (sign x_p, sign x_q) at 3 (s_p + 1) + (s_q + 1)
+ *        [13..21] the same of the step directions (d_p, d_q)
+ *      Where no row is dead var_p is bit for bit stats[1] of mmt_horizon_stats for problem p.
+ *   8. live == 0 gives NaN in every fp64 output, bqrow -1, ess 0.
+ * No float atomics: bit-identical run to run; a prompt launched alone (same samples) gives the bits it gives in
+ * company; a basket or a pair gives the same bits whatever other baskets and pairs are in the call. Nothing outside
+ * the named outputs is written.
+ * Launches: one over rows / 256 for rule 1 and the baskets of each row, one over (prompts x steps, nbk) (the weights of
+ * a prompt and the keys of one step in LDS, 56 KiB at 4096 rows), one over (prompts x steps, npair) (the weights in
+ * LDS, 16 KiB).
+ * MMT_ERR_INVALID before any launch, nothing written: what mmt_horizon_stats refuses so; nbk outside 0..8 or npair
+ * outside 0..28; a coefficient that is NaN or infinite; a basket of zeros; a pair index outside 0..count-1 or p == q; an
+ * output array or entry that is null while its count is not 0. MMT_ERR_UNSUPPORTED: count > 8, V > 2^20, samples >
+ * 4096, batch * steps >= 2^31. nbk == 0 and npair == 0 together, or batch or steps of 0, launch nothing.
+ * mmt_horizon_joint_scratch_bytes returns -1 for arguments the entry refuses. */
+int64_t mmt_horizon_joint_scratch_bytes(int32_t count, int32_t batch, int32_t samples, int32_t steps, int32_t nbk);
+int mmt_horizon_joint(void* stream, int32_t count, int32_t batch, int32_t samples, int32_t steps, const int32_t* V,
+                      const int64_t* const* tok, const int64_t* tok_stride, const double* const* values,
+                      const int32_t* is_percent /* nullable */, const int64_t* const* origin,
+                      const int64_t* origin_stride, const double* logw /* nullable */, int32_t nq,
+                      const double* levels, int32_t nbk, const double* coef, int32_t nb, const double* barriers,
+                      int32_t npair, const int32_t* pairs, double* const* bstats, double* const* bqval,
+                      int32_t* const* bqrow, double* const* btail, double* const* bhit, double* const* pstats,
+                      double* ess /* nullable */, int32_t* live /* nullable */, void* scratch, int64_t scratch_bytes);
+
 /* Evaluation at every position. mmt_eval_direction scores the last position of every window; the evaluation forward
  * has written the logits of all batch * T rows. mmt_eval_positions scores every row with t >= t_begin: direction,
  * log score and what a calibration check of the head's probabilities needs, then reduces the rows to tables. No

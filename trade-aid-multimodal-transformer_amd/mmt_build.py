@@ -16,7 +16,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "build")
 LIB = os.path.join(HERE, "libmmt_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-SOURCES = ["mmt_gemm.hip", "mmt_gemm8.hip", "mmt_mlp2.hip", "mmt_ffn.hip", "mmt_attn.hip", "mmt_attn_oc.hip", "mmt_attn2.hip", "mmt_elem.hip", "mmt_stats.hip", "mmt_qkv2.hip", "mmt_engine.hip", "mmt_ops.hip", "mmt_batch.hip", "mmt_decode.hip", "mmt_decode_fanout.hip", "mmt_sample.hip", "mmt_evidence.hip", "mmt_forecast.hip", "mmt_horizon.hip", "mmt_horizon_score.hip", "mmt_evalpos.hip", "mmt_evaltemp.hip"]
+SOURCES = ["mmt_gemm.hip", "mmt_gemm8.hip", "mmt_mlp2.hip", "mmt_ffn.hip", "mmt_attn.hip", "mmt_attn_oc.hip", "mmt_attn2.hip", "mmt_elem.hip", "mmt_stats.hip", "mmt_qkv2.hip", "mmt_engine.hip", "mmt_ops.hip", "mmt_batch.hip", "mmt_decode.hip", "mmt_decode_fanout.hip", "mmt_sample.hip", "mmt_evidence.hip", "mmt_forecast.hip", "mmt_horizon.hip", "mmt_horizon_score.hip", "mmt_horizon_joint.hip", "mmt_evalpos.hip", "mmt_evaltemp.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I" + os.path.join(REPO, "include"), "-I" + CSRC,
          "-Wall", "-Wno-unused-function", "-Wno-unused-variable", "-Wno-unused-result"]
 

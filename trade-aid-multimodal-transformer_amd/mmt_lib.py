@@ -151,6 +151,14 @@ _SIGS = {
                                   ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_i32, c_i32, ctypes.POINTER(c_vp),
                                   ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), ctypes.POINTER(c_vp),
                                   ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp, c_i64]),
+    "mmt_horizon_joint_scratch_bytes": (c_i64, [c_i32, c_i32, c_i32, c_i32, c_i32]),
+    "mmt_horizon_joint": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(c_i32), ctypes.POINTER(c_vp),
+                                  ctypes.POINTER(c_i64), ctypes.POINTER(c_vp), ctypes.POINTER(c_i32),
+                                  ctypes.POINTER(c_vp), ctypes.POINTER(c_i64), c_vp, c_i32,
+                                  ctypes.POINTER(ctypes.c_double), c_i32, ctypes.POINTER(ctypes.c_double), c_i32,
+                                  ctypes.POINTER(ctypes.c_double), c_i32, ctypes.POINTER(c_i32), ctypes.POINTER(c_vp),
+                                  ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), ctypes.POINTER(c_vp),
+                                  ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp, c_vp, c_vp, c_i64]),
     "mmt_eval_positions_scratch_bytes": (c_i64, [c_i32, c_i32, c_i32, c_i32]),
     "mmt_eval_positions": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(c_i32),
                                    ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), ctypes.POINTER(c_vp),

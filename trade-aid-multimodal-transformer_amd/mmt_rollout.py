@@ -150,9 +150,10 @@ def check_forecast(forecast, generated, vocab_sizes):
 def check_horizon(horizon, generated, vocab_sizes, forecast=None):
     """generate's horizon= for the generated modalities: None / False (off), True, or a dict with the optional keys
     "quantiles" (at most 16 levels in (0, 1)), "values" {i: V_i non-decreasing numbers}, "is_percent" {i: bool} and
-    "barriers" {i: at most 8 finite non-zero numbers}, i generated. values and is_percent default to those of
-    `forecast` (check_forecast's result) where it is given. Returns None or {"quantiles", "values" {i: CPU fp64 [V_i]},
-    "is_percent" {i: bool}, "barriers" {i: [floats]}, "modalities": the generated modalities with values, ascending};
+    "barriers" {i: at most 8 finite non-zero numbers}, i generated, and the joint keys "baskets" / "pairs"
+    (check_joint). values and is_percent default to those of `forecast` (check_forecast's result) where it is given.
+    Returns None or {"quantiles", "values" {i: CPU fp64 [V_i]}, "is_percent" {i: bool}, "barriers" {i: [floats]},
+    "modalities": the generated modalities with values, ascending}, with check_joint's entries where a joint key is given;
     ValueError for anything else, and when no generated modality has values (a horizon has no meaning on token
     indices)."""
     if horizon is None or horizon is False:
@@ -162,8 +163,9 @@ def check_horizon(horizon, generated, vocab_sizes, forecast=None):
     if not isinstance(horizon, dict):
         raise ValueError(f"generate: horizon must be True or a dict, got {horizon!r}")
     for k in horizon:
-        if k not in ("quantiles", "values", "is_percent", "barriers"):
-            raise ValueError(f"generate: horizon has no key {k!r} (quantiles, values, is_percent, barriers)")
+        if k not in ("quantiles", "values", "is_percent", "barriers", "baskets", "pairs"):
+            raise ValueError(f"generate: horizon has no key {k!r} (quantiles, values, is_percent, barriers, baskets, "
+                             "pairs)")
     out = {"quantiles": MS.check_quantiles(horizon.get("quantiles", DEFAULT_QUANTILES)),
            "values": dict(forecast["values"]) if forecast else {},
            "is_percent": dict(forecast["is_percent"]) if forecast else {}, "barriers": {}}
@@ -180,7 +182,69 @@ def check_horizon(horizon, generated, vocab_sizes, forecast=None):
     if not out["modalities"]:
         raise ValueError("generate: horizon= needs the values of a generated modality (horizon={\"values\": {i: ...}} "
                          "or forecast's): a horizon has no meaning on token indices")
+    if "baskets" in horizon or "pairs" in horizon:
+        out.update(check_joint(horizon.get("baskets"), horizon.get("pairs"), out["modalities"]))
     return out
+
+
+def check_joint(baskets, pairs, modalities):
+    """horizon's "baskets" and "pairs" against the generated modalities with values: baskets None or a list of at most
+    8 dicts {"weights": {i: a_i}, "barriers": [...]} (a modality that is not named has coefficient 0; the a_i finite,
+    not all zero), pairs None, "all" or a list of distinct (i, k), i != k. Returns {"baskets": [{"weights": {i: float},
+    "barriers": [floats]}], "pairs": [(i, k)], "joint_modalities": the modalities a basket or a pair names, ascending};
+    ValueError for anything else: a modality without values, a list that is too long, more than 8 modalities named,
+    and both keys empty."""
+    def modality(i, where):
+        if isinstance(i, bool) or not isinstance(i, int) or i not in modalities:
+            raise ValueError(f"generate: horizon[{where}] names modality {i!r}, which is not a generated modality with "
+                             f"values (horizon covers {modalities})")
+        return i
+
+    bk = []
+    if baskets is not None:
+        if not isinstance(baskets, (list, tuple)) or not all(isinstance(b, dict) for b in baskets):
+            raise ValueError("generate: horizon[\"baskets\"] must be a list of dicts {\"weights\": {modality: a}, "
+                             "\"barriers\": [...]}")
+        if len(baskets) > MS.JOINT_MAX_BASKETS:
+            raise ValueError(f"generate: horizon[\"baskets\"] holds at most {MS.JOINT_MAX_BASKETS} baskets, got "
+                             f"{len(baskets)}")
+        for n, b in enumerate(baskets):
+            for name in b:
+                if name not in ("weights", "barriers"):
+                    raise ValueError(f"generate: basket {n} has no key {name!r} (weights, barriers)")
+            w = b.get("weights")
+            if not isinstance(w, dict) or not w:
+                raise ValueError(f"generate: basket {n} needs \"weights\": a dict {{modality: coefficient}}")
+            try:
+                a = {modality(i, "'baskets'"): float(x) for i, x in w.items()}
+            except TypeError:
+                raise ValueError(f"generate: the weights of basket {n} must be numbers, got {w!r}") from None
+            if any(x != x or x in (float("inf"), float("-inf")) for x in a.values()):
+                raise ValueError(f"generate: the weights of basket {n} must be finite, got {w!r}")
+            if not any(x != 0.0 for x in a.values()):
+                raise ValueError(f"generate: basket {n} has no non-zero weight")
+            bk.append({"weights": {i: a[i] for i in sorted(a)}, "barriers": MS.check_barriers(b.get("barriers"))})
+    pr = []
+    if isinstance(pairs, str):
+        if pairs != "all":
+            raise ValueError(f"generate: horizon[\"pairs\"] must be \"all\" or a list of (i, k), got {pairs!r}")
+        pr = [(i, k) for n, i in enumerate(modalities) for k in modalities[n + 1:]]
+    elif pairs is not None:
+        try:
+            pr = [(modality(i, "'pairs'"), modality(k, "'pairs'")) for i, k in pairs]
+        except TypeError:
+            raise ValueError(f"generate: horizon[\"pairs\"] must be \"all\" or a list of (i, k), got {pairs!r}") from None
+        if any(i == k for i, k in pr) or len(set(pr)) != len(pr):
+            raise ValueError(f"generate: horizon[\"pairs\"] needs distinct pairs of two different modalities, got {pr}")
+    if len(pr) > MS.JOINT_MAX_PAIRS:
+        raise ValueError(f"generate: horizon[\"pairs\"] holds at most {MS.JOINT_MAX_PAIRS} pairs, got {len(pr)}")
+    if not bk and not pr:
+        raise ValueError("generate: horizon[\"baskets\"] / [\"pairs\"] name no basket and no pair")
+    named = sorted({i for b in bk for i in b["weights"]} | {i for pq in pr for i in pq})
+    if len(named) > MS.JOINT_MAX_PROBLEMS:
+        raise ValueError(f"generate: the baskets and pairs of one call name at most {MS.JOINT_MAX_PROBLEMS} modalities, "
+                         f"got {named}")
+    return {"baskets": bk, "pairs": pr, "joint_modalities": named}
 
 
 def check_realised(realised, horizon, B, N):
@@ -531,7 +595,8 @@ def rollout(model, idx_list, plan, use_cache, temperature, top_k, top_p, seed, r
     columns. With plan.forecast a step also issues one mmt_forecast_multi over the generated modalities' views, after
     the sampling and scoring and before a resampling, into column j of preallocated [Bp, N, V_i] buffers; one
     mmt_sample.pmf_stats follows the loop. With plan.horizon one mmt_sample.horizon_stats follows the loop too, over
-    the sequence buffers' new columns, and with plan.realised one mmt_sample.horizon_score after it, on the same
+    the sequence buffers' new columns (and, with the joint keys of horizon=, one mmt_sample.horizon_joint on the same
+    buffers, origins and weights), and with plan.realised one mmt_sample.horizon_score after it, on the same
     buffers. Returns seqs, or the tuple (seqs[, {i: logprobs}][, ev][, fc][, hz][, sc])."""
     flat = model.flat_params
     dev = flat.device
@@ -734,7 +799,22 @@ def rollout(model, idx_list, plan, use_cache, temperature, top_k, top_p, seed, r
                 d["brier"], d["aggb"] = d["brier"][..., :len(bars[k])], d["aggb"][:, :len(bars[k])]
         for d, b in zip(res_hz, bars):
             d["hit"] = d["hit"][..., :len(b)]
-        out.append(dict(zip(mods, res_hz)))
+        res_hz = dict(zip(mods, res_hz))
+        if "joint_modalities" in hz:
+            # the cross-series statistics of the same paths, origins and weights, over the modalities that a basket or a
+            # pair names: series p of the call is modality jm[p]
+            jm = hz["joint_modalities"]
+            res_j = MS.horizon_joint([bufs[i][:, n0:] for i in jm], samples=Sp, values=[hz["values"][i] for i in jm],
+                                     is_percent=[hz["is_percent"].get(i, False) for i in jm],
+                                     origin=[bufs[i][:, n0 - 1] for i in jm], logw=logw if giv else None,
+                                     quantiles=hz["quantiles"],
+                                     baskets=[{"weights": [b["weights"].get(i, 0.0) for i in jm],
+                                               "barriers": b["barriers"]} for b in hz["baskets"]],
+                                     pairs=[(jm.index(i), jm.index(k)) for i, k in hz["pairs"]])
+            res_j["pairs"] = {ik: res_j["pairs"][(jm.index(ik[0]), jm.index(ik[1]))] for ik in hz["pairs"]}
+            res_j["modalities"] = list(jm)
+            res_hz["joint"] = res_j
+        out.append(res_hz)
         if rz is not None:
             out.append(dict(zip(rz, res_sc)))
     return out[0] if len(out) == 1 else tuple(out)

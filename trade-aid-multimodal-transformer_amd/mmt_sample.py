@@ -617,6 +617,166 @@ def horizon_stats(tokens_list, *, samples, values, is_percent=False, origin=None
     return [horizon_dict(o) for o in outs]
 
 
+JOINT_FIELDS = ("mean", "var", "p_down", "p_flat", "p_up", "mean_high", "mean_low", "min", "max")  # bstats[..., k]
+JOINT_MAX_PROBLEMS = 8
+JOINT_MAX_BASKETS = 8
+JOINT_MAX_PAIRS = 28
+
+
+def check_baskets(baskets, P):
+    """The baskets of one mmt_horizon_joint call over P problems: None (none) or at most 8 dicts {"weights": P finite
+    numbers, not all zero, "barriers": at most 8 finite non-zero numbers (optional)}. Returns (coefficients [nbk][P],
+    barriers [nbk][...]); ValueError otherwise."""
+    if baskets is None:
+        return [], []
+    if not isinstance(baskets, (list, tuple)) or not all(isinstance(b, dict) for b in baskets):
+        raise ValueError("horizon_joint: baskets must be a list of dicts {\"weights\": [...], \"barriers\": [...]}")
+    if len(baskets) > JOINT_MAX_BASKETS:
+        raise ValueError(f"horizon_joint: at most {JOINT_MAX_BASKETS} baskets, got {len(baskets)}")
+    coef, bars = [], []
+    for k, b in enumerate(baskets):
+        for name in b:
+            if name not in ("weights", "barriers"):
+                raise ValueError(f"horizon_joint: basket {k} has no key {name!r} (weights, barriers)")
+        try:
+            a = [float(x) for x in b["weights"]]
+        except (KeyError, TypeError, ValueError):
+            raise ValueError(f"horizon_joint: basket {k} needs \"weights\": a sequence of {P} numbers") from None
+        if len(a) != P:
+            raise ValueError(f"horizon_joint: basket {k} has {len(a)} weights for {P} series")
+        if any(x != x or x in (float("inf"), float("-inf")) for x in a):
+            raise ValueError(f"horizon_joint: the weights of basket {k} must be finite, got {a!r}")
+        if not any(x != 0.0 for x in a):
+            raise ValueError(f"horizon_joint: basket {k} has no non-zero weight")
+        coef.append(a)
+        bars.append(check_barriers(b.get("barriers")))
+    return coef, bars
+
+
+def check_pairs(pairs, P):
+    """The pairs of one mmt_horizon_joint call over P problems: None (none), "all" (every p < q) or a sequence of
+    distinct (p, q), p != q in 0..P-1. Returns a list of tuples; ValueError otherwise."""
+    if pairs is None:
+        return []
+    if isinstance(pairs, str):
+        if pairs != "all":
+            raise ValueError(f"horizon_joint: pairs must be \"all\" or a list of (p, q), got {pairs!r}")
+        return [(p, q) for p in range(P) for q in range(p + 1, P)]
+    out = []
+    try:
+        for pq in pairs:
+            p, q = pq
+            if any(isinstance(i, bool) or not isinstance(i, int) for i in (p, q)):
+                raise TypeError
+            out.append((p, q))
+    except (TypeError, ValueError):
+        raise ValueError(f"horizon_joint: pairs must be \"all\" or a list of (p, q) ints, got {pairs!r}") from None
+    for p, q in out:
+        if not (0 <= p < P and 0 <= q < P) or p == q:
+            raise ValueError(f"horizon_joint: pair {(p, q)} must name two different series in 0..{P - 1}")
+    if len(set(out)) != len(out):
+        raise ValueError(f"horizon_joint: a pair is named twice: {out}")
+    if len(out) > JOINT_MAX_PAIRS:
+        raise ValueError(f"horizon_joint: at most {JOINT_MAX_PAIRS} pairs, got {len(out)}")
+    return out
+
+
+def horizon_joint(tokens_list, *, samples, values, is_percent=False, origin=None, logw=None,
+                  quantiles=(0.05, 0.5, 0.95), baskets=None, pairs=None):
+    """Joint horizon forecasts of finished paths (mmt_horizon_joint, include/mmt.h). tokens_list, samples, values,
+    is_percent, origin, logw, quantiles: as horizon_stats takes them, for the P <= 8 series that take part. baskets: a
+    list of at most 8 dicts {"weights": [a_0..a_{P-1}], "barriers": [...]}: the position sum_p a_p x^(p) in the series'
+    cumulative changes (barrier lists of unequal length are padded for the call and their columns cut from the result).
+    pairs: "all" or a list of (p, q). Returns {"ess", "live" [B], "baskets": a list of dicts, "pairs": {(p, q): dict}}.
+    A basket dict: "stats" fp64 [B, N, 9] and its columns by name (JOINT_FIELDS: "mean", "var", ...),
+    "quantile_values" fp64, "quantile_rows" int32 (the path that carries each quantile) and "tail_means" fp64 (the mean
+    of the basket below each quantile: the expected shortfall; mirror the weights for the upper tail) [B, N, Q], "hit"
+    fp64 [B, N, nb]. A pair dict: "cov", "corr", "var_p", "var_q" fp64 [B, N], "sign_table" and "step_table" fp64 [B, N,
+    3, 3] (the mass of (sign x_p, sign x_q) / of the step directions at [s_p + 1, s_q + 1]). A path that is dead in
+    one series is dead in all. No sync."""
+    P = len(tokens_list)
+    q = check_quantiles(quantiles)
+    S = int(samples)
+    if S < 1:
+        raise ValueError(f"horizon_joint: samples must be >= 1, got {samples!r}")
+    if S > HORIZON_MAX_SAMPLES:
+        raise ValueError(f"horizon_joint: at most {HORIZON_MAX_SAMPLES} samples per prompt, got {S}")
+    if not 1 <= P <= JOINT_MAX_PROBLEMS:
+        raise ValueError(f"horizon_joint: 1..{JOINT_MAX_PROBLEMS} series per call, got {P}")
+    if not isinstance(values, (list, tuple)) or len(values) != P:
+        raise ValueError(f"horizon_joint: values must be a list of {P} vocabularies (a horizon has no meaning on "
+                         "token indices)")
+    pct = _per_problem(is_percent, P, "is_percent")
+    org = _per_problem(origin, P, "origin") if isinstance(origin, (list, tuple)) else [origin] * P
+    coef, bars = check_baskets(baskets, P)
+    prs = check_pairs(pairs, P)
+    nbk, npair, nq = len(coef), len(prs), len(q)
+    nb = max([len(b) for b in bars], default=0)
+    R, N = tokens_list[0].shape[0], tokens_list[0].shape[1] if tokens_list[0].dim() == 2 else -1
+    dev = tokens_list[0].device
+    if R % S:
+        raise ValueError(f"horizon_joint: {R} rows are no multiple of samples={samples}")
+    B = R // S
+    if logw is not None and (logw.dtype != torch.float64 or logw.shape != (R,) or not logw.is_contiguous()
+                             or logw.device != dev):
+        raise ValueError(f"horizon_joint: logw must be a contiguous fp64 [{R}] tensor on the GPU")
+    for p, t in enumerate(tokens_list):
+        if t.dim() != 2 or t.dtype != torch.int64 or t.device.type != "cuda" or t.device != dev or (
+                tuple(t.shape) != (R, N)) or (N > 1 and t.stride(1) != 1) or (R > 1 and t.stride(0) < N):
+            raise ValueError("horizon_joint: every tokens must be an int64 [rows, N] tensor on the same GPU, the "
+                             "elements of a row contiguous")
+        if values[p] is None:
+            raise ValueError(f"horizon_joint: problem {p} has no values")
+        if not pct[p]:
+            o = org[p]
+            if o is None or o.dtype != torch.int64 or tuple(o.shape) != (R,) or o.device != dev:
+                raise ValueError(f"horizon_joint: a value series needs an int64 [{R}] origin on the GPU (problem {p})")
+    Vs = [len(torch.as_tensor(v).reshape(-1)) for v in values]
+    vals = [check_values(values[p], Vs[p]).to(dev) for p in range(P)]
+    f64, i32, i64, vp = ctypes.c_double, ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p
+    new = lambda *shape, dt=torch.float64: torch.empty(*shape, dtype=dt, device=dev)  # noqa: E731
+    bst = [new(B, N, 9) for _ in range(nbk)]
+    bqv, btl = [new(B, N, nq) for _ in range(nbk)], [new(B, N, nq) for _ in range(nbk)]
+    bqr = [new(B, N, nq, dt=torch.int32) for _ in range(nbk)]
+    bht = [new(B, N, nb) for _ in range(nbk)]
+    pst = [new(B, N, 22) for _ in range(npair)]
+    ess = torch.zeros(B, dtype=torch.float64, device=dev)  # zeros: steps == 0 launches nothing
+    live = torch.zeros(B, dtype=torch.int32, device=dev)
+    if nbk or npair:
+        L = ML.lib()
+        nbytes = int(L.mmt_horizon_joint_scratch_bytes(P, B, S, N, nbk))
+        if nbytes < 0:
+            raise ValueError(f"horizon_joint: {B} prompts x {S} samples x {N} steps is a shape the entry refuses")
+        scratch = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+        ptrs = lambda ts: (vp * max(1, len(ts)))(*[t.data_ptr() if t.numel() else None for t in ts])  # noqa: E731
+        with torch.cuda.device(dev):
+            rc = L.mmt_horizon_joint(
+                ML.stream_ptr(dev), P, B, S, N, (i32 * P)(*Vs), (vp * P)(*[t.data_ptr() for t in tokens_list]),
+                (i64 * P)(*[max(int(t.stride(0)), N) if R > 1 else max(N, 1) for t in tokens_list]),
+                (vp * P)(*[v.data_ptr() for v in vals]), (i32 * P)(*[1 if x else 0 for x in pct]),
+                (vp * P)(*[None if pct[p] else org[p].data_ptr() for p in range(P)]),
+                (i64 * P)(*[1 if pct[p] else max(int(org[p].stride(0)), 1) for p in range(P)]),
+                logw.data_ptr() if logw is not None else None, nq, (f64 * max(1, nq))(*q), nbk,
+                (f64 * max(1, nbk * P))(*[a for row in coef for a in row]), nb,
+                (f64 * max(1, nbk * nb))(*[u for b in bars for u in b + [1.0] * (nb - len(b))]), npair,
+                (i32 * max(1, 2 * npair))(*[i for pq in prs for i in pq]), ptrs(bst), ptrs(bqv), ptrs(bqr), ptrs(btl),
+                ptrs(bht), ptrs(pst), ess.data_ptr() if B else None, live.data_ptr() if B else None,
+                scratch.data_ptr(), nbytes)
+        if rc != 0:
+            raise ML.MmtError(f"mmt_horizon_joint failed (status {rc})")
+    out = {"ess": ess, "live": live, "baskets": [], "pairs": {}}
+    for k in range(nbk):
+        d = {name: bst[k][..., i] for i, name in enumerate(JOINT_FIELDS)}
+        d.update(stats=bst[k], quantile_values=bqv[k], quantile_rows=bqr[k], tail_means=btl[k],
+                 hit=bht[k][..., :len(bars[k])])
+        out["baskets"].append(d)
+    for k, pq in enumerate(prs):
+        s = pst[k]
+        out["pairs"][pq] = {"cov": s[..., 0], "corr": s[..., 1], "var_p": s[..., 2], "var_q": s[..., 3],
+                            "sign_table": s[..., 4:13].reshape(B, N, 3, 3), "step_table": s[..., 13:22].reshape(B, N, 3, 3)}
+    return out
+
+
 SCORE_FIELDS = ("realised", "crps", "pit", "mean_error", "p_realised_sign", "p_realised_step", "realised_high",
                 "realised_low")  # sc[..., k] of mmt_horizon_score
 SCORE_AGG_FIELDS = ("count", "crps", "abs_realised", "abs_error", "sq_error", "p_realised_sign", "sign_hits",

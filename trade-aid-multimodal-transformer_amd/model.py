@@ -622,6 +622,20 @@ class MultimodalTransformer(nn.Module):
         the early steps rest on few distinct ancestors. num_samples > 4096 is refused before the prefill. Sequences,
         log-probabilities, `ev` and `fc` are bit-identical to the call without horizon=.
 
+        Joint horizon forecasts: two more keys of horizon=, "baskets": [{"weights": {i: a_i}, "barriers": [...]}, ...]
+        (at most 8; i a generated modality with values, a modality that is not named has coefficient 0) and "pairs":
+        "all" or [(i, k), ...] (at most 28), add `hz["joint"]` = {"ess", "live", "modalities", "baskets": [dict per
+        basket], "pairs": {(i, k): dict}}: one mmt_horizon_joint call (include/mmt.h) after the mmt_horizon_stats
+        call, on the same buffers, origins and log_weights, over the modalities a basket or a pair names. A basket
+        dict: "stats" fp64 [Bp, N, 9] and its columns "mean", "var", "p_down", "p_flat", "p_up", "mean_high",
+        "mean_low", "min", "max" of y_j = sum_i a_i x_j^(i); "quantile_values", "quantile_rows" and "tail_means" (the
+        mean of y below each quantile: the expected shortfall; mirror the weights for the upper tail) [Bp, N, Q];
+        "hit" [Bp, N, nb]. A pair dict: "cov", "corr" (NaN where a variance is 0), "var_p", "var_q" fp64 [Bp, N],
+        "sign_table" and "step_table" fp64 [Bp, N, 3, 3], the mass of (sign x_i, sign x_k) and of the two step
+        directions at [s_i + 1, s_k + 1]. A path that is dead in one of those series is dead for every basket and
+        pair. Without the two keys nothing is launched, "joint" is absent and every output is as before; with them
+        everything else the call returns is bit-identical. realised= does not score baskets.
+
         Scored horizons (list form only, needs horizon=): realised={i: int64 [B, N]}, i a generated modality with
         values, is the series that followed each prompt (a backtest: the prompt is the head of a known window, the
         realised row its tail). One mmt_horizon_score call (include/mmt.h) follows the mmt_horizon_stats call, on the
