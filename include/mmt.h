@@ -84,7 +84,8 @@ int mmt_tensor_info(const mmt_ctx* ctx, int32_t i, char* name, int32_t name_cap,
 int64_t mmt_workspace_bytes(mmt_ctx* ctx, int32_t batch);
 
 /* forward: idx[i], tgt[i] int64 [batch, T] (tgt may be NULL: no loss); logits[i] fp32 [batch, T, V_i];
- * losses fp32 [M] (mean CE per modality, written only when tgt != NULL); training != 0 enables dropout */
+ * losses fp32 [M] (per modality the mean CE, or the objective of mmt_set_loss; written only when tgt != NULL);
+ * training != 0 enables dropout */
 int mmt_forward(mmt_ctx* ctx, void* stream, int32_t batch, const int64_t* const* idx, const int64_t* const* tgt,
                 const float* params, float* const* logits, float* losses, void* workspace, int32_t training);
 
@@ -861,6 +862,31 @@ int mmt_set_side_stream(mmt_ctx* ctx, int32_t on);
 int mmt_set_deterministic(mmt_ctx* ctx, int32_t on);
 int32_t mmt_get_deterministic(const mmt_ctx* ctx); /* the requested setting (what the next forward latches) */
 
+/* Training objective: torch's F.cross_entropy(weight =, label_smoothing =) extended by a position weight.
+ * Modality i has logits x [R, V] (R = batch * block_size; row r sits at position r mod block_size), label
+ * smoothing eps, class weights w [V] and position weights u [block_size]:
+ *   row_r = (1 - eps) w[t_r] (lse_r - x[r, t_r]) + eps / V * sum_c w[c] (lse_r - x[r, c])
+ *   D     = sum_r u_r w[t_r]
+ *   loss  = sum_r u_r row_r / D
+ * row_r is reduction = "none" of torch; with u == 1 the loss is reduction = "mean" (torch divides by
+ * sum_r w[t_r] too). D == 0 gives a non-finite loss, as in torch, and raises the modality's non-finite flag bit.
+ * The loss kernel writes the logits' gradient times R, so the backward launches are the plain loss's.
+ * `spec` is a host array of one entry per modality (copied); NULL stands for the plain mean CE. The device
+ * vectors stay the caller's and must outlive the forwards that use them. Per context; read by the next
+ * mmt_forward with targets, in training and in evaluation mode. Entries that are all {0, NULL, NULL} are the
+ * plain loss: the same kernels, launches and bits as a context that never had a spec. With class or position
+ * weights one more launch (probe label "ce_denom") computes every D in a fixed-order fp64 sum; the loss
+ * launch keeps its label "ce_fwd". MMT_ERR_INVALID, with nothing changed, for an eps that is NaN or outside
+ * [0, 1). The weights' values (finite, >= 0) are the caller's to check: they live on the device.
+ * Under data parallelism and gradient accumulation each rank / micro-batch normalises by its own D. */
+typedef struct mmt_loss_spec {
+  float label_smoothing;        /* 0 <= eps < 1 */
+  const float* class_weight;    /* device fp32 [V_i], finite and >= 0, or NULL: all 1 */
+  const float* position_weight; /* device fp32 [block_size], finite and >= 0, or NULL: all 1 */
+} mmt_loss_spec;
+int mmt_set_loss(mmt_ctx* ctx, const mmt_loss_spec* spec); /* host array [M]; NULL: the plain mean CE */
+int mmt_get_loss(const mmt_ctx* ctx, mmt_loss_spec* out);  /* [M] */
+
 /* ---- device-resident batcher: get_batch (training_utils.py:333-384) on HBM token streams ---- */
 /* in-place random walk of one int32 training stream (data_utils.py:342-351 as reached through
  * training_utils.py:350-360): x += uniform{0,+-1..+-r} where r < x < V - r */
@@ -1123,6 +1149,14 @@ int mmt_op_colsum(void* stream, int32_t R, int32_t N, const void* x, int32_t ld,
 int mmt_op_ordered_sum(void* stream, int32_t nparts, int32_t n, const float* parts, int64_t ld, float* dst);
 int mmt_op_cross_entropy(void* stream, int32_t R, int32_t V, const float* logits, const int64_t* tgt,
                          void* dlogits, int32_t ld_d, float* loss);
+/* the loss kernel of mmt_set_loss on caller buffers (rows at position r mod T): the D pre-pass when class_weight
+ * or position_weight is set (then denom, one device double, is required and receives D), then the loss and
+ * dlogits = R * dloss / dlogits. loss is accumulated (+=). part: nullable float [512], the block shares summed in
+ * block order (run-to-run identical bits); flag: nullable int [2], both words |= 1 for a non-finite loss.
+ * MMT_ERR_INVALID for R, T, V < 1, ld_d < V, eps outside [0, 1) and weights without denom. */
+int mmt_op_cross_entropy_spec(void* stream, int32_t R, int32_t T, int32_t V, const float* logits, const int64_t* tgt,
+                              void* dlogits, int32_t ld_d, float* loss, float eps, const float* class_weight,
+                              const float* position_weight, double* denom, float* part, int32_t* flag);
 int mmt_op_embedding_fwd(void* stream, int32_t B, int32_t T, int32_t C, int32_t V, const int64_t* idx,
                          const float* tok, const float* pos, float* x);
 int mmt_op_embedding_bwd(void* stream, int32_t B, int32_t T, int32_t C, int32_t V, const int64_t* idx,

@@ -127,6 +127,16 @@ def run(cfg, data, log=print):
             m, optimizer = fresh()
             log("Model: Created successfully")
 
+    # build-only keys: the training objective (label smoothing, balanced class weights, positions that count).
+    # All off by default: then nothing is imported, set or logged
+    smoothing = config_utils._get_label_smoothing(M)
+    if (any(smoothing) if isinstance(smoothing, list) else smoothing) or config_utils._get_loss_class_weights() \
+            or config_utils._get_loss_positions_from():
+        import mmt_loss
+        loss_kw, loss_line = mmt_loss.spec_from_config(data["train"], V, cfg["block_size"])
+        m.set_loss(**loss_kw)
+        log(loss_line)
+
     mmt_data.install(training_utils, data, m)
     training_utils._device_batcher[0] = None
 

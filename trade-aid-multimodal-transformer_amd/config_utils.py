@@ -25,7 +25,10 @@ _DEFAULTS = {
                             # build-only keys: scored rollouts (mmt_eval.RolloutMetrics in estimate_loss); 0 paths: off
                             "eval_rollout_paths": 0, "eval_rollout_steps": 16, "eval_rollout_seed": 0,
                             # build-only key: fit each head's temperature (mmt_eval.TemperatureFit in estimate_loss)
-                            "eval_temperature": "off"},
+                            "eval_temperature": "off",
+                            # build-only keys: the training objective (MultimodalTransformer.set_loss, mmt_loss)
+                            "label_smoothing": 0.0, "loss_class_weights": None, "loss_class_weight_power": 1.0,
+                            "loss_positions_from": 0},
     "model_architecture": {"n_embd": 384, "n_head": 6, "n_layer": 6, "dropout": 0.2,
                            "fixed_values": [-0.5, -0.2, -0.1, 0, 0.1, 0.2, 0.5],
                            # build-only key (the reference ignores unknown keys): "bf16" | "fp8"
@@ -229,4 +232,52 @@ def _get_eval_rollout_seed():
     v = _get_config().get("eval_rollout_seed", 0)
     if isinstance(v, bool) or not isinstance(v, int) or v < 0:
         raise ValueError(f"eval_rollout_seed must be an integer >= 0, got {v!r}")
+    return v
+
+
+def _get_label_smoothing(num_modalities=None):
+    """Build-only knob: the label smoothing of the training objective (MultimodalTransformer.set_loss), a number in
+    [0, 1) for every modality or a list of one per modality (its length is checked when num_modalities is given).
+    Default 0.0 (also when the key is absent): the plain cross-entropy."""
+    v = _get_config().get("label_smoothing", 0.0)
+
+    def one(e):
+        if isinstance(e, bool) or not isinstance(e, (int, float)) or e != e or e < 0 or e >= 1:
+            raise ValueError(f"label_smoothing must be a number in [0, 1) or a list of them, got {v!r}")
+        return float(e)
+
+    if isinstance(v, (list, tuple)):
+        if not v or (num_modalities is not None and len(v) != num_modalities):
+            raise ValueError(f"label_smoothing as a list needs one value per modality, got {v!r}")
+        return [one(e) for e in v]
+    return one(v)
+
+
+def _get_loss_class_weights():
+    """Build-only knob: the class weights of the training objective. None (default, also when the key is absent):
+    none. "balanced": mmt_loss.balanced_class_weights over the training tokens of every modality."""
+    v = _get_config().get("loss_class_weights", None)
+    if v is None:
+        return None
+    if not isinstance(v, str) or v != "balanced":
+        raise ValueError(f"loss_class_weights must be null or 'balanced', got {v!r}")
+    return v
+
+
+def _get_loss_class_weight_power():
+    """Build-only knob: alpha of the balanced class weights, w_c ~ (n / count_c) ** alpha: a number in [0, 1],
+    default 1 (also when the key is absent). Read only with loss_class_weights: balanced."""
+    v = _get_config().get("loss_class_weight_power", 1.0)
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v or v < 0 or v > 1:
+        raise ValueError(f"loss_class_weight_power must be a number in [0, 1], got {v!r}")
+    return float(v)
+
+
+def _get_loss_positions_from():
+    """Build-only knob: the first position of a window that counts in the training loss, an integer in
+    0..block_size - 1; the positions below it get weight 0, the rest 1. Default 0 (also when the key is absent):
+    every position."""
+    v = _get_config().get("loss_positions_from", 0)
+    if isinstance(v, bool) or not isinstance(v, int) or v < 0 or v >= _get_block_size():
+        raise ValueError(f"loss_positions_from must be an integer in 0..block_size - 1, got {v!r}")
     return v

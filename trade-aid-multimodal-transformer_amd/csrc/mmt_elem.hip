@@ -898,6 +898,200 @@ hipError_t mmt_launch_ce_fwd(const CeBatch& b, int R, hipStream_t s) {
 }
 
 // ============================================================================================
+// Cross-entropy under a loss spec (CeSpecProblem, mmt_kernels.h): label smoothing, class weights,
+// position weights. The structure of ce_rows / ce_fwd_kernel above (one wave per row, the row in
+// registers, the next row's loads in flight, the smallest instantiation per problem, three passes
+// for V > 1024); the wave also keeps its columns' class weights in registers, loaded once: they are
+// the same for every row. dlogits leave pre-scaled by R / D, so the backward is the plain one's.
+// ============================================================================================
+template <int KV>
+__device__ __forceinline__ float ce_spec_rows(const CeSpecProblem& S, int R, int T, float scale, int lane, int first,
+                                              int stride) {
+  const CeProblem& P = S.ce;
+  const int V = P.V;
+  const float eps = S.eps, keep = 1.f - eps, epsv = eps / (float)V, invv = 1.f / (float)V;
+  float w[KV];  // pad lanes: 0
+  float wsum = 0.f;
+#pragma unroll
+  for (int k = 0; k < KV; ++k) {
+    const int i = lane + 64 * k;
+    w[k] = i < V ? (S.cw ? S.cw[i] : 1.f) : 0.f;
+    wsum += w[k];
+  }
+  const float wbar = warp_sum(wsum) / (float)V;
+  float contrib = 0.f;
+  float v[KV], nv[KV];
+  auto load = [&](int row, float (&dst)[KV]) {
+    const float* x = P.logits + (int64_t)row * V;
+#pragma unroll
+    for (int k = 0; k < KV; ++k) {
+      const int i = lane + 64 * k;
+      dst[k] = (row < R && i < V) ? x[i] : -INFINITY;
+    }
+  };
+  if (first < R) load(first, v);
+  for (int row = first; row < R; row += stride) {
+    const int t = (int)P.tgt[row];
+    const float xt = P.logits[(int64_t)row * V + t];
+    const float wt = S.cw ? S.cw[t] : 1.f;
+    const float u = S.pw ? S.pw[row % T] : 1.f;
+    if (row + stride < R) load(row + stride, nv);
+    float m = v[0];
+#pragma unroll
+    for (int k = 1; k < KV; ++k) m = fmaxf(m, v[k]);
+    m = warp_max(m);
+    float sum = 0.f;
+#pragma unroll
+    for (int k = 0; k < KV; ++k) sum += __expf(v[k] - m);  // exp(-inf) = 0 for the padding
+    const float lse = m + __logf(warp_sum(sum));
+    float rl = keep * wt * (lse - xt);
+    if (eps > 0.f) {  // the smoothing term as a sum of non-negative terms w[c] (lse - x[c]), pad lanes masked
+      float sm = 0.f;
+#pragma unroll
+      for (int k = 0; k < KV; ++k) sm += (lane + 64 * k < V) ? w[k] * (lse - v[k]) : 0.f;
+      rl += epsv * warp_sum(sm);
+    }
+    contrib += u * rl;
+    // the gradient as (1 - eps) w[t] (p - onehot) + eps (Wbar p - w / V): the plain kernel's difference first
+    // (exactly zero at V = 1, and the plain kernel's bits under a neutral spec)
+    const float bt = keep * wt, g = u * scale;
+    bf16_t* d = P.dlogits + (int64_t)row * P.ld_d;
+#pragma unroll
+    for (int k = 0; k < KV; ++k) {
+      const int i = lane + 64 * k;
+      if (i < P.ld_d) {
+        const float pj = __expf(v[k] - lse);
+        d[i] = f2bf(i < V && u != 0.f ? g * (bt * (pj - (i == t ? 1.f : 0.f)) + eps * (wbar * pj - w[k] * invv)) : 0.f);
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < KV; ++k) v[k] = nv[k];
+  }
+  return contrib;
+}
+
+template <int KV>
+__global__ __launch_bounds__(256) void ce_spec_kernel(CeSpecBatch batch, int R, int T) {
+  const CeSpecProblem& S = batch.p[blockIdx.z];
+  const CeProblem& P = S.ce;
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int V = P.V;
+  __shared__ float part[4];
+  const double D = S.denom ? *S.denom : (double)R;
+  const float scale = (float)((double)R / D);
+  float contrib = 0.f;
+  const int first = blockIdx.x * 4 + wave, stride = gridDim.x * 4;
+  if (KV > 0) {
+    const int kv = (V + 63) / 64;  // uniform per problem
+    if (kv <= 1) contrib = ce_spec_rows<1>(S, R, T, scale, lane, first, stride);
+    else if (kv <= 2 && KV >= 2) contrib = ce_spec_rows<2>(S, R, T, scale, lane, first, stride);
+    else if (kv <= 4 && KV >= 4) contrib = ce_spec_rows<4>(S, R, T, scale, lane, first, stride);
+    else if (kv <= 8 && KV >= 8) contrib = ce_spec_rows<8>(S, R, T, scale, lane, first, stride);
+    else contrib = ce_spec_rows<(KV > 0 ? KV : 1)>(S, R, T, scale, lane, first, stride);
+  } else {  // V > 1024: three passes over the row, the class weights re-read (they stay in cache)
+    const float eps = S.eps, keep = 1.f - eps, epsv = eps / (float)V, invv = 1.f / (float)V;
+    float wsum = 0.f;
+    for (int i = lane; i < V; i += 64) wsum += S.cw ? S.cw[i] : 1.f;
+    const float wbar = warp_sum(wsum) / (float)V;
+    for (int row = first; row < R; row += stride) {
+      const float* x = P.logits + (int64_t)row * V;
+      const int t = (int)P.tgt[row];
+      const float wt = S.cw ? S.cw[t] : 1.f;
+      const float u = S.pw ? S.pw[row % T] : 1.f;
+      bf16_t* d = P.dlogits + (int64_t)row * P.ld_d;
+      float m = -INFINITY;
+      for (int i = lane; i < V; i += 64) m = fmaxf(m, x[i]);
+      m = warp_max(m);
+      float sum = 0.f;
+      for (int i = lane; i < V; i += 64) sum += __expf(x[i] - m);
+      const float lse = m + __logf(warp_sum(sum));
+      const float bt = keep * wt, g = u * scale;
+      float sm = 0.f;  // the smoothing term rides the store pass
+      for (int i = lane; i < P.ld_d; i += 64) {
+        float dv = 0.f;
+        if (i < V) {
+          const float wi = S.cw ? S.cw[i] : 1.f;
+          sm += wi * (lse - x[i]);
+          const float pj = __expf(x[i] - lse);
+          if (u != 0.f) dv = g * (bt * (pj - (i == t ? 1.f : 0.f)) + eps * (wbar * pj - wi * invv));
+        }
+        d[i] = f2bf(dv);
+      }
+      float rl = keep * wt * (lse - x[t]);
+      if (eps > 0.f) rl += epsv * warp_sum(sm);
+      contrib += u * rl;
+    }
+  }
+  if (lane == 0) part[wave] = contrib;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const float blk = (part[0] + part[1] + part[2] + part[3]) / (float)D;
+    if (P.part) P.part[blockIdx.x] = blk;  // summed in block order by ce_loss_kernel
+    else atomicAdd(P.loss, blk);
+    if (P.flag && !__builtin_isfinite(blk)) {  // as ce_fwd_kernel
+      atomicOr(P.flag, P.bit);
+      atomicOr(P.flag + 1, P.bit);
+    }
+  }
+}
+
+// D = sum_r u[r mod T] w[t_r] of one problem per workgroup: thread i adds rows i, i + 1024, ... in order in fp64,
+// then a fixed tree over the threads (no atomics: the same bits on every run). Reads the targets and the two
+// weight vectors only
+__global__ __launch_bounds__(1024) void ce_denom_kernel(CeSpecBatch batch, int R, int T) {
+  const CeSpecProblem& S = batch.p[blockIdx.x];
+  if (!S.denom || (!S.cw && !S.pw)) return;
+  __shared__ double red[1024];
+  double acc = 0.0;
+  for (int r = threadIdx.x; r < R; r += 1024) {
+    const float w = S.cw ? S.cw[(int)S.ce.tgt[r]] : 1.f;
+    const float u = S.pw ? S.pw[r % T] : 1.f;
+    acc += (double)u * (double)w;
+  }
+  red[threadIdx.x] = acc;
+  __syncthreads();
+  for (int o = 512; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) *S.denom = red[0];
+}
+
+hipError_t mmt_launch_ce_denom(const CeSpecBatch& b, int R, int T, hipStream_t s) {
+  bool any = false;
+  for (int g = 0; g < b.count; ++g) any = any || (b.p[g].denom && (b.p[g].cw || b.p[g].pw));
+  if (!any) return hipSuccess;
+  hipLaunchKernelGGL(ce_denom_kernel, dim3(b.count), dim3(1024), 0, s, b, R, T);
+  return hipGetLastError();
+}
+
+hipError_t mmt_launch_ce_spec(const CeSpecBatch& b, int R, int T, hipStream_t s) {
+  if (b.count == 0) return hipSuccess;
+  int maxv = 1;
+  bool any_part = false;
+  CeBatch cb{};  // ce_loss_kernel's view of the same problems
+  cb.count = b.count;
+  for (int g = 0; g < b.count; ++g) {
+    cb.p[g] = b.p[g].ce;
+    maxv = cb.p[g].V > maxv ? cb.p[g].V : maxv;
+    any_part = any_part || cb.p[g].part;
+  }
+  int blocks = (R + 3) / 4;
+  if (blocks > 512) blocks = 512;
+  dim3 grid(blocks, 1, b.count);
+  const int kv = (maxv + 63) / 64;
+  if (kv <= 1) hipLaunchKernelGGL(ce_spec_kernel<1>, grid, dim3(256), 0, s, b, R, T);
+  else if (kv <= 2) hipLaunchKernelGGL(ce_spec_kernel<2>, grid, dim3(256), 0, s, b, R, T);
+  else if (kv <= 4) hipLaunchKernelGGL(ce_spec_kernel<4>, grid, dim3(256), 0, s, b, R, T);
+  else if (kv <= 8) hipLaunchKernelGGL(ce_spec_kernel<8>, grid, dim3(256), 0, s, b, R, T);
+  else if (kv <= 16) hipLaunchKernelGGL(ce_spec_kernel<16>, grid, dim3(256), 0, s, b, R, T);
+  else hipLaunchKernelGGL(ce_spec_kernel<0>, grid, dim3(256), 0, s, b, R, T);
+  if (any_part) hipLaunchKernelGGL(ce_loss_kernel, dim3(1, 1, b.count), dim3(64), 0, s, cb, blocks);
+  return hipGetLastError();
+}
+
+// ============================================================================================
 // Bias gradients: out[n] += alpha * sum_r x[r, n]   (x bf16 [R, ld])
 // block = 32 column chunks of 8 x 8 row lanes; 256 rows per block
 // ============================================================================================

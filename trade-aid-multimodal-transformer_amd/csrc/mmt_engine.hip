@@ -313,6 +313,10 @@ struct mmt_ctx {
   // for a training == 0 forward, whose saved Q/K/V are the decode cache); onchip is what the forward's layers
   // then ran with (0 where the path does not apply), and its backward follows it. 3: Q/K/V were not written
   int onchip_req = 0, onchip = 0;
+  // the training objective (mmt_set_loss), read by every forward with targets; loss_on: some entry is not the
+  // plain mean CE (off: run_forward launches exactly what it launched before the spec existed)
+  mmt_loss_spec loss[MAXM] = {};
+  bool loss_on = false;
 };
 
 namespace {
@@ -524,6 +528,10 @@ void build_layout(mmt_ctx* c) {
 // the non-finite-loss flag words sit right after the packed weights, at the same offset for every
 // batch size, so querying them never replaces the plan of a pending backward / decode
 size_t flag_offset(const mmt_ctx* c) { return (size_t)rup(c->pack_elems * 2, 256); }
+// ... and in the same 256-byte block, behind the two words: one double per modality, the loss denominators D of
+// mmt_set_loss (written by ce_denom, read by the loss kernel of the same forward)
+constexpr size_t LOSS_DENOM_OFF = 64;
+static_assert(LOSS_DENOM_OFF + sizeof(double) * MAXM <= 256, "the loss denominators fit the flag block");
 
 // -------------------------------------------------------------------------------------------
 // workspace plan for batch B (continued)
@@ -1533,7 +1541,27 @@ int run_forward(mmt_ctx* c, Runner& r, const int64_t* const* idx, const int64_t*
   }
   static const char* const post_labels[3] = {"lnf_fwd", "head0", "head2"};
   run_post(c, r, R, xin, lnf_done.data(), post_rows, logits, lf, post_labels);
-  if (tgt && r.rc == MMT_OK) {
+  if (tgt && r.rc == MMT_OK && c->loss_on) {
+    // the objective of mmt_set_loss: D of the weighted modalities (doubles behind the two flag words of the flag
+    // block), then the loss kernel that writes dlogits times R / D: the backward is the plain loss's
+    CeSpecBatch sb{}; sb.count = M;
+    double* denom = reinterpret_cast<double*>(r.W<char>(p.flag) + LOSS_DENOM_OFF);
+    for (int i = 0; i < M; ++i) {
+      CeProblem& q = sb.p[i].ce;
+      q.logits = logits[i]; q.tgt = tgt[i]; q.dlogits = r.b16(p.dlog[i]);
+      q.loss = losses + i; q.V = c->V[i]; q.ld_d = c->ldv[i];
+      q.flag = r.W<int>(p.flag); q.bit = 1 << i;
+      q.part = r.f32(p.celoss[i]);
+      const mmt_loss_spec& ls = c->loss[i];
+      sb.p[i].eps = ls.label_smoothing; sb.p[i].cw = ls.class_weight; sb.p[i].pw = ls.position_weight;
+      sb.p[i].denom = (ls.class_weight || ls.position_weight) ? denom + i : nullptr;
+    }
+    bool weights = false;
+    for (int i = 0; i < M; ++i) weights = weights || sb.p[i].denom;
+    auto no_cost = [](double*, double*) {};
+    if (weights) r.launch("ce_denom", r.s, [&] { return mmt_launch_ce_denom(sb, R, c->T, r.s); }, no_cost);
+    r.launch("ce_fwd", r.s, [&] { return mmt_launch_ce_spec(sb, R, c->T, r.s); }, no_cost);
+  } else if (tgt && r.rc == MMT_OK) {
     CeBatch cb{}; cb.count = M;
     for (int i = 0; i < M; ++i) {
       cb.p[i].logits = logits[i]; cb.p[i].tgt = tgt[i]; cb.p[i].dlogits = r.b16(p.dlog[i]);
@@ -1541,7 +1569,7 @@ int run_forward(mmt_ctx* c, Runner& r, const int64_t* const* idx, const int64_t*
       cb.p[i].flag = r.W<int>(p.flag); cb.p[i].bit = 1 << i;
       cb.p[i].part = r.f32(p.celoss[i]);
     }
-    r.ok(mmt_launch_ce_fwd(cb, R, r.s), "ce_fwd");
+    r.launch("ce_fwd", r.s, [&] { return mmt_launch_ce_fwd(cb, R, r.s); }, [](double*, double*) {});
   }
   return r.rc;
 }
@@ -2590,6 +2618,25 @@ extern "C" int mmt_set_deterministic(mmt_ctx* c, int32_t on) {
   return MMT_OK;
 }
 extern "C" int32_t mmt_get_deterministic(const mmt_ctx* c) { return c && c->det_req ? 1 : 0; }
+
+// the training objective (include/mmt.h): checked in full before anything is stored
+extern "C" int mmt_set_loss(mmt_ctx* c, const mmt_loss_spec* spec) {
+  if (!c) return MMT_ERR_INVALID;
+  bool on = false;
+  for (int i = 0; spec && i < c->M; ++i) {
+    const float e = spec[i].label_smoothing;
+    if (!(e >= 0.f && e < 1.f)) return fail(c, MMT_ERR_INVALID, "mmt_set_loss: label_smoothing outside [0, 1)");
+    on = on || e != 0.f || spec[i].class_weight || spec[i].position_weight;
+  }
+  for (int i = 0; i < MAXM; ++i) c->loss[i] = (spec && i < c->M) ? spec[i] : mmt_loss_spec{};
+  c->loss_on = on;
+  return MMT_OK;
+}
+extern "C" int mmt_get_loss(const mmt_ctx* c, mmt_loss_spec* out) {
+  if (!c || !out) return MMT_ERR_INVALID;
+  for (int i = 0; i < c->M; ++i) out[i] = c->loss[i];
+  return MMT_OK;
+}
 
 // in-place gradient accumulation (mmt.h): read at stage 0 of the backward, per context
 extern "C" int mmt_set_grad_accumulate(mmt_ctx* c, int32_t on) {

@@ -520,6 +520,26 @@ struct CeProblem {
 struct CeBatch { CeProblem p[MMT_MAX_GROUP]; int count; };
 hipError_t mmt_launch_ce_fwd(const CeBatch& b, int R, hipStream_t s);
 
+// The cross-entropy under a loss spec (mmt_set_loss): label smoothing eps, class weights w [V], position weights
+// u [T] (row r sits at position r mod T):
+//   row_r = (1 - eps) w[t_r] (lse_r - x[r, t_r]) + eps / V * sum_c w[c] (lse_r - x[r, c])
+//   D = sum_r u_r w[t_r],  loss += sum_r u_r row_r / D
+//   dlogits[r, j] = R / D * u_r (p[r, j] ((1 - eps) w[t_r] + eps Wbar) - (1 - eps) w[t_r] [j == t_r] - eps / V * w[j])
+// with Wbar = sum_c w[c] / V: R times the loss's gradient, so the backward's 1 / R (made for softmax - onehot)
+// leaves the gradient itself. Pad columns and the rows with u_r == 0 are written zero.
+struct CeSpecProblem {
+  CeProblem ce;          // logits, targets, dlogits, loss, part, flag as for mmt_launch_ce_fwd
+  const float* cw;       // [V] class weights, nullable: all 1
+  const float* pw;       // [T] position weights, nullable: all 1
+  // D: written by mmt_launch_ce_denom when cw or pw is set, read by mmt_launch_ce_spec; null: D = R (eps alone)
+  double* denom;
+  float eps;
+};
+struct CeSpecBatch { CeSpecProblem p[MMT_MAX_GROUP]; int count; };
+// D of every problem that has weights, one workgroup each (fixed-order fp64 sum); launches nothing when none has
+hipError_t mmt_launch_ce_denom(const CeSpecBatch& b, int R, int T, hipStream_t s);
+hipError_t mmt_launch_ce_spec(const CeSpecBatch& b, int R, int T, hipStream_t s);
+
 struct ColsumProblem {
   const bf16_t* x;       // [R, ld]
   float* out;            // [N] atomic accumulate alpha * sum_r x[r, n]

@@ -470,6 +470,24 @@ int mmt_op_cross_entropy(void* stream, int32_t R, int32_t V, const float* logits
   return st(mmt_launch_ce_fwd(b, R, (hipStream_t)stream));
 }
 
+int mmt_op_cross_entropy_spec(void* stream, int32_t R, int32_t T, int32_t V, const float* logits, const int64_t* tgt,
+                              void* dlogits, int32_t ld_d, float* loss, float eps, const float* class_weight,
+                              const float* position_weight, double* denom, float* part, int32_t* flag) {
+  if (R < 1 || T < 1 || V < 1 || ld_d < V || !logits || !tgt || !dlogits || !loss) return MMT_ERR_INVALID;
+  if (!(eps >= 0.f && eps < 1.f)) return MMT_ERR_INVALID;
+  const bool weights = class_weight || position_weight;
+  if (weights && !denom) return MMT_ERR_INVALID;
+  CeSpecBatch b{};
+  b.count = 1;
+  CeSpecProblem& p = b.p[0];
+  p.ce.logits = logits; p.ce.tgt = tgt; p.ce.dlogits = (bf16_t*)dlogits; p.ce.loss = loss; p.ce.V = V;
+  p.ce.ld_d = ld_d; p.ce.part = part; p.ce.flag = flag; p.ce.bit = 1;
+  p.cw = class_weight; p.pw = position_weight; p.denom = weights ? denom : nullptr; p.eps = eps;
+  const hipError_t e = mmt_launch_ce_denom(b, R, T, (hipStream_t)stream);
+  if (e != hipSuccess) return st(e);
+  return st(mmt_launch_ce_spec(b, R, T, (hipStream_t)stream));
+}
+
 int mmt_op_embedding_fwd(void* stream, int32_t B, int32_t T, int32_t C, int32_t V, const int64_t* idx, const float* tok,
                          const float* pos, float* x) {
   EmbBatch b{};

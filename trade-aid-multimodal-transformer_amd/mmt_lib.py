@@ -56,6 +56,15 @@ class MmtGuardHeader(ctypes.Structure):
     ]
 
 
+class MmtLossSpec(ctypes.Structure):
+    """struct mmt_loss_spec (include/mmt.h): one modality's training objective."""
+    _fields_ = [
+        ("label_smoothing", c_f32),
+        ("class_weight", c_vp),
+        ("position_weight", c_vp),
+    ]
+
+
 GUARD_SLOTS = 1024  # MMT_GUARD_SLOTS: fp64 block partials after the header
 
 
@@ -193,6 +202,8 @@ _SIGS = {
     "mmt_set_side_stream": (c_i32, [c_vp, c_i32]),
     "mmt_set_deterministic": (c_i32, [c_vp, c_i32]),
     "mmt_get_deterministic": (c_i32, [c_vp]),
+    "mmt_set_loss": (c_i32, [c_vp, ctypes.POINTER(MmtLossSpec)]),
+    "mmt_get_loss": (c_i32, [c_vp, ctypes.POINTER(MmtLossSpec)]),
     "mmt_probe_count": (c_i32, [c_vp]),
     "mmt_probe_read_at": (c_i32, [c_vp, c_i32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(c_i64),
                                   ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
@@ -280,6 +291,8 @@ _SIGS = {
     "mmt_op_colsum": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_f32]),
     "mmt_op_ordered_sum": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_i64, c_vp]),
     "mmt_op_cross_entropy": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp]),
+    "mmt_op_cross_entropy_spec": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_f32, c_vp, c_vp,
+                                          c_vp, c_vp, c_vp]),
     "mmt_op_embedding_fwd": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "mmt_op_embedding_bwd": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "mmt_op_embedding_bwd_ws": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),

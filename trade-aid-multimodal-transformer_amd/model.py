@@ -136,6 +136,45 @@ class MultimodalTransformer(nn.Module):
         self.grad_accumulation = False  # set_grad_accumulation: the backward writes into flat_params.grad in place
         self._grad_buf = None  # the in-place mode's persistent gradient buffer (becomes .grad when .grad is None)
         self._no_sync = False  # inside no_sync(): no gradient exchange
+        self._loss_host = None  # set_loss: [(eps, class weights, position weights)] on the host; None: the plain loss
+        self._loss_dev = None   # ... and (device, the device tensors the engine reads), made at the first forward there
+
+    def set_loss(self, label_smoothing=0.0, class_weights=None, position_weights=None):
+        """The training objective (include/mmt.h, mmt_set_loss): torch's F.cross_entropy(weight=, label_smoothing=)
+        extended by a weight per position of the window, for every forward that gets targets (train or eval mode).
+        Each argument is one value for all modalities or a {modality: value} dict: label_smoothing a number in
+        [0, 1), class_weights a vector [V_i], position_weights a vector [block_size], both finite, >= 0 and not all
+        zero (ValueError otherwise, before anything changes). No arguments: back to the plain mean cross-entropy.
+        The model keeps the device copies alive; the spec is a plain attribute, not part of state_dict."""
+        import mmt_loss
+        spec = mmt_loss.normalize_spec(label_smoothing, class_weights, position_weights, self.vocab_sizes,
+                                       self.block_size)
+        self._install_loss(spec, self.flat_params.device)
+
+    def _install_loss(self, spec, dev):
+        M = self.num_modalities
+        arr = (ML.MmtLossSpec * M)()
+        keep = []
+        for i in range(M if spec is not None else 0):
+            eps, cw, pw = spec[i]
+            cw = None if cw is None else cw.to(dev)
+            pw = None if pw is None else pw.to(dev)
+            keep.append((cw, pw))
+            arr[i].label_smoothing = eps
+            arr[i].class_weight = None if cw is None else cw.data_ptr()
+            arr[i].position_weight = None if pw is None else pw.data_ptr()
+        ML.check(ML.lib().mmt_set_loss(self._ctx, arr if spec is not None else None), self._ctx, "mmt_set_loss")
+        self._loss_host = spec
+        self._loss_dev = (dev, keep) if spec is not None else None
+
+    @property
+    def loss_spec(self):
+        """The current objective: one {"label_smoothing", "class_weights", "position_weights"} dict per modality
+        (host copies; None for absent weights), or None for the plain loss."""
+        if self._loss_host is None:
+            return None
+        return [{"label_smoothing": e, "class_weights": None if w is None else w.clone(),
+                 "position_weights": None if u is None else u.clone()} for e, w, u in self._loss_host]
 
     def set_calibrated_temperatures(self, mapping):
         """The per-head temperatures generate(temperature="calibrated") stands for: {modality: tau}, ints 0..M - 1
@@ -273,6 +312,8 @@ class MultimodalTransformer(nn.Module):
         losses = torch.empty(self.num_modalities, dtype=torch.float32, device=dev) if tgt is not None else None
         idx_arr = ML.ptr_array(idx)
         tgt_arr = ML.ptr_array(tgt) if tgt is not None else None
+        if self._loss_dev is not None and self._loss_dev[0] != dev:
+            self._install_loss(self._loss_host, dev)  # the model moved since set_loss: the weights follow it
         if training:
             self.last_dropout_seed = self._next_dropout_seed(dev)
             ML.check(L.mmt_set_dropout_seed(self._ctx, self.last_dropout_seed), self._ctx, "mmt_set_dropout_seed")
