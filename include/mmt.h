@@ -918,12 +918,13 @@ int mmt_exact_walk(void* stream, int32_t nmod, int32_t* const* data, const int64
                    const int32_t* vocab, uint32_t* mt_state, const uint32_t* words, int64_t nwords, void* scratch,
                    int64_t scratch_bytes, int32_t* status);
 /* tuning knob: bit 0 / bit 1 = the slice-streamed hs-64 attention dK/dV / dQ pass, bit 2 = dK/dV at 3 waves
- * per SIMD, bit 3 = the slice-streamed hs-64 forward, bit 5 = the one-pass hs-64 backward at T <= 512 with one
+ * per SIMD, bit 3 = the slice-streamed hs-64 forward, bit 4 unused, bit 5 = the one-pass hs-64 backward at T <= 512 with one
  * KV stream, bit 6 = the one-pass hs-32 backward at T <= 256, bit 7 = that kernel also for several KV streams
- * (default 79 = 15 | 64; env MMT_ATTN_RING); returns the old value */
+ * (default 79 = 15 | 64; env MMT_ATTN_RING, read when the library loads); returns the old value */
 int mmt_attn_set_ring(int v);
 /* tuning knob: attention dropout keep-bit tiles made per wave by attn_mask_kernel (1, 2, 4, 8 or 16; 0 = the env
- * MMT_MASK_G, default 16 at T >= 1024, else 8). The bits do not depend on it. Returns the old value */
+ * MMT_MASK_G, read when the library loads; default 16 at T >= 1024, else 8). The bits do not depend on it. Returns
+ * the old value */
 int mmt_attn_set_mask_g(int g);
 /* tuning knob: 1 = the big GEMM launches with K < 1024 (the d512 FFN / cross-attention K/V products) on a
  * 128 x 256 tile at two workgroups per CU instead of the 256 x 256 ping-pong kernel; 0 (default, env
@@ -1139,6 +1140,22 @@ int mmt_op_attention_bwd_h1_drop(void* stream, int32_t B, int32_t T, int32_t H, 
                                  const float* w2, const void* o, int32_t o_ld, const float* lse, const void* dout,
                                  int32_t dout_ld, void* dh1, float* dw2, float* db1, uint32_t drop_key,
                                  uint32_t drop_thr, float drop_scale, uint32_t* dmask);
+/* The launch plan of an attention batch, from numbers alone: no stream, no device memory, no HIP call, so it runs
+ * without a GPU (tests/test_attn_plan_cpu.py pins the dispatch policy with it). pass: 0 forward, 1 backward, 2 the
+ * keep-bit mask. count problems of one shape with nstreams[g] KV streams. ld: NULL, or 10 ints of which a 0 means
+ * the packed default (C = H * hs): q_ld, kv_ld, kv_hstride (hs), o_ld, dout_ld, dq_ld, dkv_ld, dkv_hstride (hs),
+ * dq32_ld, the h1 rows' (3 H * 16). flags: bit g (g < 8) dropout on in problem g; 0x100 the stage-2 fields, 0x200
+ * the on-chip Q/K/V fields, 0x400 the fp32 dQ scratch, 0x800 deterministic partials; 0x1000 / 0x2000 / 0x4000 /
+ * 0x8000 the Q / dO / dQ / O base at 8 mod 16 bytes; 0x10000 the backward as mmt_backward asks before it sets the
+ * stage-2 fields (taken as present and aligned). Writes 32 ints: status (0 ok, 1 nothing to launch, 2 invalid),
+ * the number of launches (2: the dQ pass, then dK/dV), then per launch 14 ints, the second launch's 0 when there is
+ * one: family (0 chunked forward, 1 chunked dQ, 2 chunked dK/dV, 3 hs-64 ring forward, 4 ring dQ, 5 ring dK/dV,
+ * 6 one-pass hs-64 backward, 7 one-pass hs-32 backward, 8 on-chip-QKV hs-32 forward, 9 mask), hs, DROP, the
+ * one-pass hs-32 kernel's MS / Q2 / DET / OC, the dK/dV ring's waves per SIMD, ring depth, the mask kernel's tiles
+ * per wave, grid x / y / z, workgroup size; last the deterministic launch's floats of partials per problem, a 64-bit
+ * count as its low and its high 32 bits. */
+int mmt_op_attention_plan(int32_t pass, int32_t count, int32_t B, int32_t T, int32_t H, int32_t hs,
+                          const int32_t* nstreams, const int32_t* ld, int32_t flags, int32_t* plan);
 int mmt_op_qkv2_fwd(void* stream, int32_t R, int32_t nblk, int32_t hs, const void* h1, int32_t ld_h1,
                     const float* w2, void* out, int32_t ld_out);
 int mmt_op_qkv2_bwd(void* stream, int32_t R, int32_t nblk, int32_t hs, const void* h1, int32_t ld_h1,

@@ -21,6 +21,7 @@ import pytest
 import torch
 
 import attn_drop_ref as R
+import attn_plan as AP
 import mmt_lib as ML
 
 pytestmark = pytest.mark.gpu
@@ -364,20 +365,8 @@ def _readout_dq(P):
     return worst
 
 
-# (path, mmt_attn_set_ring, hs, T, streams, fp32 dQ scratch)
-PATHS = [
-    ("chunked", 15, 16, 45, 1, False), ("chunked", 15, 16, 45, 2, False),
-    ("chunked", 15, 32, 37, 1, False), ("chunked", 15, 32, 37, 3, False),
-    ("chunked", 15, 32, 300, 1, False), ("chunked", 15, 32, 300, 3, False),  # past the 256-row chunk
-    ("chunked", 15, 48, 96, 2, False),
-    ("onepass32", 79, 32, 37, 1, False), ("onepass32", 79, 32, 256, 1, False),
-    ("onepass32-scratch", 79 | 128, 32, 100, 3, True),
-    ("chunked64", 0, 64, 33, 1, False), ("chunked64", 0, 64, 33, 2, False),
-    ("chunked64", 0, 64, 160, 1, False), ("chunked64", 0, 64, 160, 2, False),  # past the 128-row chunk
-    ("ring64", 15, 64, 160, 1, False), ("ring64", 15, 64, 160, 3, False),
-    ("ring64", 15, 64, 300, 1, False), ("ring64", 15, 64, 300, 3, False),
-    ("onepass64", 47, 64, 300, 1, False),
-]
+# (path, mmt_attn_set_ring, hs, T, streams, fp32 dQ scratch): attn_plan.PATHS, with the kernels each path names
+PATHS = AP.PATHS
 READOUTS = {"fwd": _readout_fwd, "dv": _readout_dv, "dq": _readout_dq}
 
 
@@ -391,6 +380,10 @@ def test_readout(path, ring, hs, T, ns, scratch, readout, p):
     B, H = 2, 3
     old = L.mmt_attn_set_ring(ring)
     try:
+        # the launches below take the kernels the row is named for (the plan: host arithmetic, no launch)
+        fwd, bwd = AP.PATH_FAMILIES[path]
+        assert AP.families(L, AP.readout_call(AP.FWD, T, hs, ns, scratch)) == (fwd,)
+        assert AP.families(L, AP.readout_call(AP.BWD, T, hs, ns, scratch)) == bwd
         P = _Problem(B, T, H, hs, ns, p, 0x5EED0000 + 64 * hs + ns, scratch)
         if p == 0.5:
             assert (~np.tril(P.keep[0]).any(-1)).any()

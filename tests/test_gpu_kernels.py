@@ -10,6 +10,7 @@ import ctypes
 import pytest
 import torch
 
+import attn_plan as AP
 import mmt_lib as ML
 
 pytestmark = pytest.mark.gpu
@@ -664,9 +665,7 @@ def test_attention_fwd_bwd(B, T, H, hs, ns, scratch=False, drop=0.0):
 
 
 # one T per kernel path of tests/test_gpu_attn_dropout.py's table (the larger): (ring, hs, T, streams, scratch)
-DROP_PATHS = [(15, 16, 45, 1, False), (15, 16, 45, 2, False), (15, 32, 300, 1, False), (15, 32, 300, 3, False),
-              (15, 48, 96, 2, False), (79, 32, 256, 1, False), (79 | 128, 32, 100, 3, True), (0, 64, 160, 1, False),
-              (0, 64, 160, 2, False), (15, 64, 300, 1, False), (15, 64, 300, 3, False), (47, 64, 300, 1, False)]
+DROP_PATHS = AP.DROP_PATHS
 
 
 @pytest.mark.parametrize("ring,hs,T,ns,scratch", DROP_PATHS)
@@ -682,9 +681,8 @@ def test_attention_fwd_bwd_dropout(ring, hs, T, ns, scratch):
         L.mmt_attn_set_ring(old)
 
 
-@pytest.mark.parametrize("ring", [0, 1, 3, 7, 8, 15, 47])
-@pytest.mark.parametrize("B,T,H,ns", [(2, 100, 2, 1), (1, 520, 2, 2), (1, 1024, 1, 1), (2, 300, 2, 3), (1, 33, 2, 1),
-                                      (3, 64, 2, 7), (2, 512, 2, 1), (1, 500, 3, 1), (3, 7, 2, 1), (1, 96, 1, 1)])
+@pytest.mark.parametrize("ring", AP.HS64_RINGS)
+@pytest.mark.parametrize("B,T,H,ns", AP.HS64_SHAPES)
 def test_attention_hs64_backward_variants(B, T, H, ns, ring):
     """Every hs-64 attention variant (mmt_attn_set_ring: 0 the chunked dQ and dK/dV passes, 1 the
     slice-streamed dK/dV ring, 3 both rings with two query tiles per wave in the dQ ring, 7 that with
@@ -695,17 +693,18 @@ def test_attention_hs64_backward_variants(B, T, H, ns, ring):
     L = ML.lib()
     old = L.mmt_attn_set_ring(ring)
     try:
+        # the launches below take the variant's kernels (the plan: host arithmetic, no launch)
+        fwd, bwd, occ = AP.hs64_claim(ring, T, ns)
+        assert AP.families(L, AP.kernel_test_call(AP.FWD, B, T, H, 64, ns)) == fwd
+        got = AP.plan(L, AP.kernel_test_call(AP.BWD, B, T, H, 64, ns))
+        assert tuple(l[0] for l in got) == bwd and (not occ or got[1][1][1] == occ)
         test_attention_fwd_bwd(B, T, H, 64, ns)
     finally:
         L.mmt_attn_set_ring(old)
 
 
-@pytest.mark.parametrize("ring", [79 | 128, 79, 15])
-@pytest.mark.parametrize("B,T,H,ns,scratch", [(2, 256, 8, 1, False), (3, 37, 2, 1, False), (1, 2, 2, 1, False),
-                                              (2, 255, 1, 1, False), (1, 33, 4, 1, False), (4, 224, 2, 1, False),
-                                              (2, 256, 2, 2, False), (1, 300, 2, 1, False), (2, 256, 2, 3, True),
-                                              (3, 37, 2, 2, True), (1, 100, 4, 7, True), (2, 64, 1, 4, True),
-                                              (1, 300, 2, 3, True)])
+@pytest.mark.parametrize("ring", AP.HS32_RINGS)
+@pytest.mark.parametrize("B,T,H,ns,scratch", AP.HS32_SHAPES)
 def test_attention_hs32_backward_variants(B, T, H, ns, scratch, ring):
     """The one-pass hs-32 backward (mmt_attn_set_ring bit 6, default: T <= 256; with bit 7 also several KV
     streams when the caller passes fp32 dQ scratch, mmt_op_attention_bwd_ws) and the two-pass pair (ring 15) against the
@@ -714,6 +713,8 @@ def test_attention_hs32_backward_variants(B, T, H, ns, scratch, ring):
     L = ML.lib()
     old = L.mmt_attn_set_ring(ring)
     try:
+        # the one-pass kernel where the docstring says so, the two-pass pair elsewhere (the plan: no launch)
+        assert AP.families(L, AP.kernel_test_call(AP.BWD, B, T, H, 32, ns, scratch)) == AP.hs32_claim(ring, T, ns, scratch)
         test_attention_fwd_bwd(B, T, H, 32, ns, scratch)
     finally:
         L.mmt_attn_set_ring(old)

@@ -12,7 +12,8 @@ at a time, each under its own time limit, and stops at the first child that fail
 built library and the fixtures of DIR. The "probe" group saves, per launch label, the launch count
 and the algorithmic flops / bytes (host arithmetic on the descriptors) of one training step; its step is not timed.
 
-Entries named "tol:*" (gradients of the default mode, whose float atomics add in arrival order) are compared by
+Entries named "tol:*" (gradients of the default mode and, in "attn_ops", the stage-2 sums of the one-pass hs-32 attention
+backward, whose float atomics add in arrival order) are compared by
 rel-L2 against tests/test_gpu_determinism.py's bound, with A's own run-to-run difference printed beside it. Every
 other entry must be equal bit for bit.
 """
@@ -50,7 +51,7 @@ FWD_BWD = ["f_small", "f_hs32", "f_m1", "f_tiny_v", "f_c1", "f_m8:bf16", "f_m8:f
 ENV_CASES = ["MMT_LN_FUSE=0", "MMT_LN_FUSE_FWD=0", "MMT_LN2_FUSE=0", "MMT_MLP2=0", "MMT_MLP2_BWD=0", "MMT_MLP2_BWD=1",
              "MMT_QKV2_FUSE=0", "MMT_MASK_AHEAD=1", "MMT_MASK_AHEAD=2", "MMT_MASK_T2=0", "MMT_DW_ATTN_SMALL=1",
              "MMT_FLUSH_HOLD=1", "MMT_SIDE_STREAM=0"]
-GROUPS = ["eval", "det", "setters", "staged", "decode", "default", "probe"] + ["env:" + e for e in ENV_CASES]
+GROUPS = ["eval", "det", "setters", "staged", "decode", "default", "probe", "attn_ops"] + ["env:" + e for e in ENV_CASES]
 
 
 def _fixture(name):
@@ -208,6 +209,89 @@ def group_default():
         a, b = _fwd_bwd(m, idx, tgt), _fwd_bwd(m, idx, tgt)
         a["tol:grad"], a["tol:grad.again"] = a.pop("grad"), b["grad"]
         out[name] = a
+    return out
+
+
+def _attn_op(hs, T, ns, ring, p, scratch=False, B=2, H=2):
+    """One forward and one backward through mmt_op_attention_fwd_drop / _bwd_drop under mmt_attn_set_ring(ring)."""
+    import torch
+    import attn_drop_ref as DR
+    import mmt_lib as ML
+    L, C, R = ML.lib(), H * hs, B * T
+    g = torch.Generator().manual_seed(1000 * hs + 10 * T + ns)
+    rnd = lambda: torch.randn(R, C, generator=g).to(torch.bfloat16).cuda()
+    z16 = lambda: torch.zeros(R, C, dtype=torch.bfloat16, device="cuda")
+    zf = lambda: torch.zeros(B * H * T, device="cuda")
+    arr = lambda ts: (ctypes.c_void_p * 8)(*[t.data_ptr() for t in ts])
+    q, k, v, do = rnd(), [rnd() for _ in range(ns)], [rnd() for _ in range(ns)], rnd()
+    o, oj, lse, dvec = z16(), [z16() for _ in range(ns)], [zf() for _ in range(ns)], [zf() for _ in range(ns)]
+    dq, dk, dv = z16(), [z16() for _ in range(ns)], [z16() for _ in range(ns)]
+    dq32 = torch.zeros(R, C + 4, device="cuda") if scratch else None
+    key, thr, c = (0xA77E0000 + T, DR.thr_of(p), DR.scale_of(p)) if p else (0, 0, 0.0)
+    dm = [torch.zeros(L.mmt_op_attention_mask_dwords(B, H, T), dtype=torch.int32, device="cuda") for _ in range(ns)]
+    s = ML.stream_ptr("cuda")
+
+    def go():
+        if p:
+            assert L.mmt_op_attention_mask(s, 1, B, T, H, (ctypes.c_int32 * 1)(ns), (ctypes.c_uint32 * 1)(key),
+                                           (ctypes.c_uint32 * 1)(thr), arr(dm)) == 0
+        head = (s, B, T, H, hs, ns, ML.ptr(q), C, arr(k), arr(v), C, hs, ML.ptr(o), C, arr(oj), arr(lse))
+        assert L.mmt_op_attention_fwd_drop(*head, key, thr, c, arr(dm)) == 0
+        assert L.mmt_op_attention_bwd_drop(*head, ML.ptr(do), C, arr(dvec), ML.ptr(dq), C, arr(dk), arr(dv), C, hs,
+                                           ML.ptr(dq32), C + 4 if scratch else 0, key, thr, c, arr(dm)) == 0
+        torch.cuda.synchronize()
+    _with("mmt_attn_set_ring", ring, go)
+    out = {"o": o, "dq": dq}
+    for j in range(ns):
+        out.update({f"oj.{j}": oj[j], f"lse.{j}": lse[j], f"dk.{j}": dk[j], f"dv.{j}": dv[j]})
+    return {n: t.float() for n, t in out.items()}
+
+
+def _attn_h1_op(T, p, B=2, H=2):
+    """The same through the on-chip-QKV entries (hs 32): the stage-2 sums dW2 / db1 are float atomics ("tol:")."""
+    import torch
+    import attn_drop_ref as DR
+    import mmt_lib as ML
+    L, C, R, ld = ML.lib(), H * 32, B * T, 3 * H * 16
+    g = torch.Generator().manual_seed(77 + T)
+    h1 = torch.tanh(torch.randn(R, ld, generator=g)).to(torch.bfloat16).cuda()
+    w2 = (torch.randn(3 * H, 32, 16, generator=g) * 0.25).cuda()
+    do = torch.randn(R, C, generator=g).to(torch.bfloat16).cuda()
+    o, lse = torch.zeros(R, C, dtype=torch.bfloat16, device="cuda"), torch.zeros(B * H * T, device="cuda")
+    dh1 = torch.zeros(R, ld, dtype=torch.bfloat16, device="cuda")
+    key, thr, c = (0xA77E1000 + T, DR.thr_of(p), DR.scale_of(p)) if p else (0, 0, 0.0)
+    dm = torch.zeros(L.mmt_op_attention_mask_dwords(B, H, T), dtype=torch.int32, device="cuda")
+    s = ML.stream_ptr("cuda")
+    if p:
+        ptrs = (ctypes.c_void_p * 8)(dm.data_ptr())
+        assert L.mmt_op_attention_mask(s, 1, B, T, H, (ctypes.c_int32 * 1)(1), (ctypes.c_uint32 * 1)(key),
+                                       (ctypes.c_uint32 * 1)(thr), ptrs) == 0
+    assert L.mmt_op_attention_fwd_h1_drop(s, B, T, H, ML.ptr(h1), ld, ML.ptr(w2), ML.ptr(o), C, ML.ptr(lse), key, thr, c,
+                                          ML.ptr(dm)) == 0
+    sums = []
+    for _ in range(2):  # the second run's sums are A's run-to-run figure
+        dw2, db1 = torch.zeros(3 * H, 32, 16, device="cuda"), torch.zeros(3 * H * 16, device="cuda")
+        assert L.mmt_op_attention_bwd_h1_drop(s, B, T, H, ML.ptr(h1), ld, ML.ptr(w2), ML.ptr(o), C, ML.ptr(lse), ML.ptr(do),
+                                              C, ML.ptr(dh1), ML.ptr(dw2), ML.ptr(db1), key, thr, c, ML.ptr(dm)) == 0
+        torch.cuda.synchronize()
+        sums.append((dw2, db1))
+    return {"o": o.float(), "lse": lse, "dh1": dh1.float(), "tol:dw2": sums[0][0], "tol:dw2.again": sums[1][0],
+            "tol:db1": sums[0][1], "tol:db1.again": sums[1][1]}
+
+
+def group_attn_ops():
+    """One forward and one backward per attention kernel family through the op entries, without and with dropout."""
+    out = {}
+    for p in (0.0, 0.1):
+        for ring in (0, 15, 47):  # hs 64: chunked, rings, one-pass (one stream)
+            for ns in (1, 3):
+                out[f"hs64.T160.ns{ns}.ring{ring}.p{p}"] = _attn_op(64, 160, ns, ring, p)
+        for T in (37, 256):       # hs 32: one-pass
+            out[f"hs32.T{T}.ns1.ring79.p{p}"] = _attn_op(32, T, 1, 79, p)
+        out[f"hs32.T100.ns3.ring207.scratch.p{p}"] = _attn_op(32, 100, 3, 79 | 128, p, scratch=True)
+        out[f"hs32.T300.ns3.ring79.p{p}"] = _attn_op(32, 300, 3, 79, p)  # the chunked pair at hs 32
+        out[f"hs16.T45.ns1.ring79.p{p}"] = _attn_op(16, 45, 1, 79, p)
+        out[f"h1.T37.p{p}"] = _attn_h1_op(37, p)
     return out
 
 

@@ -32,6 +32,7 @@
 
 #include "mmt_common.h"
 #include "mmt_kernels.h"
+#include "mmt_attn_plan.h"
 
 #include "mmt_attn_dev.h"
 
@@ -1355,21 +1356,36 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_fused32(AttnBatch batch, int 
   }  // streams
 }
 
-// attention variant knob (bit 0: the slice-streamed hs-64 dK/dV pass, bit 1: its dQ pass, bit 2: the
-// dK/dV pass at 3 waves per SIMD, bit 3: the slice-streamed hs-64 forward, bit 5: the one-pass hs-64
-// backward at T <= 512 with one KV stream, bit 6: the one-pass hs-32 backward at T <= 256, bit 7: that
-// kernel also for several KV streams): MMT_ATTN_RING, or mmt_attn_set_ring() for in-process A/B
-// default: both hs-64 passes on the rings (dQ: two query tiles per wave), dK/dV at 3 waves per SIMD
-// (standalone backward: target 277 -> 273 us, C3 cross-attention 2461 -> 2298, C4 2237 -> 2116;
-// C3 step -1.5 %: profiles/r3u_ring_ab.txt), and the forward on the ring too (round 4: target
-// 20.42 -> 20.34 ms, C3 157.3 -> 153.8 ms same box, profiles/r4m_ab.txt)
-// bit 6 (round 6): the one-pass hs-32 backward
-static int g_attn_ring = mmt_env_int("MMT_ATTN_RING", 15 | 64);
+// =============================================================================================
+// Host side: the knobs, the launch plan (mmt_attn_plan.h) and the launch switch. mmt_attn_plan and
+// mmt_attn_mask_plan are the only places that decide an attention or mask launch.
+// =============================================================================================
+// Every knob of the attention dispatch, read once when the library loads. DESIGN.md section 3 has the table.
+struct AttnKnobs {
+  // MMT_ATTN_RING / mmt_attn_set_ring (in-process A/B): bit 0 the slice-streamed hs-64 dK/dV pass, bit 1 the
+  // slice-streamed hs-64 dQ pass, bit 2 that dK/dV pass at 3 waves per SIMD (else 2), bit 3 the slice-streamed hs-64
+  // forward, bit 4 unused, bit 5 the one-pass hs-64 backward at T <= 512 with one KV stream, bit 6 the one-pass
+  // hs-32 backward at T <= 256, bit 7 that kernel also for several KV streams (with the fp32 dQ scratch)
+  int ring = mmt_env_int("MMT_ATTN_RING", 15 | 64);
+  // MMT_MASK_G: keep-bit tiles per wave of the mask kernel, 1, 2, 4, 8 or 16 (0: by T; another value: 8)
+  int mask_g = mmt_env_int("MMT_MASK_G", 0);
+  // mmt_attn_set_mask_g (no variable): the same, and ahead of MMT_MASK_G while it is not 0
+  int mask_g_rt = 0;
+};
+static AttnKnobs g_ak;
+
 extern "C" int mmt_attn_set_ring(int v) {
-  const int old = g_attn_ring;
-  g_attn_ring = v;
+  const int old = g_ak.ring;
+  g_ak.ring = v;
   return old;
 }
+extern "C" int mmt_attn_set_mask_g(int g) {
+  const int old = g_ak.mask_g_rt;
+  g_ak.mask_g_rt = g;
+  return old;
+}
+
+int64_t mmt_attn_q2_det_floats(int count, int B, int H) { return (int64_t)count * B * 3 * H * (512 + 16); }
 
 // the slice-streamed hs-64 kernels address a sequence's rows (and one (batch, head)'s keep-bit
 // records) with 32-bit per-lane offsets from a per-batch-row buffer base: a sequence whose span
@@ -1386,195 +1402,194 @@ static bool ring64_fits(const AttnBatch& bt, int T) {
   return true;
 }
 
-// the one-pass hs-32 backward (knob bit 6) takes the batch: T <= 256, Q / dO rows by LDS-DMA (16-B aligned
-// rows, sequences whose span fits a buffer descriptor); several KV streams only with knob bit 7 and the
-// fp32 dQ scratch. Every problem sets the Q/K/V stage-2 fields (AttnProblem::q2_*) or none does, and
-// only with one KV stream.
 // the on-chip Q/K/V fields of one problem (AttnProblem::oc_*): 8-B row pieces of h1, 16-B rows of W2
 static bool oc_ok(const AttnProblem& P) {
   return P.oc_h1 && P.oc_w2 && P.nstreams == 1 && !(P.oc_ld & 7) && !((uintptr_t)P.oc_h1 & 15) &&
          !((uintptr_t)P.oc_w2 & 15);
 }
 
-static bool fused32_ok(const AttnBatch& bt, int T, int ns) {
-  if (!(g_attn_ring & 64) || T > 256 || bt.count < 1) return false;
-  const bool q2 = bt.p[0].q2_w2 != nullptr;
-  if (q2 && ns > 1) return false;
-  bool ok = true;
-  for (int g = 0; g < bt.count; ++g) {
-    const AttnProblem& P = bt.p[g];
-    ok = ok && !(P.q_ld & 7) && !(P.dout_ld & 7) && !((uintptr_t)P.q & 15) && !((uintptr_t)P.dout & 15) &&
-         !(P.kv_ld & 7) && !(P.kv_hstride & 7) && (int64_t)T * std::max(P.q_ld, P.dout_ld) * 2 < ((int64_t)1 << 31);
+AttnPlan mmt_attn_plan(const AttnBatch& b, int B, int T, int H, int hs, bool bwd, int assume) {
+  AttnPlan p{};
+  p.status = ATTN_PLAN_EMPTY;
+  if (b.count == 0 || B == 0 || T == 0) return p;
+  p.status = ATTN_PLAN_INVALID;
+  for (int g = 0; g < b.count; ++g) {
+    if (b.p[g].nstreams < 1 || b.p[g].nstreams > MMT_MAX_STREAMS) return p;
+    for (int j = 0; j < b.p[g].nstreams && b.p[g].nstreams > 1; ++j)  // per-stream outputs (summed, and
+      if (!b.p[g].oj[j]) return p;                                      // read by the backward)
+    if (b.p[g].drop_thr)  // dropout reads the keep bits of mmt_launch_attn_mask
+      for (int j = 0; j < b.p[g].nstreams; ++j)
+        if (!b.p[g].dmask[j]) return p;
+    // one instantiation serves the whole batch, and the DROP one reads every problem's dmask: a batch that mixes
+    // dropout on and off is refused
+    if ((b.p[g].drop_thr != 0) != (b.p[0].drop_thr != 0)) return p;
+  }
+  for (int g = 0; g < b.count; ++g) {  // O / O_j leave the forward as 16-B row pieces
+    if (b.p[g].o_ld & 7 || ((uintptr_t)b.p[g].o & 15)) return p;
+    for (int j = 0; j < b.p[g].nstreams && b.p[g].nstreams > 1; ++j)
+      if ((uintptr_t)b.p[g].oj[j] & 15) return p;
+  }
+  if (bwd) {  // all problems in a bwd batch must share nstreams (grid.x = tiles * B*H*nstreams)
+    for (int g = 1; g < b.count; ++g)
+      if (b.p[g].nstreams != b.p[0].nstreams) return p;
+    // dQ, dK, dV leave the kernels as 16-B row pieces (8-element aligned rows and head offsets)
+    for (int g = 0; g < b.count; ++g) {
+      if ((b.p[g].dkv_ld & 7) || (b.p[g].dkv_hstride & 7)) return p;
+      if ((b.p[g].dq_ld & 7) || ((uintptr_t)b.p[g].dq & 15)) return p;
+      for (int j = 0; j < b.p[g].nstreams; ++j)
+        if (((uintptr_t)b.p[g].dk[j] | (uintptr_t)b.p[g].dv[j]) & 15) return p;
+    }
+  }
+  if (!attn_hs_built(hs)) return p;
+
+  const int ring_kn = g_ak.ring;
+  const bool drop = b.p[0].drop_thr != 0;
+  const int nt = (T + 31) / 32, nb = (nt + 7) / 8, ns = b.p[0].nstreams;
+  const auto set = [&](int i, int family, int gx) -> AttnLaunch& {
+    AttnLaunch& l = p.l[i];
+    l.family = family; l.hs = hs; l.drop = drop; l.gx = gx; l.gy = 1; l.gz = b.count; l.wg = 256;
+    p.nlaunch = i + 1;
+    return l;
+  };
+  // hs 64: the slice-streamed kernels (mmt_attn2.hip). Default: both backward passes on the rings (dQ: two query
+  // tiles per wave), dK/dV at 3 waves per SIMD (standalone backward: target 277 -> 273 us, C3 cross-attention
+  // 2461 -> 2298, C4 2237 -> 2116; C3 step -1.5 %: profiles/r3u_ring_ab.txt), and the forward on the ring too
+  // (round 4: target 20.42 -> 20.34 ms, C3 157.3 -> 153.8 ms same box, profiles/r4m_ab.txt). MMT_ATTN_RING=0 keeps
+  // the chunked ones.
+  // ring depth 4 (three slices in flight): depth 6 measured slower (target backward 294 -> 301 us, C4
+  // 2315 -> 2394 us: profiles/r3e_ring_slots_ab.txt); a one-query-tile-per-wave dQ ring equal at the
+  // target and slower at C3, 8 key tiles per dK/dV workgroup slower at C3 / C4
+  // (profiles/r3h_dkdv_waves_ab.txt), two plain dK/dV slices per barrier slower at C3 / C4
+  // (profiles/r3u_ring_ab.txt): those variants were removed in round 4.
+  const bool ring = hs == 64 && ring64_fits(b, T);
+  if (!bwd) {
+    bool oc = false;
+    for (int g = 0; g < b.count; ++g) oc = oc || b.p[g].oc_w2 != nullptr;
+    if (ring && (ring_kn & 8)) {  // knob bit 3: the forward on the LDS-DMA slice ring
+      set(0, ATTN_RING64_FWD, nb * B * H).depth = 4;
+    } else if (oc) {  // on-chip Q/K/V (AttnProblem::oc_*): hs 32, T <= 256, one stream, every problem; refused otherwise
+      for (int g = 0; g < b.count; ++g)
+        if (hs != 32 || T > 256 || !oc_ok(b.p[g])) return p;
+      set(0, ATTN_OC32_FWD, B * H);
+    } else {
+      set(0, ATTN_CHUNK_FWD, nb * B * H);
+    }
+    p.status = ATTN_PLAN_OK;
+    return p;
+  }
+  // The one-pass hs-32 backward (knob bit 6, round 6) takes the batch: T <= 256, Q / dO rows by LDS-DMA (16-B aligned
+  // rows, sequences whose span fits a buffer descriptor); several KV streams only with knob bit 7 and the fp32 dQ
+  // scratch. Every problem sets the Q/K/V stage-2 fields (AttnProblem::q2_*) or none does, and only with one KV
+  // stream. Pointers count only as "field present" and by their alignment; ATTN_ASSUME_Q2 takes the stage-2 fields
+  // as present and aligned.
+  const bool a2 = (assume & ATTN_ASSUME_Q2) != 0;
+  const bool q2 = a2 || b.p[0].q2_w2 != nullptr;
+  const bool oc = b.p[0].oc_w2 != nullptr;
+  bool f32 = hs == 32 && (ring_kn & 64) && T <= 256 && !(q2 && ns > 1);
+  for (int g = 0; g < b.count && f32; ++g) {
+    const AttnProblem& P = b.p[g];
+    f32 = !(P.q_ld & 7) && !(P.dout_ld & 7) && !((uintptr_t)P.q & 15) && !((uintptr_t)P.dout & 15) && !(P.kv_ld & 7) &&
+          !(P.kv_hstride & 7) && (int64_t)T * std::max(P.q_ld, P.dout_ld) * 2 < ((int64_t)1 << 31);
     // several KV streams (knob bit 7, off by default): one workgroup walks the streams in turn, and at
     // C1's cross-attention (3 streams, 512 workgroups: one generation) that measured slower than the
     // two-pass pair, which spreads the dK/dV pass over 3x the workgroups (70.7 vs 67.9 us standalone,
     // tools/attn_bench.py c1_ca)
     if (ns > 1)
-      ok = ok && (g_attn_ring & 128) && P.dq32 && !(P.dq32_ld & 3) && !((uintptr_t)P.dq32 & 15) &&
-           (int64_t)T * P.dq32_ld * 4 < ((int64_t)1 << 31);
+      f32 = f32 && (ring_kn & 128) && P.dq32 && !(P.dq32_ld & 3) && !((uintptr_t)P.dq32 & 15) &&
+            (int64_t)T * P.dq32_ld * 4 < ((int64_t)1 << 31);
     // one stream without the stage-2 fields: dQ rows leave as 8-B pieces
-    if (ns == 1 && !q2) ok = ok && !(P.dq_ld & 3) && !((uintptr_t)P.dq & 7);
-    if ((P.q2_w2 != nullptr) != q2) return false;
-    if (q2)
-      ok = ok && P.q2_h1 && P.q2_dh1 && P.q2_dw2 && P.q2_db1 && !(P.q2_ld & 7) && !((uintptr_t)P.q2_h1 & 15) &&
-           !((uintptr_t)P.q2_dh1 & 7);
+    if (ns == 1 && !q2) f32 = f32 && !(P.dq_ld & 3) && !((uintptr_t)P.dq & 7);
+    if (!a2) {
+      f32 = f32 && (P.q2_w2 != nullptr) == q2;
+      if (q2)
+        f32 = f32 && P.q2_h1 && P.q2_dh1 && P.q2_dw2 && P.q2_db1 && !(P.q2_ld & 7) && !((uintptr_t)P.q2_h1 & 15) &&
+              !((uintptr_t)P.q2_dh1 & 7);
+    }
     // on-chip Q/K/V: every problem or none, and only beside the stage-2 backward
-    if ((P.oc_w2 != nullptr) != (bt.p[0].oc_w2 != nullptr)) return false;
-    if (P.oc_w2) ok = ok && q2 && oc_ok(P);
+    f32 = f32 && (P.oc_w2 != nullptr) == oc && (!oc || (q2 && oc_ok(P)));
   }
-  return ok;
-}
-
-bool mmt_attn_bwd_fuses_qkv2(const AttnBatch& bt, int T, int hs) {
-  if (hs != 32 || bt.count < 1) return false;
-  for (int g = 0; g < bt.count; ++g)
-    if (bt.p[g].nstreams != 1) return false;
-  AttnBatch t = bt;  // as the launch will see it with the stage-2 fields set
-  for (int g = 0; g < t.count; ++g) {
-    AttnProblem& P = t.p[g];
-    P.q2_w2 = reinterpret_cast<const float*>(16); P.q2_h1 = reinterpret_cast<const bf16_t*>(16);
-    P.q2_dh1 = reinterpret_cast<bf16_t*>(16); P.q2_dw2 = reinterpret_cast<float*>(16); P.q2_db1 = P.q2_dw2;
-    P.q2_ld = 8;
-  }
-  return fused32_ok(t, T, 1);
-}
-
-int64_t mmt_attn_q2_det_floats(int count, int B, int H) { return (int64_t)count * B * 3 * H * (512 + 16); }
-
-template <int HS>
-static hipError_t attn_launch(const AttnBatch& bt, int B, int T, int H, float scale, bool bwd, hipStream_t s) {
-  const int nb = ((T + 31) / 32 + 7) / 8;
-  if (!bwd) {
-    bool drop = false;
-    for (int g = 0; g < bt.count; ++g) drop = drop || bt.p[g].drop_thr != 0;
-    // hs 64, knob bit 3: the forward on the LDS-DMA slice ring (mmt_attn2.hip)
-    if (HS == 64 && (g_attn_ring & 8) && ring64_fits(bt, T)) return mmt_attn_fwd_ring64(bt, B, T, H, scale, drop, s);
-    const dim3 grid(nb * B * H, 1, bt.count);
-    // on-chip Q/K/V (AttnProblem::oc_*): hs 32, T <= 256, one stream, every problem; refused otherwise
-    bool oc = false;
-    for (int g = 0; g < bt.count; ++g) oc = oc || bt.p[g].oc_w2 != nullptr;
-    if (oc) {
-      for (int g = 0; g < bt.count; ++g)
-        if (HS != 32 || T > 256 || !oc_ok(bt.p[g])) return hipErrorInvalidValue;
-      return mmt_attn_fwd_oc32(bt, B, T, H, scale, drop, s);  // (mmt_attn_oc.hip)
-    }
-    if (drop) hipLaunchKernelGGL((attn_fwd_kernel<HS, true>), grid, dim3(256), 0, s, bt, T, H, scale);
-    else hipLaunchKernelGGL((attn_fwd_kernel<HS, false>), grid, dim3(256), 0, s, bt, T, H, scale);
+  // the stage-2 fields are a promise that the fused kernel writes dh1 / dW2 / db1 (and not dq / dk / dv):
+  // refused rather than dropped when it cannot run (mmt_attn_bwd_fuses_qkv2 decides beforehand)
+  for (int g = 0; g < b.count; ++g)
+    if ((a2 || b.p[g].q2_w2 || b.p[g].oc_w2) && !f32) return p;
+  p.status = ATTN_PLAN_OK;
+  if (ring && (ring_kn & 32) && T <= 512 && ns == 1) {  // knob bit 5: dQ, dK, dV in one pass at hs 64
+    set(0, ATTN_FUSED64, B * H).depth = 3;
+  } else if (f32) {  // knob bit 6: dQ, dK, dV in one pass at hs 32
+    AttnLaunch& l = set(0, ATTN_FUSED32, B * H);
+    l.ms = ns > 1; l.q2 = q2; l.oc = oc;  // (oc: Q / K / V made in the prologue; only with q2)
+    // deterministic mode: the stage-2 sums as per-batch-element partials, dW2 [B][3 H * 512] then db1
+    // [B][3 H * 16] per problem, + the ordered sum
+    l.det = q2 && b.det.base != nullptr;
+    const int64_t stride = l.det ? mmt_attn_q2_det_floats(1, B, H) : 0;
+    p.det_stride[0] = (int)(uint32_t)stride; p.det_stride[1] = (int)(stride >> 32);
   } else {
-    const int ns = bt.p[0].nstreams;
-    bool drop = false;
-    for (int g = 0; g < bt.count; ++g) drop = drop || bt.p[g].drop_thr != 0;
-    // the stage-2 fields are a promise that the fused kernel writes dh1 / dW2 / db1 (and not dq / dk / dv):
-    // refused rather than dropped when it cannot run (mmt_attn_bwd_fuses_qkv2 decides beforehand)
-    for (int g = 0; g < bt.count; ++g)
-      if ((bt.p[g].q2_w2 || bt.p[g].oc_w2) && (HS != 32 || !fused32_ok(bt, T, ns))) return hipErrorInvalidValue;
-    // hs 64: the slice-streamed kernels (mmt_attn2.hip): bit 1 of the knob the dQ pass, bit 0 the
-    // dK/dV pass; MMT_ATTN_RING=0 (or mmt_attn_set_ring(0)) keeps the chunked ones
-    const bool ring = HS == 64 && ring64_fits(bt, T);
-    // knob bit 5: dQ, dK, dV in one pass (mmt_attn2.hip) for T <= 512 and one KV stream
-    if (ring && (g_attn_ring & 32) && T <= 512 && ns == 1) return mmt_attn_bwd_fused64(bt, B, T, H, scale, drop, s);
-    // knob bit 6: dQ, dK, dV in one pass at hs 32 for T <= 256 (fused32_ok)
-    if (HS == 32 && fused32_ok(bt, T, ns)) {
-      const dim3 grid(B * H, 1, bt.count);
-      const bool q2 = bt.p[0].q2_w2 != nullptr;
-      const bool oc = bt.p[0].oc_w2 != nullptr;  // Q / K / V made in the prologue (fused32_ok: only with q2)
-      if (ns > 1) {
-        if (drop) hipLaunchKernelGGL((attn_bwd_fused32<true, true, false>), grid, dim3(256), 0, s, bt, T, H, scale);
-        else hipLaunchKernelGGL((attn_bwd_fused32<false, true, false>), grid, dim3(256), 0, s, bt, T, H, scale);
-      } else if (q2 && bt.det.base) {
-        // deterministic mode: the stage-2 sums as per-batch-element partials, dW2 [B][3 H * 512] then db1
-        // [B][3 H * 16] per problem, + the ordered sum
-        AttnBatch d = bt;
-        d.det.stride = mmt_attn_q2_det_floats(1, B, H);
-        DetLaunch L;
-        hipError_t e = L.begin(d.det, d.count, d.det.stride, s);
-        if (e != hipSuccess) return e;
-        if (oc && drop) hipLaunchKernelGGL((attn_bwd_fused32<true, false, true, true, true>), grid, dim3(256), 0, s, d, T, H, scale);
-        else if (oc) hipLaunchKernelGGL((attn_bwd_fused32<false, false, true, true, true>), grid, dim3(256), 0, s, d, T, H, scale);
-        else if (drop) hipLaunchKernelGGL((attn_bwd_fused32<true, false, true, true>), grid, dim3(256), 0, s, d, T, H, scale);
-        else hipLaunchKernelGGL((attn_bwd_fused32<false, false, true, true>), grid, dim3(256), 0, s, d, T, H, scale);
-        e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        for (int g = 0; g < d.count; ++g) {
-          L.seg(g, d.det.stride, 0, d.p[g].q2_dw2, B, 3 * H * 512);
-          L.seg(g, d.det.stride, (int64_t)B * 3 * H * 512, d.p[g].q2_db1, B, 3 * H * 16);
-        }
-        return L.finish();
-      } else if (q2) {
-        if (oc && drop) hipLaunchKernelGGL((attn_bwd_fused32<true, false, true, false, true>), grid, dim3(256), 0, s, bt, T, H, scale);
-        else if (oc) hipLaunchKernelGGL((attn_bwd_fused32<false, false, true, false, true>), grid, dim3(256), 0, s, bt, T, H, scale);
-        else if (drop) hipLaunchKernelGGL((attn_bwd_fused32<true, false, true>), grid, dim3(256), 0, s, bt, T, H, scale);
-        else hipLaunchKernelGGL((attn_bwd_fused32<false, false, true>), grid, dim3(256), 0, s, bt, T, H, scale);
-      } else {
-        if (drop) hipLaunchKernelGGL((attn_bwd_fused32<true, false, false>), grid, dim3(256), 0, s, bt, T, H, scale);
-        else hipLaunchKernelGGL((attn_bwd_fused32<false, false, false>), grid, dim3(256), 0, s, bt, T, H, scale);
-      }
-      return hipGetLastError();
+    // knob bit 1: the dQ pass on its ring; bit 0: the dK/dV pass, bit 2: at 3 waves per SIMD (<= 168 VGPRs)
+    if (ring && (ring_kn & 2)) set(0, ATTN_RING64_DQ, nb * B * H).depth = 4;  // two query tiles per wave (8 per workgroup)
+    else set(0, ATTN_CHUNK_DQ, nb * B * H);
+    if (ring && (ring_kn & 1)) {
+      AttnLaunch& l = set(1, ATTN_RING64_DKDV, ((nt + 3) / 4) * B * H * ns);
+      l.occ = (ring_kn & 4) ? 3 : 2; l.depth = 4;
+    } else {
+      // dK/dV: one key tile per wave at 2 waves per SIMD (a paired two-key-tile walk at one wave per
+      // SIMD measured slower: C1 103 vs 127 us, target step 25.4 vs 25.9 ms; removed in round 4)
+      set(1, ATTN_CHUNK_DKDV, nb * B * H * ns);
     }
-    if (ring && (g_attn_ring & 2)) {
-      const hipError_t e = mmt_attn_bwd_dq_ring64(bt, B, T, H, scale, drop, s);
-      if (e != hipSuccess) return e;  // (hipGetLastError cleared it: report it here)
-    } else if (drop) hipLaunchKernelGGL((attn_bwd_dq_kernel<HS, true>), dim3(nb * B * H, 1, bt.count), dim3(256), 0, s, bt, T, H, scale);
-    else hipLaunchKernelGGL((attn_bwd_dq_kernel<HS, false>), dim3(nb * B * H, 1, bt.count), dim3(256), 0, s, bt, T, H, scale);
-    if (ring && (g_attn_ring & 1)) return mmt_attn_bwd_dkdv_ring64(bt, B, T, H, scale, drop, g_attn_ring, s);
-    // dK/dV: one key tile per wave at 2 waves per SIMD (a paired two-key-tile walk at one wave per
-    // SIMD measured slower: C1 103 vs 127 us, target step 25.4 vs 25.9 ms; removed in round 4)
-    if (drop)
-      hipLaunchKernelGGL((attn_bwd_dkdv1_kernel<HS, true>), dim3(nb * B * H * ns, 1, bt.count), dim3(256), 0, s, bt, T, H,
-                         scale);
-    else
-      hipLaunchKernelGGL((attn_bwd_dkdv1_kernel<HS, false>), dim3(nb * B * H * ns, 1, bt.count), dim3(256), 0, s, bt, T,
-                         H, scale);
+  }
+  return p;
+}
+
+// launches one entry of the plan: the kernels of this file here, the others in their own translation units
+static hipError_t launch_plan(const AttnBatch& bt, const AttnLaunch& l, int T, int H, float scale, hipStream_t s) {
+  const dim3 grid(l.gx, l.gy, l.gz), wg(l.wg);
+  switch (attn_key(l)) {
+#define X(HS)                                                                                             \
+  case attn_key(ATTN_CHUNK_FWD, HS, false): hipLaunchKernelGGL((attn_fwd_kernel<HS, false>), grid, wg, 0, s, bt, T, H, scale); break; \
+  case attn_key(ATTN_CHUNK_FWD, HS, true): hipLaunchKernelGGL((attn_fwd_kernel<HS, true>), grid, wg, 0, s, bt, T, H, scale); break; \
+  case attn_key(ATTN_CHUNK_DQ, HS, false): hipLaunchKernelGGL((attn_bwd_dq_kernel<HS, false>), grid, wg, 0, s, bt, T, H, scale); break; \
+  case attn_key(ATTN_CHUNK_DQ, HS, true): hipLaunchKernelGGL((attn_bwd_dq_kernel<HS, true>), grid, wg, 0, s, bt, T, H, scale); break; \
+  case attn_key(ATTN_CHUNK_DKDV, HS, false): hipLaunchKernelGGL((attn_bwd_dkdv1_kernel<HS, false>), grid, wg, 0, s, bt, T, H, scale); break; \
+  case attn_key(ATTN_CHUNK_DKDV, HS, true): hipLaunchKernelGGL((attn_bwd_dkdv1_kernel<HS, true>), grid, wg, 0, s, bt, T, H, scale); break;
+    ATTN_CHUNK_HS(X)
+#undef X
+#define X(D, MS, Q2, DET, OC)                                                                             \
+  case attn_key(ATTN_FUSED32, 0, D, MS, Q2, DET, OC):                                                      \
+    hipLaunchKernelGGL((attn_bwd_fused32<D, MS, Q2, DET, OC>), grid, wg, 0, s, bt, T, H, scale); break;
+    ATTN_FUSED32_OPS(X)
+#undef X
+    default:
+      if (l.family == ATTN_OC32_FWD) return mmt_attn_oc_launch_plan(bt, l, T, H, scale, s);
+      return mmt_attn2_launch_plan(bt, l, T, H, scale, s);
   }
   return hipGetLastError();
 }
 
-static hipError_t attn_dispatch(const AttnBatch& b, int B, int T, int H, int hs, float scale, bool bwd,
-                                hipStream_t s) {
-  if (b.count == 0 || B == 0 || T == 0) return hipSuccess;
-  for (int g = 0; g < b.count; ++g) {
-    if (b.p[g].nstreams < 1 || b.p[g].nstreams > MMT_MAX_STREAMS) return hipErrorInvalidValue;
-    for (int j = 0; j < b.p[g].nstreams && b.p[g].nstreams > 1; ++j)  // per-stream outputs (summed, and
-      if (!b.p[g].oj[j]) return hipErrorInvalidValue;                   // read by the backward)
-    if (b.p[g].drop_thr)  // dropout reads the keep bits of mmt_launch_attn_mask
-      for (int j = 0; j < b.p[g].nstreams; ++j)
-        if (!b.p[g].dmask[j]) return hipErrorInvalidValue;
-    // one instantiation serves the whole batch (attn_launch: DROP if any problem drops), and the DROP one
-    // reads every problem's dmask: a batch that mixes dropout on and off is refused
-    if ((b.p[g].drop_thr != 0) != (b.p[0].drop_thr != 0)) return hipErrorInvalidValue;
-  }
-  for (int g = 0; g < b.count; ++g) {  // O / O_j leave the forward as 16-B row pieces
-    if (b.p[g].o_ld & 7 || ((uintptr_t)b.p[g].o & 15)) return hipErrorInvalidValue;
-    for (int j = 0; j < b.p[g].nstreams && b.p[g].nstreams > 1; ++j)
-      if ((uintptr_t)b.p[g].oj[j] & 15) return hipErrorInvalidValue;
-  }
-  if (bwd) {  // all problems in a bwd batch must share nstreams (grid.y = B*H*nstreams)
-    for (int g = 1; g < b.count; ++g)
-      if (b.p[g].nstreams != b.p[0].nstreams) return hipErrorInvalidValue;
-    // dQ, dK, dV leave the kernels as 16-B row pieces (8-element aligned rows and head offsets)
-    for (int g = 0; g < b.count; ++g) {
-      if ((b.p[g].dkv_ld & 7) || (b.p[g].dkv_hstride & 7)) return hipErrorInvalidValue;
-      if ((b.p[g].dq_ld & 7) || ((uintptr_t)b.p[g].dq & 15)) return hipErrorInvalidValue;
-      for (int j = 0; j < b.p[g].nstreams; ++j)
-        if (((uintptr_t)b.p[g].dk[j] | (uintptr_t)b.p[g].dv[j]) & 15) return hipErrorInvalidValue;
+static hipError_t attn_run(const AttnBatch& b, int B, int T, int H, int hs, float scale, bool bwd, hipStream_t s) {
+  const AttnPlan p = mmt_attn_plan(b, B, T, H, hs, bwd);
+  if (p.status != ATTN_PLAN_OK) return p.status == ATTN_PLAN_EMPTY ? hipSuccess : hipErrorInvalidValue;
+  if (p.l[0].det) {  // the partials' region, the launch, then the ordered sums of every problem's dW2 and db1
+    AttnBatch d = b;
+    d.det.stride = attn_det_stride(p);
+    DetLaunch L;
+    hipError_t e = L.begin(d.det, d.count, d.det.stride, s);
+    if (e == hipSuccess) e = launch_plan(d, p.l[0], T, H, scale, s);
+    if (e != hipSuccess) return e;
+    for (int g = 0; g < d.count; ++g) {
+      L.seg(g, d.det.stride, 0, d.p[g].q2_dw2, B, 3 * H * 512);
+      L.seg(g, d.det.stride, (int64_t)B * 3 * H * 512, d.p[g].q2_db1, B, 3 * H * 16);
     }
+    return L.finish();
   }
-  switch (hs) {
-    case 8: return attn_launch<8>(b, B, T, H, scale, bwd, s);
-    case 16: return attn_launch<16>(b, B, T, H, scale, bwd, s);
-    case 24: return attn_launch<24>(b, B, T, H, scale, bwd, s);
-    case 32: return attn_launch<32>(b, B, T, H, scale, bwd, s);
-    case 48: return attn_launch<48>(b, B, T, H, scale, bwd, s);
-    case 64: return attn_launch<64>(b, B, T, H, scale, bwd, s);
-    default: return hipErrorInvalidValue;
-  }
+  hipError_t e = hipSuccess;
+  for (int i = 0; i < p.nlaunch && e == hipSuccess; ++i) e = launch_plan(b, p.l[i], T, H, scale, s);
+  return e;
 }
 
 hipError_t mmt_launch_attn_fwd(const AttnBatch& b, int B, int T, int H, int hs, float scale, hipStream_t s) {
-  return attn_dispatch(b, B, T, H, hs, scale, false, s);
+  return attn_run(b, B, T, H, hs, scale, false, s);
 }
 hipError_t mmt_launch_attn_bwd(const AttnBatch& b, int B, int T, int H, int hs, float scale, hipStream_t s) {
-  return attn_dispatch(b, B, T, H, hs, scale, true, s);
+  return attn_run(b, B, T, H, hs, scale, true, s);
 }
 
 // =============================================================================================
@@ -1663,44 +1678,52 @@ __global__ __launch_bounds__(256) void attn_mask_kernel(AttnBatch batch, int BH,
   }
 }
 
-static int g_mask_g_rt = 0;
-extern "C" int mmt_attn_set_mask_g(int g) {
-  const int old = g_mask_g_rt;
-  g_mask_g_rt = g;
-  return old;
-}
-
-hipError_t mmt_launch_attn_mask(const AttnBatch& b, int B, int T, int H, hipStream_t s) {
-  if (b.count == 0 || B == 0 || T == 0) return hipSuccess;
+AttnPlan mmt_attn_mask_plan(const AttnBatch& b, int B, int T, int H) {
+  AttnPlan p{};
+  p.status = ATTN_PLAN_EMPTY;
+  if (b.count == 0 || B == 0 || T == 0) return p;
+  p.status = ATTN_PLAN_INVALID;
   int ns = 0;
   for (int g = 0; g < b.count; ++g) {
     const AttnProblem& P = b.p[g];
     if (!P.drop_thr) continue;
-    if (P.nstreams < 1 || P.nstreams > MMT_MAX_STREAMS) return hipErrorInvalidValue;
+    if (P.nstreams < 1 || P.nstreams > MMT_MAX_STREAMS) return p;
     for (int j = 0; j < P.nstreams; ++j)
-      if (!P.dmask[j]) return hipErrorInvalidValue;
+      if (!P.dmask[j]) return p;
     ns = P.nstreams > ns ? P.nstreams : ns;
   }
-  if (ns == 0) return hipSuccess;
-  const int64_t nt = (T + 31) / 32;
-  const int64_t tiles = (int64_t)B * H * (nt * (nt + 1) / 2) * ns;
-  // tiles per wave (MMT_MASK_G or mmt_attn_set_mask_g: 1, 2, 4, 8 or 16)
-  static const int g_env = mmt_env_int("MMT_MASK_G", 0);
+  if (ns == 0) {  // no problem drops
+    p.status = ATTN_PLAN_EMPTY;
+    return p;
+  }
+  const int64_t tiles = mmt_attn_mask_tiles(B, H, T) * ns;
+  // tiles per wave, by default:
   // (16 against 8 at T = 1024 / 4096: C3 140.3-140.4 -> 139.3-140.0 ms, C4 319.4-319.5 -> 317.6-318.7; at C1
   // (T = 256) equal within noise, so 8 below T = 1024: profiles/r6aq_mask_g16_ab.txt)
-  const int g_def = T >= 1024 ? 16 : 8;
   // (8 against 4: C3 142.3 -> 140.9-141.1 ms, C1 / target equal; 4 against 1, the one-tile form: C3 149.2 ->
   // 143.7, target 19.40 -> 19.24, C1 7.98 -> 7.91: profiles/r6aa_mask_pileup.txt, r6ab_mask_ab.txt)
-  const int gv = g_mask_g_rt ? g_mask_g_rt : g_env ? g_env : g_def;
-  const int g = (gv == 1 || gv == 2 || gv == 4 || gv == 16) ? gv : 8;
-  const int64_t waves = (tiles + g - 1) / g;
-  const dim3 grid((unsigned)((waves + 3) / 4), 1, b.count);
-  switch (g) {
-    case 1: hipLaunchKernelGGL(attn_mask_kernel<1>, grid, dim3(256), 0, s, b, B * H, T); break;
-    case 2: hipLaunchKernelGGL(attn_mask_kernel<2>, grid, dim3(256), 0, s, b, B * H, T); break;
-    case 4: hipLaunchKernelGGL(attn_mask_kernel<4>, grid, dim3(256), 0, s, b, B * H, T); break;
-    case 16: hipLaunchKernelGGL(attn_mask_kernel<16>, grid, dim3(256), 0, s, b, B * H, T); break;
-    default: hipLaunchKernelGGL(attn_mask_kernel<8>, grid, dim3(256), 0, s, b, B * H, T); break;
+  const int gv = g_ak.mask_g_rt ? g_ak.mask_g_rt : g_ak.mask_g ? g_ak.mask_g : T >= 1024 ? 16 : 8;
+  AttnLaunch& l = p.l[0];
+  l.family = ATTN_MASK;
+  l.g = (gv == 1 || gv == 2 || gv == 4 || gv == 16) ? gv : 8;
+  const int64_t waves = (tiles + l.g - 1) / l.g;
+  l.gx = (int)(unsigned)((waves + 3) / 4); l.gy = 1; l.gz = b.count; l.wg = 256;
+  p.nlaunch = 1;
+  p.status = ATTN_PLAN_OK;
+  return p;
+}
+
+hipError_t mmt_launch_attn_mask(const AttnBatch& b, int B, int T, int H, hipStream_t s) {
+  const AttnPlan p = mmt_attn_mask_plan(b, B, T, H);
+  if (p.status != ATTN_PLAN_OK) return p.status == ATTN_PLAN_EMPTY ? hipSuccess : hipErrorInvalidValue;
+  const AttnLaunch& l = p.l[0];
+  const dim3 grid((unsigned)l.gx, l.gy, l.gz), wg(l.wg);
+  switch (attn_key(l)) {
+#define X(G) \
+  case attn_key(ATTN_MASK, G, false): hipLaunchKernelGGL(attn_mask_kernel<G>, grid, wg, 0, s, b, B * H, T); break;
+    ATTN_MASK_G(X)
+#undef X
+    default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
 }

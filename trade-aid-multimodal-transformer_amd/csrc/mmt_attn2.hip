@@ -21,6 +21,7 @@
 // so the slice loop carries almost no address arithmetic.
 #include "mmt_common.h"
 #include "mmt_kernels.h"
+#include "mmt_attn_plan.h"
 
 namespace {
 
@@ -1159,47 +1160,26 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_fused64(AttnBatch batch, int 
   }
 }
 
-hipError_t mmt_attn_bwd_fused64(const AttnBatch& bt, int B, int T, int H, float scale, bool drop, hipStream_t s) {
-  if (T > 512 || bt.p[0].nstreams != 1) return hipErrorInvalidValue;
-  const dim3 grid(B * H, 1, bt.count);
-  if (drop) hipLaunchKernelGGL((attn_bwd_fused64<true, 3>), grid, dim3(256), 0, s, bt, T, H, scale);
-  else hipLaunchKernelGGL((attn_bwd_fused64<false, 3>), grid, dim3(256), 0, s, bt, T, H, scale);
-  return hipGetLastError();
-}
-
-hipError_t mmt_attn_fwd_ring64(const AttnBatch& bt, int B, int T, int H, float scale, bool drop, hipStream_t s) {
-  const int nt = (T + 31) / 32;
-  const dim3 g2(((nt + 7) / 8) * B * H, 1, bt.count);
-  if (drop) hipLaunchKernelGGL((attn_fwd_ring64x2<true, 4>), g2, dim3(256), 0, s, bt, T, H, scale);
-  else hipLaunchKernelGGL((attn_fwd_ring64x2<false, 4>), g2, dim3(256), 0, s, bt, T, H, scale);
-  return hipGetLastError();
-}
-
-// ring depth 4 (three slices in flight): depth 6 measured slower (target backward 294 -> 301 us, C4
-// 2315 -> 2394 us: profiles/r3e_ring_slots_ab.txt); a one-query-tile-per-wave dQ ring equal at the
-// target and slower at C3, 8 key tiles per dK/dV workgroup slower at C3 / C4
-// (profiles/r3h_dkdv_waves_ab.txt), two plain dK/dV slices per barrier slower at C3 / C4
-// (profiles/r3u_ring_ab.txt): those variants were removed in round 4.
-hipError_t mmt_attn_bwd_dq_ring64(const AttnBatch& bt, int B, int T, int H, float scale, bool drop, hipStream_t s) {
-  const int nt = (T + 31) / 32;
-  const dim3 g2(((nt + 7) / 8) * B * H, 1, bt.count);  // two query tiles per wave (8 per workgroup)
-  if (drop) hipLaunchKernelGGL((attn_bwd_dq_ring64x2<true, 4>), g2, dim3(256), 0, s, bt, T, H, scale);
-  else hipLaunchKernelGGL((attn_bwd_dq_ring64x2<false, 4>), g2, dim3(256), 0, s, bt, T, H, scale);
-  return hipGetLastError();
-}
-
-// variant bit 2: 3 waves per SIMD (<= 168 VGPRs; the default), else 2
-hipError_t mmt_attn_bwd_dkdv_ring64(const AttnBatch& bt, int B, int T, int H, float scale, bool drop, int variant,
-                                    hipStream_t s) {
-  const int nt = (T + 31) / 32;
-  const bool occ3 = (variant & 4) != 0;
-  const dim3 grid(((nt + 3) / 4) * B * H * bt.p[0].nstreams, 1, bt.count);
-  if (occ3) {
-    if (drop) hipLaunchKernelGGL((attn_bwd_dkdv_ring64<true, 3, 4, 4>), grid, dim3(256), 0, s, bt, T, H, scale);
-    else hipLaunchKernelGGL((attn_bwd_dkdv_ring64<false, 3, 4, 4>), grid, dim3(256), 0, s, bt, T, H, scale);
-  } else {
-    if (drop) hipLaunchKernelGGL((attn_bwd_dkdv_ring64<true, 2, 4, 4>), grid, dim3(256), 0, s, bt, T, H, scale);
-    else hipLaunchKernelGGL((attn_bwd_dkdv_ring64<false, 2, 4, 4>), grid, dim3(256), 0, s, bt, T, H, scale);
+// launches the plan's entry of this file's kernels (mmt_attn_plan decided it and sized the grid)
+hipError_t mmt_attn2_launch_plan(const AttnBatch& bt, const AttnLaunch& l, int T, int H, float scale, hipStream_t s) {
+  const dim3 grid(l.gx, l.gy, l.gz), wg(l.wg);
+#define GO(K) hipLaunchKernelGGL(K, grid, wg, 0, s, bt, T, H, scale); break
+  switch (attn_key(l)) {
+#define X(D, S) case attn_key(ATTN_RING64_FWD, S, D): GO((attn_fwd_ring64x2<D, S>));
+    ATTN_RING64_FWD_OPS(X)
+#undef X
+#define X(D, S) case attn_key(ATTN_RING64_DQ, S, D): GO((attn_bwd_dq_ring64x2<D, S>));
+    ATTN_RING64_DQ_OPS(X)
+#undef X
+#define X(D, OCC, S) \
+  case attn_key(ATTN_RING64_DKDV, S, D, false, false, false, false, OCC): GO((attn_bwd_dkdv_ring64<D, OCC, S, 4>));
+    ATTN_RING64_DKDV_OPS(X)
+#undef X
+#define X(D, S) case attn_key(ATTN_FUSED64, S, D): GO((attn_bwd_fused64<D, S>));
+    ATTN_FUSED64_OPS(X)
+#undef X
+    default: return hipErrorInvalidValue;
   }
+#undef GO
   return hipGetLastError();
 }

@@ -3,6 +3,7 @@
 // attn_fwd_kernel<32, true> (the cross-attention's and the eval forward's kernel, whose text did not change) 171
 // VGPRs instead of 167, past the 168 that three waves per SIMD allow.
 #include "mmt_attn_dev.h"
+#include "mmt_attn_plan.h"
 
 // =============================================================================================
 // forward at hs 32, T <= 256, one KV stream, with Q / K / V made on chip (AttnProblem::oc_*): grid (B*H, 1, G),
@@ -120,10 +121,15 @@ __global__ __launch_bounds__(256, MMT_FWD_MINB(32)) void attn_fwd_oc32_kernel(At
 }
 
 
-hipError_t mmt_attn_fwd_oc32(const AttnBatch& b, int B, int T, int H, float scale, bool drop, hipStream_t s) {
-  if (T > 256 || b.count < 1) return hipErrorInvalidValue;
-  const dim3 grid(B * H, 1, b.count);
-  if (drop) hipLaunchKernelGGL((attn_fwd_oc32_kernel<true>), grid, dim3(256), 0, s, b, T, H, scale);
-  else hipLaunchKernelGGL((attn_fwd_oc32_kernel<false>), grid, dim3(256), 0, s, b, T, H, scale);
+// launches the plan's on-chip-QKV forward (mmt_attn_plan checked the fields and sized the grid)
+hipError_t mmt_attn_oc_launch_plan(const AttnBatch& b, const AttnLaunch& l, int T, int H, float scale, hipStream_t s) {
+  const dim3 grid(l.gx, l.gy, l.gz), wg(l.wg);
+  switch (attn_key(l)) {
+#define X(D) \
+  case attn_key(ATTN_OC32_FWD, 0, D): hipLaunchKernelGGL((attn_fwd_oc32_kernel<D>), grid, wg, 0, s, b, T, H, scale); break;
+    ATTN_OC32_OPS(X)
+#undef X
+    default: return hipErrorInvalidValue;
+  }
   return hipGetLastError();
 }

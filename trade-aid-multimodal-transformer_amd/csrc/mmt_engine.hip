@@ -20,6 +20,7 @@
 #include "mmt.h"
 #include "mmt_common.h"
 #include "mmt_gemm_plan.h"
+#include "mmt_attn_plan.h"
 #include "mmt_kernels.h"
 
 namespace {
@@ -1389,7 +1390,7 @@ int run_forward(mmt_ctx* c, Runner& r, const int64_t* const* idx, const int64_t*
     // Bit 0: the attention forward makes them from h1 and W2; bit 1: the backward will; both: stage 2 leaves this
     // GEMM and the rows are never written. The same for every layer, kept in c->onchip for the backward.
     int oc = 0;
-    if (c->onchip_req && fuse_qkv2 && kn.attn_qkv2 && mmt_attn_bwd_fuses_qkv2(ab, T, hs) && !(ldh1 & 7)) {
+    if (c->onchip_req && fuse_qkv2 && kn.attn_qkv2 && mmt_attn_bwd_fuses_qkv2(ab, B, T, H, hs) && !(ldh1 & 7)) {
       oc = c->onchip_req;
       for (int i = 0; i < M; ++i)
         if (((uintptr_t)r.b16(a[i].h1) | (uintptr_t)r.P(x[i].w2)) & 15) oc = 0;
@@ -2057,7 +2058,7 @@ int run_backward_stage(mmt_ctx* c, Runner& r, int stage, const float* loss_grads
   });
   // hs 32: the Q/K/V stage-2 backward runs in the attention kernel's epilogue (dQ / dK / dV stay on chip:
   // dh1, dW2, db1 leave it), so the separate qkv2 backward and its gqkv round trip go
-  const bool q2 = kn.attn_qkv2 && mmt_attn_bwd_fuses_qkv2(ab, T, hs);
+  const bool q2 = kn.attn_qkv2 && mmt_attn_bwd_fuses_qkv2(ab, r.B, T, H, hs);
   if (q2)
     for (int i = 0; i < M; ++i) {
       AttnProblem& q = ab.p[i];

@@ -281,21 +281,12 @@ struct AttnBatch {
 };
 hipError_t mmt_launch_attn_fwd(const AttnBatch& b, int B, int T, int H, int hs, float scale, hipStream_t s);
 hipError_t mmt_launch_attn_bwd(const AttnBatch& b, int B, int T, int H, int hs, float scale, hipStream_t s);
-// true when mmt_launch_attn_bwd runs this batch on the one-pass hs-32 kernel with one KV stream, which
-// can take the Q/K/V stage-2 backward in its epilogue (AttnProblem::q2_*)
-bool mmt_attn_bwd_fuses_qkv2(const AttnBatch& b, int T, int hs);
-// hs 64 dK/dV pass streaming the query slices through an LDS-DMA ring (mmt_attn2.hip)
-// variant (the mmt_attn_set_ring bits): 4 = 3 waves per SIMD (default), else 2
-hipError_t mmt_attn_bwd_dkdv_ring64(const AttnBatch& b, int B, int T, int H, float scale, bool drop, int variant,
-                                    hipStream_t s);
-// hs 64 dQ pass (and D_j) streaming the key slices through an LDS-DMA ring (mmt_attn2.hip)
-hipError_t mmt_attn_bwd_dq_ring64(const AttnBatch& b, int B, int T, int H, float scale, bool drop, hipStream_t s);
-hipError_t mmt_attn_fwd_ring64(const AttnBatch& b, int B, int T, int H, float scale, bool drop, hipStream_t s);
-// hs 32, T <= 256, one KV stream, Q / K / V made on chip (AttnProblem::oc_* set and checked by the caller,
-// mmt_launch_attn_fwd; mmt_attn_oc.hip)
-hipError_t mmt_attn_fwd_oc32(const AttnBatch& b, int B, int T, int H, float scale, bool drop, hipStream_t s);
-// hs 64, T <= 512, one KV stream: dQ, dK, dV in one pass, one workgroup per (batch, head) (mmt_attn2.hip)
-hipError_t mmt_attn_bwd_fused64(const AttnBatch& b, int B, int T, int H, float scale, bool drop, hipStream_t s);
+// (which kernels a batch takes, and whether the backward can fuse the Q/K/V stage 2: mmt_attn_plan.h)
+// launch one entry of that plan whose kernel lives in mmt_attn2.hip / mmt_attn_oc.hip; hipErrorInvalidValue for an
+// instantiation that is not built
+struct AttnLaunch;
+hipError_t mmt_attn2_launch_plan(const AttnBatch& b, const AttnLaunch& l, int T, int H, float scale, hipStream_t s);
+hipError_t mmt_attn_oc_launch_plan(const AttnBatch& b, const AttnLaunch& l, int T, int H, float scale, hipStream_t s);
 // fill dmask[j] (j < nstreams) of every problem with drop_thr != 0 from its counter hash
 hipError_t mmt_launch_attn_mask(const AttnBatch& b, int B, int T, int H, hipStream_t s);
 

@@ -5,6 +5,7 @@
 
 #include "mmt.h"
 #include "mmt_gemm_plan.h"
+#include "mmt_attn_plan.h"
 #include "mmt_kernels.h"
 
 static int st(hipError_t e) { return e == hipSuccess ? MMT_OK : MMT_ERR_HIP; }
@@ -301,6 +302,49 @@ int mmt_op_attention_bwd(void* stream, int32_t B, int32_t T, int32_t H, int32_t 
   return mmt_op_attention_bwd_drop(stream, B, T, H, hs, nstreams, q, q_ld, k, v, kv_ld, kv_hstride, o, o_ld, oj, lse,
                                    dout, dout_ld, dvec, dq, dq_ld, dk, dv, dkv_ld, dkv_hstride, nullptr, 0, 0, 0, 0.f,
                                    nullptr);
+}
+
+// The launch plan of an AttnBatch made from numbers alone (no stream, no device memory, no HIP call): what
+// mmt_launch_attn_fwd / _bwd / _mask would launch for it. Pointers the checks want are a dummy that is never read;
+// the leading dimensions go in as given, so a span of 2^31 bytes needs no memory behind it.
+int mmt_op_attention_plan(int32_t pass, int32_t count, int32_t B, int32_t T, int32_t H, int32_t hs,
+                          const int32_t* nstreams, const int32_t* ld, int32_t flags, int32_t* plan) {
+  if (pass < 0 || pass > 2 || count < 0 || count > MMT_MAX_GROUP || !plan || (count && !nstreams)) return MMT_ERR_INVALID;
+  alignas(16) static char dummy[32];
+  const auto at = [&](int bit) { return dummy + ((flags >> bit) & 1 ? 8 : 0); };
+  const int C = H * hs;
+  const int dflt[10] = {C, C, hs, C, C, C, C, hs, C, 3 * H * 16};
+  int v[10];
+  for (int i = 0; i < 10; ++i) v[i] = ld && ld[i] ? ld[i] : dflt[i];
+  AttnBatch b{};
+  b.count = count;
+  if (flags & 0x800) { b.det.base = (float*)dummy; b.det.cap = INT64_MAX; }
+  for (int g = 0; g < count; ++g) {
+    AttnProblem& p = b.p[g];
+    p.nstreams = nstreams[g];
+    p.q = (const bf16_t*)at(12); p.q_ld = v[0]; p.kv_ld = v[1]; p.kv_hstride = v[2];
+    p.o = (bf16_t*)at(15); p.o_ld = v[3];
+    p.dout = (const bf16_t*)at(13); p.dout_ld = v[4];
+    p.dq = (bf16_t*)at(14); p.dq_ld = v[5]; p.dkv_ld = v[6]; p.dkv_hstride = v[7];
+    if ((flags >> g) & 1) { p.drop_thr = 1; p.drop_scale = 1.f; }
+    for (int j = 0; j < p.nstreams && j < MMT_MAX_STREAMS; ++j) {
+      p.k[j] = p.v[j] = (const bf16_t*)dummy;
+      p.oj[j] = p.dk[j] = p.dv[j] = (bf16_t*)dummy;
+      p.lse[j] = p.dvec[j] = (float*)dummy;
+      p.dmask[j] = (uint32_t*)dummy;
+    }
+    if (flags & 0x100) {
+      p.q2_h1 = (const bf16_t*)dummy; p.q2_dh1 = (bf16_t*)dummy; p.q2_ld = v[9];
+      p.q2_w2 = (const float*)dummy; p.q2_dw2 = p.q2_db1 = (float*)dummy;
+    }
+    if (flags & 0x200) { p.oc_h1 = (const bf16_t*)dummy; p.oc_ld = v[9]; p.oc_w2 = (const float*)dummy; }
+    if (flags & 0x400) { p.dq32 = (float*)dummy; p.dq32_ld = v[8]; }
+  }
+  const AttnPlan pl = pass == 2 ? mmt_attn_mask_plan(b, B, T, H)
+                                : mmt_attn_plan(b, B, T, H, hs, pass == 1, (flags & 0x10000) ? ATTN_ASSUME_Q2 : 0);
+  static_assert(sizeof(AttnPlan) == ATTN_PLAN_INTS * sizeof(int32_t), "AttnPlan is all ints");
+  memcpy(plan, &pl, sizeof(pl));
+  return MMT_OK;
 }
 
 // KV-cache decode attention (mmt_decode.hip), the launcher mmt_decode_step calls; everything the kernel

@@ -286,6 +286,8 @@ _SIGS = {
     "mmt_op_attention_fwd_h1": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp]),
     "mmt_op_attention_bwd_h1": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32,
                                         c_vp, c_vp, c_vp]),
+    "mmt_op_attention_plan": (c_i32, [c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(c_i32),
+                                      ctypes.POINTER(c_i32), c_i32, ctypes.POINTER(c_i32)]),
     "mmt_op_qkv2_fwd": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_i32]),
     "mmt_op_qkv2_bwd": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp]),
     "mmt_op_colsum": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_f32]),
